@@ -40,7 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-# What cannot be shown on the driver's GPU box, said in the line itself (VERDICT r5 "Next 7"): /root/reference does not
+# What cannot be shown on the driver's GPU box, said in the line itself (VERDICT r5 "Next 7"): the reference does not
 # travel, so `kind` is "port" there; the reference itself was timed beside the port on a builder box in round 5.
 CPU_BASELINE_NOTE = ("kind 'port' = the oracle's restatement of the reference's algorithm (the reference cannot travel to "
                      "this box); the reference itself, pygsp 0.6.1, measured on a builder MI355X box in round 5: "
@@ -112,7 +112,32 @@ def parse():
     p.add_argument("--evaluation", choices=["recurrence", "newton"], default="recurrence",
                    help="recurrence = the reference's three-term Chebyshev recurrence (headline); "
                         "newton = same polynomial, Newton form (extra line 'newton_form')")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed to DIR/<name>.npy: the "
+                        "output block (vertices x signals) of each GPU (rank 0's under a launcher), whole or as a fixed seeded sample of its rows "
+                        "(at most 64 MB in all), so that two builds can be compared output for output")
     return p.parse_args()
+
+
+DUMP_BYTES = 32 << 20   # bytes of output written by --dump-outputs (the row index beside it is small)
+DUMP_SEED = 20240601    # the row sample is a function of (N, nsig, blocks) alone: identical from run to run
+
+
+def dump_outputs(path, blocks):
+    """--dump-outputs: `blocks` maps a name to a host array (N, nsig) of the timed path's output.  Each is written
+    as DIR/<name>.npy in its own float type, whole when all blocks fit DUMP_BYTES, else the same fixed seeded
+    sample of rows from each, sorted; the sampled row numbers are then written as DIR/<name>_rows.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    first = next(iter(blocks.values()))
+    n, row_bytes = first.shape[0], first[0].nbytes
+    keep = max(1, min(n, DUMP_BYTES // max(row_bytes * len(blocks), 1)))
+    rows = None if keep == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+    for name, y in blocks.items():
+        y = np.asarray(y)
+        assert y.dtype in (np.float32, np.float64) and y.shape == first.shape, (name, y.dtype, y.shape)
+        np.save(os.path.join(path, name + ".npy"), y if rows is None else y[rows])
+        if rows is not None:
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
 
 
 def smi_sample(device=0):
@@ -977,6 +1002,8 @@ def main_threads(a):
 
     spans = group.run(timed)
     elapsed = max(t1 for _, t1 in spans) - min(t0 for t0, _ in spans)  # first start to last finish
+    if a.dump_outputs:  # what the last timed step left in every GPU's output block
+        dump_outputs(a.dump_outputs, {"y_gpu{}".format(i): r.by.download((N, nsig), dtype) for i, r in enumerate(ranks)})
 
     # ---- the path's one collective, outside the timed region: every GPU's output block -> context 0 ----
     gather = None
@@ -1157,6 +1184,8 @@ def main():
     from pygsp_amd import engine, graphs
     from tools import torchrun_plumbing as gdist  # launcher plumbing (torch only when WORLD_SIZE > 1)
 
+    if a.no_headline and a.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs writes the headline's output; it has none with --no-headline")
     if a.no_headline:  # profiling passes of single configs
         ctx0 = engine.default_context(local)
         for kv in a.opt:
@@ -1260,6 +1289,8 @@ def main():
         steps_ms_max = gdist.max_over_ranks(steps_ms, rdev)
     else:
         steps_ms_max = steps_ms
+    if a.dump_outputs and rank == 0:  # before the Newton / product forms below write y again
+        dump_outputs(a.dump_outputs, {"y": download_y()})
 
     # ---- same polynomial in Newton form (extra, reported separately; not the headline) ----------
     def time_form(step_form):
@@ -1645,7 +1676,7 @@ def main():
             "multi_core": cpu_all,
         }
         # the reference ITSELF beside it whenever a real pygsp can be imported on this box (installed,
-        # or $PYGSP_PATH - /root/reference does not travel to the driver's GPU box, so the driver's line says "port")
+        # or $PYGSP_PATH - the reference does not travel to the driver's GPU box, so the driver's line says "port")
         ref_run = reference_cpu_baseline(W, lmax, a.scale, K, xs)
         if ref_run is not None:
             t_ref, y_ref, where = ref_run

@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz by running the REAL reference (pygsp v0.6.1 from /root/reference).
+"""Generate tests/golden/*.npz by running the REAL reference (pygsp v0.6.1, the checkout named by $PYGSP_PATH).
 
-Run in the build container only (the GPU box has no /root/reference):
-    python tests/golden/gen_golden.py
-The fixtures are committed; tests read them, never /root/reference.
+Run where a checkout of the reference is at hand:
+    PYGSP_PATH=path/to/reference python tests/golden/gen_golden.py
+The fixtures are committed; tests read them, never the reference.
 """
 import os
 import sys
 
 import numpy as np
 
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["PYGSP_PATH"])
 os.environ.setdefault("MPLBACKEND", "agg")
 import pygsp  # noqa: E402
 from pygsp import filters, graphs  # noqa: E402

@@ -1,7 +1,7 @@
 """pytest plugin (test infrastructure, loaded with `-p seam_device_plugin`): the REAL pygsp's own test files on the
 REAL device - `pygsp_amd.plugin.install(pygsp)` with nothing replaced.  Used by tests/test_gpu_b_real_pygsp.py,
-which arms itself only on a box that has both a GPU and an importable pygsp (the reference checkout or an
-installed package); tests/seam_plugin.py is the CPU form of the same seam with an oracle-backed device object.
+which arms itself only on a box that has both a GPU and an importable pygsp (an installed package or a checkout
+named by $PYGSP_PATH); tests/test_seam_real_pygsp.py is the CPU form of the same seam on a pygsp-shaped stand-in.
 
 The number of calls that went through the seam is written to $GSPX_SEAM_REPORT at session end."""
 import json

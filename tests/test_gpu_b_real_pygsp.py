@@ -1,7 +1,6 @@
 """The REAL pygsp on the REAL device (VERDICT r3 Missing 6): `plugin.install(pygsp)` + libgspx executing together.
-Self-arming, like the two >= 2-GPU tests: it needs an importable pygsp - an installed package, $PYGSP_PATH, or the
-reference checkout at /root/reference - next to a GPU.  The builder's GPU boxes carry neither (only /root/repo
-travels), so there it skips; on a box that has both it runs the reference's own `pygsp/tests/test_filters.py`
+Self-arming, like the two >= 2-GPU tests: it needs an importable pygsp - an installed package, or a checkout named
+by $PYGSP_PATH - next to a GPU.  Where there is none it skips; on a box that has both it runs the reference's own `pygsp/tests/test_filters.py`
 through the patched seam on the device and the doctest chain of filter.py:232-256 with device-resident arrays."""
 import importlib.util
 import json
@@ -17,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 def _pygsp_location():
     """(extra sys.path entry or None, directory of pygsp's tests or None) of an importable real pygsp."""
-    for extra in (os.environ.get("PYGSP_PATH"), None, "/root/reference"):
+    for extra in (os.environ.get("PYGSP_PATH"), None):
         if extra is not None and not os.path.isdir(os.path.join(extra, "pygsp")):
             continue
         if extra is None:
@@ -34,7 +33,7 @@ def _pygsp_location():
 
 EXTRA, REF_TESTS = _pygsp_location()
 needs_pygsp = pytest.mark.skipif(EXTRA is False, reason="needs an importable pygsp next to the GPU (installed, "
-                                                        "$PYGSP_PATH or /root/reference): not on this box")
+                                                        "or $PYGSP_PATH): not on this box")
 
 
 def _env(tmp_path):

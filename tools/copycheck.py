@@ -1,15 +1,14 @@
 #!/usr/bin/env python3
 """How many code lines of the Python mirror are character-identical to lines of the reference?
 (the mirror had been written with the reference open; the bar is < 10 % identical code
-lines, signatures and exception strings aside.)  Needs /root/reference; CPU only.
+lines, signatures and exception strings aside.)  Needs a checkout of the reference; CPU only.
 
-usage: tools/copycheck.py [--show] file.py ..."""
+usage: tools/copycheck.py --ref path/to/pygsp [--show] [--body] file.py ..."""
 import glob
 import io
 import sys
 import tokenize
 
-REF = "/root/reference/pygsp"
 TRIVIAL = {"else:", "try:", "return", "pass", "continue", "break", ")", "(", "]", "[", "}", "{", "finally:"}
 
 
@@ -35,9 +34,13 @@ def code_lines(path):
 
 def main():
     show = "--show" in sys.argv
-    files = [a for a in sys.argv[1:] if not a.startswith("--")]
+    args = sys.argv[1:]
+    if "--ref" not in args or args.index("--ref") + 1 >= len(args):
+        raise SystemExit(__doc__)
+    ref_dir = args.pop(args.index("--ref") + 1)
+    files = [a for a in args if not a.startswith("--")]
     ref = set()
-    for f in glob.glob(REF + "/**/*.py", recursive=True):
+    for f in glob.glob(ref_dir + "/**/*.py", recursive=True):
         if "/tests/" not in f:
             ref.update(code_lines(f))
     for f in files:

@@ -67,6 +67,23 @@ int gspx_laplacian_apply_dev(gspx_graph* g, int64_t Nsig, const void* x_dev, voi
  * graph.py:642-702 (a scalar for one signal). */
 int gspx_dirichlet_energy_dev(gspx_graph* g, int64_t Nsig, const void* x_dev, double* gram_host,
                               double* kernel_ms);
+/* ---- dense fp64 panel primitives (partial Fourier basis, pygsp_amd/fourier.py) ---------------------------
+ * Panels: fp64 DEVICE pointers, row-major, N rows, leading dimension ld* >= width (elements); widths 1..512; any
+ * N >= 0.  Matrix-core (f64 MFMA) kernels; every reduction goes through per-workgroup partials and a fixed-order
+ * second pass, so the same inputs give the same bits on every call.  Vertex order: whatever the caller's panels use.
+ * C_host (na x nb, row-major, HOST) = A^T B. */
+int gspx_panel_gram_dev(gspx_ctx* ctx, int64_t N, const double* A, int64_t lda, int na, const double* B, int64_t ldb,
+                        int nb, double* C_host, double* kernel_ms);
+/* Y = X Q, Q (p x q, row-major, HOST) staged in LDS tiles; Y must not overlap X (GSPX_ERR_INVALID). */
+int gspx_panel_combine_dev(gspx_ctx* ctx, int64_t N, const double* X, int64_t ldx, int p, const double* Q_host, int q,
+                           double* Y, int64_t ldy, double* kernel_ms);
+/* out_host[i] (HOST) = || LX[:, i] - theta_host[i] X[:, i] ||_2, both panels read once (no ||LX||^2 - theta^2). */
+int gspx_panel_residual_norms_dev(gspx_ctx* ctx, int64_t N, const double* X, const double* LX, int64_t ld, int p,
+                                  const double* theta_host, double* out_host, double* kernel_ms);
+/* Y[:, 0:w] = X[:, 0:w] row by row (hipMemcpy2DAsync), e.g. a column block of a wider panel out or back in;
+ * Y must not overlap X.  kernel_ms of all four: the device work only, not the small host copies of Q / theta / C. */
+int gspx_panel_copy_dev(gspx_ctx* ctx, int64_t N, const double* X, int64_t ldx, int w, double* Y, int64_t ldy,
+                        double* kernel_ms);
 /* Tikhonov regression with tau > 0 (pygsp/learning.py:324-337): solves (diag(M) + tau L) x = M y,
  * one conjugate-gradient run per column with scipy.sparse.linalg.cg's recurrence and stopping rule
  * (x0 = 0, ||r|| < max(atol, rtol ||b||); scipy's defaults are rtol 1e-5, atol 0, maxiter 10 N).

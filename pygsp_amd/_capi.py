@@ -80,6 +80,11 @@ SIGNATURES = {
     "gspx_graph_download_internal": (_c.c_int, [_P, _P, _P]),
     "gspx_laplacian_apply_dev": (_c.c_int, [_P, _c.c_int64, _P, _P, _P]),
     "gspx_dirichlet_energy_dev": (_c.c_int, [_P, _c.c_int64, _P, _P, _P]),
+    # dense fp64 panel primitives of the partial Fourier basis (pygsp_amd/fourier.py)
+    "gspx_panel_gram_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int64, _c.c_int, _P, _P]),
+    "gspx_panel_combine_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int, _P, _c.c_int64, _P]),
+    "gspx_panel_residual_norms_dev": (_c.c_int, [_P, _c.c_int64, _P, _P, _c.c_int64, _c.c_int, _P, _P, _P]),
+    "gspx_panel_copy_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int64, _P]),
     "gspx_tikhonov_cg_dev": (_c.c_int, [_P, _c.c_double, _P, _c.c_int64, _P, _P, _c.c_double,
                                          _c.c_double, _c.c_int64, _P, _P]),
     "gspx_graph_n_edges": (_c.c_int, [_P, _P]),

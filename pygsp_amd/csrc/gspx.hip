@@ -413,6 +413,7 @@ struct gspx_ctx {
   DevMem ws_r;      // accumulators
   DevMem ws_w;      // per-step flush weights / combine coefficients
   DevMem io_x, io_y;  // staging for the host-pointer entry point
+  DevMem ws_spec;     // small matrices and reduction partials of the panel primitives (gspx_spectral.hip.h)
   HostPipe* pipe = nullptr;  // its pipelined form (created on first use)
   CopyStage* copy = nullptr; // staged transfers of large buffers (created on first use)
   bool counted = false;      // this context is in g_live_ctx
@@ -594,6 +595,7 @@ extern "C" int gspx_ctx_destroy(gspx_ctx* ctx) {
   ctx->ws_w.release();
   ctx->io_x.release();
   ctx->io_y.release();
+  ctx->ws_spec.release();
   if (ctx->pipe) {
     ctx->pipe->destroy();
     delete ctx->pipe;
@@ -3221,3 +3223,4 @@ extern "C" int gspx_ctx_tune_placement(gspx_graph* g, double lmax, int M, const 
 #include "gspx_ops.hip.h"
 #include "gspx_knn.hip.h"
 #include "gspx_setup.hip.h"
+#include "gspx_spectral.hip.h"

@@ -198,7 +198,9 @@ class Graph:
 
     def _forget_spectrum(self):
         """Everything derived from the Laplacian's spectrum (graph.py:602-609)."""
+        self._release_basis_dev()
         self._lmax = self._lmax_method = self._e = self._U = None
+        self.fourier_stats = None
 
     # ---- adjacency -----------------------------------------------------------------------------
     @property
@@ -452,23 +454,141 @@ class Graph:
             candidates.append(np.max(deg + W.dot(deg) / deg))
         return min(candidates)
 
-    def compute_fourier_basis(self):
-        """Dense eigendecomposition (fourier.py:97-195) - host LAPACK, for small graphs / tests."""
-        if self._U is None:
-            lam, vec = np.linalg.eigh(self.L.toarray().astype(np.float64))
-            if abs(lam[0]) < 1e-9:
-                lam[0] = 0
-            self._e, self._U = lam, vec
-            self._lmax, self._lmax_method = lam[-1], "fourier"
+    def compute_fourier_basis(self, n_eigenvectors=None, *, method="auto", tol=1e-10, maxiter=100, seed=0,
+                              degree=(10, 300)):
+        """The (partial) Fourier basis of L (fourier.py:97-195), cached in ``G.e`` / ``G.U``.
+
+        ``n_eigenvectors=None`` or ``N``: the dense host eigendecomposition, sets ``lmax`` (method 'fourier').
+        A partial request (k < N) keeps a cached basis of at least k vectors; otherwise `method` picks the solver:
+        'device' - Chebyshev-filtered subspace iteration on the float64 device graph (pygsp_amd.fourier), residuals
+        ||L u_i - e_i u_i|| <= tol * b with b the rigorous upper bound of lambda_max, ValueError after `maxiter`
+        iterations, filter degree per iteration within `degree`, start block from `seed`; 'dense' - host eigh,
+        sliced; 'auto' - 'device' when N >= 2048 and the block (k plus guard vectors) is at most N / 4.
+        A partial basis leaves ``lmax`` alone; e[0] is checked to be within 1e-5 of zero and set to zero, and each
+        column's largest-magnitude entry is made positive."""
+        N = self.n_vertices
+        k = N if n_eigenvectors is None else int(n_eigenvectors)
+        if k == N:
+            if self._U is None or self._U.shape[1] < N:
+                self._release_basis_dev()
+                lam, vec = np.linalg.eigh(self.L.toarray().astype(np.float64))
+                if abs(lam[0]) < 1e-9:
+                    lam[0] = 0
+                self._e, self._U = lam, vec
+                self._lmax, self._lmax_method = lam[-1], "fourier"
+            return
+        if not 1 <= k < N:
+            raise ValueError("n_eigenvectors must be in 1..{}, got {}".format(N, n_eigenvectors))
+        if method not in ("auto", "device", "dense"):
+            raise ValueError("method must be 'auto', 'device' or 'dense', got {!r}".format(method))
+        if self._U is not None and k <= len(self._e):
+            return
+        from . import fourier
+        if method == "device" or (method == "auto" and fourier.use_device(N, k)):
+            dev = self.device_graph(np.float64)
+            e, U, U_dev, stats = fourier.device_partial_basis(dev, k, self._get_upper_bound(), tol=tol,
+                                                              maxiter=maxiter, seed=seed, degree=degree)
+            self._release_basis_dev()
+            self._e, self._U, self._U_dev, self.fourier_stats = e, U, (dev, U_dev), stats
+            return
+        lam, vec = np.linalg.eigh(self.L.toarray().astype(np.float64))
+        e, U = np.array(lam[:k]), np.array(vec[:, :k])
+        fourier.finish_partial(e, U)
+        self._release_basis_dev()
+        self._e, self._U, self.fourier_stats = e, U, None
+
+    def _release_basis_dev(self):
+        """Drop the device copy of U: (float64 DeviceGraph, fourier.DevicePanel) or None."""
+        held = getattr(self, "_U_dev", None)
+        self._U_dev = None
+        if held is not None:
+            dev, panel = held
+            if panel.buf is not None:
+                dev.ctx.give(panel.buf)
+                panel.buf = None
+
+    def _basis_on_device(self):
+        """(float64 DeviceGraph, DevicePanel N x n of U): the solver's copy, or U uploaded once."""
+        if self._U_dev is None:
+            from . import fourier
+            dev = self.device_graph(np.float64)
+            be = fourier.DeviceBackend(dev, 1.0)
+            self._U_dev = (dev, be.from_host(self.U))
+        return self._U_dev
+
+    def gft(self, s):
+        """Graph Fourier transform U^T s (fourier.py:197-230): numpy input on the host, exactly the reference's
+        arithmetic.  A float64 engine.DeviceArray is read on the device (gspx_panel_gram_dev against the device copy
+        of U) and the result is a DeviceArray of shape (n, ...) for a basis of n vectors; the n x Nsig coefficients
+        themselves make a host round trip (the Gram entry point returns them to the host, they are uploaded again)."""
+        if isinstance(s, engine.DeviceArray):
+            return self._transform_device(s, inverse=False)
+        s = self._check_signal(s)
+        U = np.conjugate(self.U)  # True Hermitian. (Although U is often real.)
+        return np.tensordot(U, s, ([0], [0]))
+
+    def igft(self, s_hat):
+        """Inverse transform U s_hat (fourier.py:232-264).  The first axis of s_hat runs over the basis vectors
+        (N of them for a full basis, as in the reference).  A float64 DeviceArray gives a DeviceArray: the small
+        n x Nsig coefficients are downloaded (they are the Q of gspx_panel_combine_dev, a host matrix) and the
+        N x Nsig product is formed on the device."""
+        if isinstance(s_hat, engine.DeviceArray):
+            return self._transform_device(s_hat, inverse=True)
+        n = self.U.shape[1]
+        arr = np.asanyarray(s_hat)
+        if arr.ndim == 0 or arr.shape[0] != n:
+            raise ValueError("First dimension must be the number of basis vectors "
+                             "{}, got {}.".format(n, arr.shape))
+        return np.tensordot(self.U, arr, ([1], [0]))
+
+    def _transform_device(self, a, inverse):
+        from . import fourier
+        if a.dtype != np.float64:
+            raise TypeError("gft / igft of a device array need float64 signals (got {}); fp32 is not "
+                            "supported".format(a.dtype))
+        n = self.U.shape[1]
+        if n > fourier.MAX_BLOCK:
+            raise ValueError("gft / igft on the device take bases of at most {} vectors, this one has {}"
+                             .format(fourier.MAX_BLOCK, n))
+        rows_in, rows_out = (n, self.N) if inverse else (self.N, n)
+        if a.cube[0] != rows_in:
+            raise ValueError("First dimension must be {}, got {}.".format(rows_in, a.shape))
+        dev, U = self._basis_on_device()
+        ctx = dev.ctx
+        if a.ctx is not ctx:
+            raise ValueError("the device array lives on another context than the graph's Fourier basis")
+        _, S, F = a.cube
+        shape = (rows_out,) + tuple(a.shape[1:])
+        if inverse:
+            hat = a.numpy().reshape(n, S, F)  # n x S x F coefficients: small, they travel to the host as Q
+            out = engine.DeviceArray.empty(ctx, (rows_out, S, F), np.float64)
+            for f in range(F):
+                for j0 in range(0, S, fourier.MAX_BLOCK):
+                    j1 = min(S, j0 + fourier.MAX_BLOCK)
+                    if self.N:
+                        fourier.panel_combine(ctx, self.N, U.ptr, U.ld, n, hat[:, j0:j1, f],
+                                              out.ptr + 8 * (f * self.N * S + j0), S)
+        else:
+            res = np.zeros((n, S, F))
+            for f in range(F):
+                for j0 in range(0, S, fourier.MAX_BLOCK):
+                    j1 = min(S, j0 + fourier.MAX_BLOCK)
+                    res[:, j0:j1, f] = fourier.panel_gram(ctx, self.N, U.ptr, U.ld, n, a.ptr + 8 * (f * self.N * S + j0),
+                                                          S, j1 - j0)[0]
+            out = engine.DeviceArray.from_host(ctx, res)
+        out.shape = shape
+        return out
 
     @property
     def e(self):
-        self.compute_fourier_basis()
+        if self._U is None:  # (a cached partial basis is returned as it is, fourier.py:156)
+            self.compute_fourier_basis()
         return self._e
 
     @property
     def U(self):
-        self.compute_fourier_basis()
+        if self._U is None:
+            self.compute_fourier_basis()
         return self._U
 
     def __repr__(self):

@@ -171,8 +171,42 @@ def _filters_logger(bank):
     return logging.getLogger(type(bank).__module__)
 
 
+def _compute_fourier_basis_on_device(self, n_eigenvectors=None):
+    """``Graph.compute_fourier_basis`` of the reference (fourier.py:97-195) with its partial branch on the device: a
+    request for k < N vectors that pygsp_amd.fourier.use_device sends there (N >= 2048, a block of at most N / 4) runs
+    Chebyshev-filtered subspace iteration on the graph's float64 device Laplacian instead of ARPACK
+    (eigsh(L, k, which='SM'), fourier.py:174-175) and is stored in ``_e`` / ``_U``; a cached basis of at least k
+    vectors is kept (fourier.py:156).  Everything else - full bases, small graphs - is the reference's own code."""
+    from . import fourier
+    n = self.n_vertices if n_eigenvectors is None else int(n_eigenvectors)
+    if 1 <= n < self.n_vertices and fourier.use_device(self.n_vertices, n):
+        if self._U is not None and n <= len(self._e):
+            return
+        e, U, U_dev, _ = fourier.device_partial_basis(device_graph_for(self, dtype=np.float64), n,
+                                                      self._get_upper_bound())
+        U_dev.buf.free()  # (the real Graph keeps host arrays only)
+        self._e, self._U = e, U
+        return
+    return _saved_on(type(self))["compute_fourier_basis"](self, n_eigenvectors)
+
+
+def _patch_graph_class(graph_cls, lmax_device, fourier):
+    """Replace estimate_lmax (lmax='device') and compute_fourier_basis (fourier=True) on the reference's Graph class;
+    whatever was patched before and is not asked for now is restored."""
+    _restore(graph_cls, tuple(graph_cls.__dict__.get(_SAVED, ())))
+    wanted = {}
+    if lmax_device:
+        wanted["estimate_lmax"] = _estimate_lmax_on_device
+    if fourier:
+        wanted["compute_fourier_basis"] = _compute_fourier_basis_on_device
+    if wanted:
+        setattr(graph_cls, _SAVED, {n: getattr(graph_cls, n) for n in wanted})
+        for n, fn in wanted.items():
+            setattr(graph_cls, n, fn)
+
+
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
-            tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None):
+            tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -186,7 +220,9 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     reference's three-term recurrence, approximations.py:99-112), 'newton' (the same polynomial in Newton form:
     fewer panel passes per order) or 'auto' (Newton where it is faster and filters.newton_guard() clears the
     polynomial for the compute dtype, the recurrence otherwise); None (default): pygsp_amd.filters.EVALUATION,
-    which is 'recurrence' unless filters.set_evaluation() changed it."""
+    which is 'recurrence' unless filters.set_evaluation() changed it.
+    `fourier` (default False): also replace ``Graph.compute_fourier_basis`` so that partial requests on large graphs
+    run on the device (pygsp_amd.fourier); full bases and small graphs keep the reference's code."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -219,12 +255,8 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     elif filter_cls is not None:
         _restore(filter_cls, ("filter", "compute_frame"))
     graph_cls = getattr(getattr(pygsp_module, "graphs", None), "Graph", None)
-    if lmax == "device" and graph_cls is not None:
-        if _SAVED not in graph_cls.__dict__:
-            setattr(graph_cls, _SAVED, {"estimate_lmax": graph_cls.estimate_lmax})
-        graph_cls.estimate_lmax = _estimate_lmax_on_device
-    elif graph_cls is not None:
-        _restore(graph_cls, ("estimate_lmax",))
+    if graph_cls is not None:
+        _patch_graph_class(graph_cls, lmax == "device", bool(fourier))
     return pygsp_module
 
 
@@ -264,7 +296,7 @@ def uninstall(pygsp_module=None):
         _restore(filter_cls, ("filter", "compute_frame"))
     graph_cls = getattr(getattr(pygsp_module, "graphs", None), "Graph", None)
     if graph_cls is not None:
-        _restore(graph_cls, ("estimate_lmax",))
+        _restore(graph_cls, tuple(graph_cls.__dict__.get(_SAVED, ())))
 
 
 def use_backend(name, pygsp_module=None, **install_options):

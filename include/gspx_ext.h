@@ -84,6 +84,23 @@ int gspx_panel_residual_norms_dev(gspx_ctx* ctx, int64_t N, const double* X, con
  * Y must not overlap X.  kernel_ms of all four: the device work only, not the small host copies of Q / theta / C. */
 int gspx_panel_copy_dev(gspx_ctx* ctx, int64_t N, const double* X, int64_t ldx, int w, double* Y, int64_t ldy,
                         double* kernel_ms);
+/* ---- Lanczos filtering (pygsp_amd/lanczos.py; approximations.lanczos_op of the reference) -----------------------
+ * fp64 graphs only (an fp32 graph: GSPX_ERR_INVALID).  x_dev: N x Nsig fp64 (DEVICE, caller's vertex order, leading
+ * dimension ldx >= Nsig), Nsig 0..256 and, with the `order` stack panels and three work panels, within the context's
+ * ws_limit_mb.  V_dev: order x N x Nsig fp64 (DEVICE), written as the Krylov stack in the graph's INTERNAL vertex
+ * order (column c of panel j = q_j of signal c; zero where a column has stopped).  HOST outputs, row-major
+ * order x Nsig: alpha_host (H's diagonal), beta_host (row 0 = ||x||, row k = beta_k, H's off-diagonal), proj_host
+ * (V^T x); steps_host: Nsig ints, the Krylov dimension m of each column (0 for a zero column).  A column stops at
+ * step k when beta_k <= breakdown.  phase_ms (6 doubles or NULL: permute, product, three-term, dots, update,
+ * projection) times every launch with events when given.  The same inputs give the same bits on every call. */
+int gspx_lanczos_krylov_dev(gspx_graph* g, int order, int64_t Nsig, const void* x_dev, int64_t ldx, double breakdown,
+                            void* V_dev, double* alpha_host, double* beta_host, double* proj_host, int32_t* steps_host,
+                            double* phase_ms, double* kernel_ms);
+/* y[f N + n][c] = sum_j weights_host[f][j][c] V_j[n][c] for the Nf filters (HOST weights Nf x order x Nsig), one pass
+ * over the stack V_dev of gspx_lanczos_krylov_dev; y_dev (DEVICE, Nf N rows, leading dimension ldy >= Nsig) in the
+ * caller's vertex order. */
+int gspx_lanczos_combine_dev(gspx_graph* g, int order, int64_t Nsig, const void* V_dev, int Nf,
+                             const double* weights_host, void* y_dev, int64_t ldy, double* kernel_ms);
 /* Tikhonov regression with tau > 0 (pygsp/learning.py:324-337): solves (diag(M) + tau L) x = M y,
  * one conjugate-gradient run per column with scipy.sparse.linalg.cg's recurrence and stopping rule
  * (x0 = 0, ||r|| < max(atol, rtol ||b||); scipy's defaults are rtol 1e-5, atol 0, maxiter 10 N).

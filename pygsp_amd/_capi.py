@@ -85,6 +85,10 @@ SIGNATURES = {
     "gspx_panel_combine_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int, _P, _c.c_int64, _P]),
     "gspx_panel_residual_norms_dev": (_c.c_int, [_P, _c.c_int64, _P, _P, _c.c_int64, _c.c_int, _P, _P, _P]),
     "gspx_panel_copy_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int64, _P]),
+    # Lanczos filtering (pygsp_amd/lanczos.py)
+    "gspx_lanczos_krylov_dev": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _c.c_int64, _c.c_double, _P, _P, _P, _P, _P,
+                                           _P, _P]),
+    "gspx_lanczos_combine_dev": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _c.c_int, _P, _P, _c.c_int64, _P]),
     "gspx_tikhonov_cg_dev": (_c.c_int, [_P, _c.c_double, _P, _c.c_int64, _P, _P, _c.c_double,
                                          _c.c_double, _c.c_int64, _P, _P]),
     "gspx_graph_n_edges": (_c.c_int, [_P, _P]),

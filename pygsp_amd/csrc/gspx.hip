@@ -3224,3 +3224,4 @@ extern "C" int gspx_ctx_tune_placement(gspx_graph* g, double lmax, int M, const 
 #include "gspx_knn.hip.h"
 #include "gspx_setup.hip.h"
 #include "gspx_spectral.hip.h"
+#include "gspx_lanczos.hip.h"

@@ -1093,6 +1093,18 @@ def _ops_methods():
             bx.free()
         return (x[:, 0] if one_d else x), iters, ms
 
+    def lanczos_basis(self, x, order, breakdown=0.0):
+        """The Krylov stacks of gspx_lanczos_krylov_dev for x (N,) or (N, n), n <= 256, on this float64 graph,
+        downloaded: (V (N, order[, n]) in the caller's vertex order, alpha (order[, n]), beta (order[, n]: row 0 is
+        ||x||, row k beta_k), steps (Krylov dimension per column; an int for 1-D x)).  A column stops at step k when
+        beta_k <= `breakdown`.  For tests at small N."""
+        from . import lanczos
+        x2, one_d = _panel(self, x, self.N, "lanczos_basis")
+        V, alpha, beta, steps = lanczos.device_basis(self, x2, order, breakdown)
+        if one_d:
+            return V[:, :, 0], alpha[:, 0], beta[:, 0], int(steps[0])
+        return V, alpha, beta, steps
+
     def n_edges(self):
         v = ctypes.c_int64(0)
         _capi.check(_capi.load().gspx_graph_n_edges(self._h, ctypes.byref(v)))
@@ -1161,8 +1173,8 @@ def _ops_methods():
         return _edge_op(self, y, n_edges(self), self.N, div_dev, "div")
 
     for f in (laplacian_apply_dev, laplacian_apply, dirichlet_energy_dev, dirichlet_energy,
-              tikhonov_cg_dev, tikhonov_cg, n_edges, edge_list, differential_operator, set_edge_list, grad_dev,
-              div_dev, grad, div):
+              tikhonov_cg_dev, tikhonov_cg, lanczos_basis, n_edges, edge_list, differential_operator, set_edge_list,
+              grad_dev, div_dev, grad, div):
         setattr(DeviceGraph, f.__name__, f)
 
 

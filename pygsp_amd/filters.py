@@ -4,6 +4,7 @@ Mirrors (names, argument meaning, shapes, exceptions):
 
 * ``compute_cheby_coeff``   pygsp/filters/approximations.py:9-55   (host quadrature, K+1 points)
 * ``cheby_op``              pygsp/filters/approximations.py:58-114 -> gspx_cheby_filter (device)
+* ``lanczos_op``            pygsp/filters/approximations.py:228-341 -> gspx_lanczos_krylov_dev / _combine_dev
 * ``Filter.filter`` & co    pygsp/filters/filter.py:146-391, 506-600
 * ``Heat``                  pygsp/filters/heat.py:102-119
 * ``MexicanHat``            pygsp/filters/mexicanhat.py:55-84 (+ utils.compute_log_scales)
@@ -559,6 +560,72 @@ def cheby_op(G, c, signal, **kwargs):
     _record_timing(G, ms, how)
     stacked = np.asarray(y, dtype=np.float64).reshape(coeffs.shape[0] * G.N, x.shape[1])
     return stacked[:, 0] if vector_in else stacked
+
+
+def lanczos_op(f, s, order=30):
+    """Lanczos approximation of the filter bank `f` applied to `s` (approximations.py:228-277), on the GPU.
+
+    `f`: anything with ``G``, ``Nf`` and ``evaluate`` (this package's Filter or the real pygsp one); `s`: (N,) or
+    (N, Nv), a host array or a float64 engine.DeviceArray.  Returns (N Nf,) or (N Nf, Nv), row i N + n = filter i
+    at vertex n; a DeviceArray in gives a DeviceArray out.  Per column x: the Krylov basis V of L from x with full
+    reorthogonalisation, H = V^T L V = Uh Eh Uh^T (Eh clipped at 0), y_i = V Uh f_i(Eh) Uh^T (V^T x), all in float64
+    (an fp32 graph is filtered by its float64 device graph).  Differences from the reference, on purpose:
+    Nf is read from ``f.Nf`` (the reference reads ``f.g``, which Filter no longer has); a Krylov breakdown
+    (beta_k <= 64 eps b, b the upper bound of lambda_max, where the reference tests an absolute np.spacing(1))
+    keeps the m x m leading block of H, so the result is exact when s lies in an invariant subspace (the reference
+    slices H to a non-square matrix and fails); a zero column gives zeros (the reference: NaN)."""
+    from . import engine, lanczos
+    G = f.G
+    order = int(order)
+    if order < 1:
+        raise ValueError("order must be >= 1, got {}".format(order))
+    on_device = isinstance(s, engine.DeviceArray)
+    shape = tuple(s.shape) if on_device else np.shape(s)
+    if not on_device:
+        s = np.asanyarray(s)
+        if np.iscomplexobj(s):
+            raise TypeError("complex signals are not supported by the Lanczos path")
+    if len(shape) not in (1, 2) or shape[0] != G.N:
+        raise ValueError("First dimension must be the number of vertices "
+                         "G.N = {}, got {}.".format(G.N, shape))
+    Nf = int(f.Nf)
+    N = G.N
+    n = 1 if len(shape) == 1 else shape[1]
+    dev = G.device_graph(np.float64) if hasattr(G, "device_graph") else _plugin_graph64(G)
+    out_shape = (N * Nf,) if len(shape) == 1 else (N * Nf, n)
+    be = lanczos.DeviceBackend(dev)
+    bound = G._get_upper_bound()
+    if on_device:
+        if s.dtype != np.float64:
+            raise ValueError("Lanczos filtering needs a float64 DeviceArray, got {}".format(s.dtype))
+        if s.ctx is not dev.ctx:
+            raise ValueError("the DeviceArray does not live on the context of this graph's device Laplacian")
+        x_ptr, keep = s.planes(n, 1)
+        out = engine.DeviceArray.empty(dev.ctx, (N * Nf, n, 1), np.float64)
+        if N * n:
+            lanczos.filter_columns(be, f, (x_ptr, n), n, order, bound, (out.ptr, n))
+        del keep
+        out.shape = out_shape
+        _record_timing(G, be.ms["krylov"] + be.ms["combine"], "lanczos")
+        return out
+    x = np.ascontiguousarray(s.reshape(N, n), dtype=np.float64)
+    if N * n == 0:
+        return np.zeros(out_shape)
+    bx = dev.ctx.upload(x)
+    by = dev.ctx.alloc(N * Nf * n * 8)
+    try:
+        lanczos.filter_columns(be, f, (bx.ptr, n), n, order, bound, (by.ptr, n))
+        y = by.download((N * Nf, n), np.float64)
+    finally:
+        bx.free()
+        by.free()
+    _record_timing(G, be.ms["krylov"] + be.ms["combine"], "lanczos")
+    return y.reshape(out_shape)
+
+
+def _plugin_graph64(G):
+    from . import plugin
+    return plugin.device_graph_for(G, dtype=np.float64)
 
 
 def _rect_coefficients(lo, hi, order):

@@ -205,8 +205,30 @@ def _patch_graph_class(graph_cls, lmax_device, fourier):
             setattr(graph_cls, n, fn)
 
 
+_SAVED_LANCZOS = "_gspx_saved_lanczos"  # (on the approximations module: lanczos_op and its pygsp.filters alias)
+
+
+def _patch_lanczos(pygsp_module, wanted):
+    """Replace approximations.lanczos_op and the pygsp.filters.lanczos_op alias with filters.lanczos_op (wanted), or
+    put back the originals saved by an earlier install (not wanted)."""
+    approx = pygsp_module.filters.approximations
+    saved = approx.__dict__.get(_SAVED_LANCZOS)
+    if wanted:
+        if saved is None:
+            setattr(approx, _SAVED_LANCZOS, {"lanczos_op": getattr(approx, "lanczos_op", None),
+                                             "alias": getattr(pygsp_module.filters, "lanczos_op", None)})
+        approx.lanczos_op = _filters.lanczos_op
+        pygsp_module.filters.lanczos_op = _filters.lanczos_op
+    elif saved is not None:
+        for obj, key in ((approx, "lanczos_op"), (pygsp_module.filters, "alias")):
+            if saved[key] is not None:
+                setattr(obj, "lanczos_op", saved[key])
+        delattr(approx, _SAVED_LANCZOS)
+
+
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
-            tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False):
+            tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
+            lanczos=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -222,7 +244,9 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     polynomial for the compute dtype, the recurrence otherwise); None (default): pygsp_amd.filters.EVALUATION,
     which is 'recurrence' unless filters.set_evaluation() changed it.
     `fourier` (default False): also replace ``Graph.compute_fourier_basis`` so that partial requests on large graphs
-    run on the device (pygsp_amd.fourier); full bases and small graphs keep the reference's code."""
+    run on the device (pygsp_amd.fourier); full bases and small graphs keep the reference's code.
+    `lanczos` (default False): also replace ``approximations.lanczos_op`` and the ``pygsp.filters.lanczos_op`` alias
+    with pygsp_amd.filters.lanczos_op (Lanczos filtering on the device, pygsp_amd.lanczos)."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -257,6 +281,7 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     graph_cls = getattr(getattr(pygsp_module, "graphs", None), "Graph", None)
     if graph_cls is not None:
         _patch_graph_class(graph_cls, lmax == "device", bool(fourier))
+    _patch_lanczos(pygsp_module, bool(lanczos))
     return pygsp_module
 
 
@@ -286,6 +311,7 @@ def uninstall(pygsp_module=None):
     if not _installed:
         _config["evaluation"] = None
     approx = pygsp_module.filters.approximations
+    _patch_lanczos(pygsp_module, False)
     saved = _restore(approx, ("cheby_op",))
     if saved is None:
         return

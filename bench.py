@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py - Chebyshev graph filtering throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
             --master-port P bench.py --gpus N --steps K --warmup W)
+
+A plain run does what its headline figure needs and nothing else: set-up (graph, coefficients, input, the placement
+tuning of the work panels), warm-up, the timed steps, --dump-outputs, the result line.  Everything below that takes
+runs of its own or checks the result - the gather and the RCCL version, parity against the oracle, the Newton and product forms, the mix
+ceiling, copy and stream rates, live HBM traffic, fp32, end to end, the chain, the CPU baselines, the other configs -
+runs with --full only (the --no-* options then skip parts of it).
 
 A "step" is one pass of the hot path over one batch of synthetic input: an order-30 Heat filter
 of 64 signals on a 1M-vertex k=8 sensor graph (~10M stored entries of W) - the north-star
@@ -19,12 +25,12 @@ roofline: ALGORITHMIC bytes per recurrence-step launch (SURVEY.md 8d:
 B_alg = K*(CSR + 3U) + Nf*U, per launch B_alg/K) divided by the average launch duration measured
 with HIP events on the engine's own stream over the timed steps.
 
-cpu_baseline: the oracle PORT (numpy/scipy restatement = the reference's algorithm, scipy's
+cpu_baseline (--full): the oracle PORT (numpy/scipy restatement = the reference's algorithm, scipy's
 csr_matvecs kernel, single-threaded like the reference) on a bounded column sample of the same
 workload, rank 0 at N=1 only; "all_cores" beside it is the same port run by one process per host
 core on disjoint signal columns (the reference itself uses one core).
 
-configs: the other BASELINE.json configurations that fit one GPU (configs[1..3] and one rank's share
+configs (--full): the other BASELINE.json configurations that fit one GPU (configs[1..3] and one rank's share
 of configs[4]), each with its own time, algorithmic roofline fraction and parity against oracle
 columns, appended after the headline keys (N=1 only; --no-configs skips them).
 """
@@ -66,6 +72,9 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: gather, parity, other evaluations, dtypes "
+                        "and configs, calibrations, live traffic, end to end, CPU baselines (a plain run skips them)")
     p.add_argument("--dtype", choices=["f64", "f32"], default="f64",
                    help="arithmetic type (the reference computes in f64)")
     p.add_argument("--vertices", dest="n", type=int, default=1000000)
@@ -116,7 +125,13 @@ def parse():
                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy: the "
                         "output block (vertices x signals) of each GPU (rank 0's under a launcher), whole or as a fixed seeded sample of its rows "
                         "(at most 64 MB in all), so that two builds can be compared output for output")
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:  # a plain run: every extra off, as if each --no-* option had been given
+        for extra in ("no_cpu", "no_gather", "no_newton", "no_mix", "no_e2e", "no_configs", "no_f32", "no_chain",
+                      "no_live_traffic"):
+            setattr(a, extra, True)
+        a.cpu_all_cores = 0
+    return a
 
 
 DUMP_BYTES = 32 << 20   # bytes of output written by --dump-outputs (the row index beside it is small)
@@ -190,7 +205,7 @@ def live_traffic(dtype_flag, timeout_s=150, device=0):
     prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(prof):
         return None
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--dtype", dtype_flag,
+    child = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "1", "--warmup", "0", "--dtype", dtype_flag,
              "--no-cpu", "--no-newton", "--no-mix", "--no-e2e", "--no-configs", "--no-live-traffic", "--no-f32",
              "--calibrate-copy", "--tune-candidates", "0"]
     # a single-process child on ONE GPU (this rank's), whatever launched the parent
@@ -1054,7 +1069,7 @@ def main_threads(a):
             res["error"] = repr(e)
         return res
 
-    calib = group.run(calibrate)
+    calib = group.run(calibrate) if a.full else [{} for _ in ranks]
     # ---- HBM traffic of the step (rocprofv3 child passes on the first GPU) and the CPU baseline, as at N = 1 ----
     traffic = traffic_source = None
     default_workload = (N, nsig, K, a.knn, a.tiles) == (1000000, 64, 30, 8, "auto")
@@ -1087,7 +1102,8 @@ def main_threads(a):
         del Lh, xs, ref, y0
 
     from pygsp_amd import engine
-    seen = engine.comm_info()  # after the gather: the device set ncclCommInitAll built, as RCCL reports it
+    # after the gather: the device set ncclCommInitAll built, as RCCL reports it (loading RCCL takes seconds: --full only)
+    seen = engine.comm_info() if a.full else {"rccl_version": None, "nranks": 0}
     r0 = ranks[0]
     nnz_l = r0.dev.nnz_l
     U = N * nsig * elt
@@ -1186,6 +1202,8 @@ def main():
 
     if a.no_headline and a.dump_outputs:
         raise SystemExit("bench.py: --dump-outputs writes the headline's output; it has none with --no-headline")
+    if a.no_headline and not a.full:
+        raise SystemExit("bench.py: --no-headline runs the other configs only, which is part of --full")
     if a.no_headline:  # profiling passes of single configs
         ctx0 = engine.default_context(local)
         for kv in a.opt:
@@ -1224,7 +1242,7 @@ def main():
     coords, W, knn_info, t_gen_dev, t_graph = rw.coords, rw.W, rw.knn_info, rw.t_gen_dev, rw.t_graph
     G, dev, lmax, c, x, bx, by = rw.G, rw.dev, rw.lmax, rw.c, rw.x, rw.bx, rw.by
     t_gen, knn_diff = None, None
-    if world == 1:  # ... and are checked against the host (KD-tree) construction of the same matrix
+    if world == 1 and a.full:  # ... and are checked against the host (KD-tree) construction of the same matrix
         t0 = time.perf_counter()
         Wh, ch = graphs.sensor_weights(N, k=a.knn, seed=42 + rank)
         t_gen = time.perf_counter() - t0
@@ -1480,14 +1498,15 @@ def main():
     # the streaming-copy rate of THIS box and process, right after the timed region: the recurrence runs at
     # a fixed fraction of it, and it moves by several percent between boxes
     copy_now = None
-    try:
-        copy_now = ctx.bench_copy(1 << 30, 5)
-    except Exception:
-        pass
+    if a.full:
+        try:
+            copy_now = ctx.bench_copy(1 << 30, 5)
+        except Exception:
+            pass
     # N > 1: the slowest and the fastest GPU of the job, for the copy rate, the step and its mix ceiling (every rank
     # measures its own; rank 0's own values are the plain keys)
     spread = None
-    if torch is not None:
+    if torch is not None and a.full:
         def lo_hi(v):
             v = float(v or 0.0)
             return [-gdist.max_over_ranks(-v, rdev), gdist.max_over_ranks(v, rdev)]
@@ -1559,7 +1578,8 @@ def main():
                 "engine_options": a.opt, "gather_tiles": G.tile_stats,
                 # the path's one collective as this run executed it (self-validating on a multi-GPU node: the ranks RCCL
                 # itself reports must equal n_gpus)
-                "gather_impl": gather_impl, "rccl_version": (comm_seen or engine.comm_info())["rccl_version"],
+                "gather_impl": gather_impl,
+                "rccl_version": (comm_seen or engine.comm_info())["rccl_version"] if a.full else None,
                 "rccl_nranks_seen": comm_seen["nranks"] if comm_seen else 0, "launcher_world_size": world,
                 "real_pygsp_on_device": REAL_PYGSP_RECORD,
             },

@@ -168,7 +168,7 @@ def test_two_ranks_on_this_gpu_through_bench():
     # on one device - the attempt (id exchange, communicator creation under the watchdog), the agreement of the
     # ranks on its failure and the fall-back to the launcher's gather all run
     env = dict(os.environ, GSPX_ALL_RANKS_DEVICE0="1", HSA_ENABLE_IPC_MODE_LEGACY="0", GSPX_BENCH_LIB_GATHER="force")
-    res = _torchrun_bench(2, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--vertices", "100000", "--nsig", "16",
+    res = _torchrun_bench(2, ["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--vertices", "100000", "--nsig", "16",
                               "--backend", "gloo", "--no-newton"], env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -202,7 +202,7 @@ def check_multi_line_keys(out, wide):
 def test_multi_gpu_lines_carry_the_single_gpu_keys():
     """The same check on a wide panel (64 fp64 signals: the wide LDS-staged step, so the mix ceiling is measured) for
     the launcher-free form, per device."""
-    res = _run_bench(["--gpus", "2", "--devices", "0,0", "--steps", "2", "--warmup", "1", "--vertices", "100000",
+    res = _run_bench(["--full", "--gpus", "2", "--devices", "0,0", "--steps", "2", "--warmup", "1", "--vertices", "100000",
                       "--nsig", "64", "--no-configs", "--cpu-cols", "4"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -229,10 +229,27 @@ def test_bench_refuses_more_gpus_than_visible():
     assert "refusing" in res.stderr and not [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain `bench.py --gpus 1`: the timed steps, the dumped output and the headline keys; nothing that --full adds."""
+    res = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--vertices", "100000", "--nsig", "16",
+                      "--dump-outputs", str(tmp_path)], timeout=300)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+    out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["unit"] == "vertex*signal*order/s" and out["metric"] and (out["steps"], out["warmup"]) == (2, 1)
+    assert out["value"] == pytest.approx(100000 * 16 * 30 * 1e3 / out["ms_per_step"], rel=1e-9)
+    for key in ("configs", "cpu_baseline", "headline_f32", "end_to_end_host_arrays", "chain3", "parity_vs_oracle",
+                "batch_config4"):
+        assert key not in out, key
+    assert out["newton_form"] is None and out["product_form"] is None and out["gather_ms"] is None
+    assert out["roofline"]["frac"] > 0 and out["roofline"]["copy_GBps_this_run"] is None
+    assert np.load(tmp_path / "y.npy").shape == (100000, 16)
+
+
 def test_bench_threads_two_contexts_on_this_gpu():
     """The launcher-free N > 1 path of bench.py on this box's one GPU: two contexts, two driver threads
     (`--devices 0,0`), barrier-bracketed timing, gspx_gather, parity of BOTH ranks, the strong-scaling batch."""
-    res = _run_bench(["--gpus", "2", "--devices", "0,0", "--steps", "2", "--warmup", "1", "--vertices", "100000",
+    res = _run_bench(["--full", "--gpus", "2", "--devices", "0,0", "--steps", "2", "--warmup", "1", "--vertices", "100000",
                       "--nsig", "16"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -253,7 +270,7 @@ def test_bench_threads_eight_contexts_on_this_gpu():
     """The 8-way form the driver's 8-GPU node would run, dry on this box's one GPU (`--gpus 8 --devices 0,0,0,0,0,0,0,0`):
     eight contexts and driver threads, the weak line, the 64 signals of one graph split 8 x 8 (signal_parallel), the
     batch of BASELINE configs[4] one graph per context, gspx_gather of eight parts - parity on all eight."""
-    res = _run_bench(["--gpus", "8", "--devices", "0,0,0,0,0,0,0,0", "--steps", "2", "--warmup", "1", "--vertices", "100000"],
+    res = _run_bench(["--full", "--gpus", "8", "--devices", "0,0,0,0,0,0,0,0", "--steps", "2", "--warmup", "1", "--vertices", "100000"],
                      timeout=1200)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -298,7 +315,7 @@ def test_bench_all_visible_gpus_through_rccl():
     n = _capi.device_count()
     if n < 2:
         pytest.skip("one GPU visible: cross-device gspx_gather cannot run here")
-    res = _run_bench(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--vertices", "200000", "--nsig", "16"])
+    res = _run_bench(["--full", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--vertices", "200000", "--nsig", "16"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == n and out["rccl_ranks"] == n and "RCCL" in out["gather_impl"]
@@ -314,7 +331,7 @@ def test_comm_gather_real_peers():
         pytest.skip("one GPU visible")
     pytest.importorskip("torch")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = _torchrun_bench(n, ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--vertices", "200000", "--nsig", "16",
+    res = _torchrun_bench(n, ["--full", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--vertices", "200000", "--nsig", "16",
                               "--no-newton"], env, timeout=1200)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])

@@ -255,6 +255,29 @@ def test_bench_refuses_gpus_it_cannot_see():
     assert not [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """A plain `bench.py` run skips every extra, as if each --no-* option had been given; --full runs them all unless
+    a --no-* option says otherwise; --no-headline (configs only) is part of --full."""
+    import subprocess
+    import sys
+
+    import bench
+    extras = ("no_cpu", "no_gather", "no_newton", "no_mix", "no_e2e", "no_configs", "no_f32", "no_chain", "no_live_traffic")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, k) for k in extras) and a.cpu_all_cores == 0
+    assert (a.steps, a.warmup, a.tune_candidates, a.evaluation) == (4, 2, 32, "recurrence")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-f32"])
+    a = bench.parse()
+    assert a.full and a.no_f32 and not any(getattr(a, k) for k in extras if k != "no_f32") and a.cpu_all_cores == -1
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-headline", "--only-config", "c1"], cwd=root,
+                         env=env, capture_output=True, text=True, timeout=300)
+    assert res.returncode != 0 and "--full" in res.stderr
+    assert not [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+
+
 def test_expander_like_tells_random_graphs_from_embedded_ones():
     """engine.expander_like: balls of a random graph (ER, SBM) grow by the mean degree per hop, those of a k-NN graph
     or a grid by a factor near 2 - the test that lets random graphs skip the reverse Cuthill-McKee pass."""

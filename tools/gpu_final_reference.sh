@@ -3,7 +3,7 @@ python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "sm
 timeout 1500 python -m pytest tests -m gpu -q --durations=6 > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -12 $O/pytest_gpu.log
 PYGSP_PATH=$R/_ref_stage timeout 600 python -m pytest tests/test_gpu_b_real_pygsp.py -m gpu -q -rs > $O/pytest_real_pygsp.log 2>&1; echo "real pygsp rc=$?"; tail -3 $O/pytest_real_pygsp.log
 SECONDS=0
-PYGSP_PATH=$R/_ref_stage timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err; echo "bench rc=$? wall=${SECONDS}s"
+PYGSP_PATH=$R/_ref_stage timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err; echo "bench rc=$? wall=${SECONDS}s"
 python - <<'PY'
 import json
 b=json.loads(open("gpurun_out/bench_driver_form.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 cd /tmp
 OUT=$R/gpurun_out/prof_$CFG
 mkdir -p $OUT
-ARGS="--no-headline --only-config $CFG --config-reps 1 --config-oracle-cols 0 --no-cpu --calibrate-copy"
+ARGS="--full --no-headline --only-config $CFG --config-reps 1 --config-oracle-cols 0 --no-cpu --calibrate-copy"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python $R/bench.py $ARGS > $OUT/stats_bench.json 2> $OUT/stats.err
 DEFAULT_PASSES="FETCH_SIZE;WRITE_SIZE;TCC_HIT_sum TCC_MISS_sum;TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum;TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_WRITE_REQ_sum;SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD"
 IFS=';' read -r -a PASSES <<< "${PROF_PASSES:-$DEFAULT_PASSES}"

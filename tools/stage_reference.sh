@@ -4,7 +4,7 @@
 # _ref_stage/ (git-ignored, not gpurun-ignored: it travels with the snapshot like _lib/*.so), is never committed,
 # is not on any product path, and is removed with `tools/stage_reference.sh clean` right after the job.
 #   tools/stage_reference.sh            # stage
-#   gpurun -- 'bash tools/gpu_real_pygsp.sh'
+#   bash tools/gpu_real_pygsp.sh <output dir>   # on the GPU box
 #   tools/stage_reference.sh clean      # remove
 set -e
 cd "$(dirname "$0")/.."

@@ -430,14 +430,6 @@ struct gspx_ctx {
   std::vector<unsigned char> seen_key;   // key of the last eager call (empty: none)
   std::vector<unsigned char> graph_key;  // key the instantiated graph was captured for
   hipGraphExec_t graph_exec = nullptr;
-  // a polynomial program for the batches of the pipelined host-pointer call instead of the recurrence (set by
-  // gspx_poly_program for the duration of its call)
-  const struct BatchProgram* batch_program = nullptr;
-};
-struct BatchProgram {
-  int S;
-  const double *sc, *be, *ga;
-  bool old_is_x;
 };
 
 // any other work on the context invalidates a recorded replay (it may have rewritten the weights,
@@ -1890,6 +1882,65 @@ static int prepare_coff(gspx_graph* g, const Shape& shape, unsigned ld, hipStrea
   return GSPX_OK;
 }
 
+// the widest lane vector, at most v, whose accesses to rows of pitch ld starting at p stay aligned
+template <typename T> static int vec_cap(int v, unsigned ld, const T* p) {
+  while (v > 1 && ((ld % v) != 0 || (((uintptr_t)p / sizeof(T)) % v) != 0)) v /= 2;
+  return v;
+}
+
+// The work panels of a batch of ld signals.  tile_direct: the tile kernels on panels of pitch ld, the last step storing
+// into y.  padded: rows that are not made of 16-byte pieces (or a y the final flush cannot store such pieces into) get
+// work panels of pitch ldw, rounded up to whole pieces, so that the tile kernels take them all the same - zero columns
+// cost little next to kernels that are several times faster - and the result leaves through a copy.  `tiles`: the
+// caller's steps may take the tile kernels at all; `planes`: the panels one tile launch spans (its buffer window stays
+// below 2 GiB).
+struct WorkPanels {
+  bool tile_direct, padded;
+  unsigned ldw;
+};
+template <typename T>
+static WorkPanels work_panels(const gspx_graph* g, const Options& opt, bool tiles, size_t planes, unsigned ld,
+                              const T* y, unsigned ldy) {
+  constexpr unsigned TVEC = 16 / (unsigned)sizeof(T);
+  const unsigned ldp = (ld + TVEC - 1) / TVEC * TVEC;
+  auto window = [&](unsigned w) { return planes * (size_t)g->N * w * sizeof(T) < ((size_t)1 << 31); };
+  // (a single signal on a graph whose matrix stays in the L2s: the sub-wave kernel is the faster one there, 0.125
+  // against 0.150 ms for 30 orders at N = 50k; from ~20 MB of matrix on the padded tile path wins, 0.86 against
+  // 1.19 ms at N = 1M.  Two signals and more: the tile path at every size - 0.15 against 0.18 ms for two fp32
+  // signals at N = 100k.)
+  const bool pad_pays = opt.tile_pad == 2 || ld >= 2 ||
+                        (size_t)g->nnz_int * (sizeof(T) + 4) >= ((size_t)20 << 20);
+  WorkPanels p;
+  p.tile_direct = tiles && tile_usable<T>(g, opt, ld, y, ldy) && window(ld);
+  p.padded = !p.tile_direct && tiles && opt.tile_pad && pad_pays && tile_geometry<T>(g, opt, ldp) && window(ldp);
+  p.ldw = p.padded ? ldp : ld;
+  return p;
+}
+
+// what every plain step (StepArgs) of a batch shares: the graph, the panel geometry and the final store into y
+template <typename T>
+static StepArgs<T> step_base(const gspx_graph* g, unsigned ld, T* y, unsigned ldy) {
+  StepArgs<T> a{};
+  a.rowptr = g->rptr.as<int>();
+  a.col = g->rcol.as<int>();
+  a.val = g->fval.as<T>();
+  a.N = (int)g->N;
+  a.ld = ld;
+  a.curbytes = (u32)((size_t)g->N * ld * sizeof(T));
+  a.y = y;
+  a.ldy = ldy;
+  a.perm = g->has_perm ? g->perm.as<int>() : nullptr;
+  return a;
+}
+
+// the four pool events of a batch, the first recorded at once: copy in | steps | combine or copy out between them
+// (run_batches sums each phase over the batches)
+static int batch_events(gspx_ctx* ctx, size_t& ev_idx, hipEvent_t ev[4]) {
+  for (int i = 0; i < 4; ++i) ev[i] = pool_event(ctx, ++ev_idx);
+  if (!ev[0] || !ev[1] || !ev[2] || !ev[3]) return set_err(GSPX_ERR_HIP, "hipEventCreate failed");
+  HIPCHK(hipEventRecord(ev[0], ctx->stream));
+  return GSPX_OK;
+}
 
 template <typename T>
 static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp, const T* x,
@@ -1900,26 +1951,12 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
   hipStream_t st = ctx->stream;
   const int N = (int)g->N;
   const int K = M - 1;
-  // Rows that are not made of 16-byte pieces (or a y the final flush cannot store such pieces into): the work
-  // panels get padded rows of pitch ldw, so that the tile kernels take them all the same - zero columns cost
-  // little next to kernels that are several times faster - and the result leaves through a copy.
-  constexpr unsigned TVEC = 16 / (unsigned)sizeof(T);
-  const unsigned ldp = (ld + TVEC - 1) / TVEC * TVEC;
-  const bool tile_direct = (deferred || nf == 1) && tile_usable<T>(g, opt, ld, y, ldy);
-  // (a single signal on a graph whose matrix stays in the L2s: the sub-wave kernel is the faster one there, 0.125
-  // against 0.150 ms for 30 orders at N = 50k; from ~20 MB of matrix on the padded tile path wins, 0.86 against
-  // 1.19 ms at N = 1M.  Two signals and more: the tile path at every size - 0.15 against 0.18 ms for two fp32
-  // signals at N = 100k.)
-  const bool pad_pays = opt.tile_pad == 2 || ld >= 2 ||
-                        (size_t)g->nnz_int * (sizeof(T) + 4) >= ((size_t)20 << 20);
-  const bool padded = !tile_direct && (deferred || nf == 1) && opt.tile_pad && pad_pays && tile_geometry<T>(g, opt, ldp);
-  const unsigned ldw = padded ? ldp : ld;
+  const WorkPanels wp = work_panels<T>(g, opt, deferred || nf == 1, 1, ld, y, ldy);
+  const bool tile_direct = wp.tile_direct, padded = wp.padded;
+  const unsigned ldw = wp.ldw;
   const size_t U = (size_t)N * ldw;  // elements per panel
   // vector stores into y need aligned rows: cap the lane vector width accordingly
-  int veccap = 4;
-  while (veccap > 1 && ((ldy % veccap) != 0 || (((uintptr_t)y / sizeof(T)) % veccap) != 0))
-    veccap /= 2;
-  const Shape shape = choose_shape(opt, sizeof(T), ld, veccap);
+  const Shape shape = choose_shape(opt, sizeof(T), ld, vec_cap(4, ldy, y));
   const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
 
   std::vector<PlanStep> plan;
@@ -1954,15 +1991,8 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
   T* slots = ctx->ws_t.as<T>();
   T* racc = ctx->ws_r.as<T>();
 
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-  if (!cap) {
-    e0 = pool_event(ctx, ++ev_idx);
-    e1 = pool_event(ctx, ++ev_idx);
-    e2 = pool_event(ctx, ++ev_idx);
-    e3 = pool_event(ctx, ++ev_idx);
-    if (!e0 || !e1 || !e2 || !e3) return set_err(GSPX_ERR_HIP, "hipEventCreate failed");
-    HIPCHK(hipEventRecord(e0, st));
-  }
+  hipEvent_t ev[4] = {};
+  if (!cap) CHK(batch_events(ctx, ev_idx, ev));
   // LDS-staged gather: one filter with the fused flush
   // (or a filterbank's deferred combine, whose steps are plain recurrence steps into kept slots)
   const bool tile_ok = tile_direct || padded;
@@ -1981,27 +2011,15 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
   } else if (padded) {
     const unsigned nb = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
     hipLaunchKernelGGL((k_permute_in_pad<T>), dim3(nb), dim3(256), 0, st, x, ldx, slots, ldw, ld, N, perm);
-  } else {
-    // permute-in vector width: x rows must be aligned too
-    int pvec = shape.vec;
-    while (pvec > 1 && ((ldx % pvec) != 0 || (((uintptr_t)x / sizeof(T)) % pvec) != 0)) pvec /= 2;
-    launch_permute_in<T>(x, ldx, slots, ld, N, perm, pvec, st);
+  } else {  // (permute-in vector width: x rows must be aligned too)
+    launch_permute_in<T>(x, ldx, slots, ld, N, perm, vec_cap(shape.vec, ldx, x), st);
   }
-  if (!cap) HIPCHK(hipEventRecord(e1, st));
+  if (!cap) HIPCHK(hipEventRecord(ev[1], st));
 
   CHK(prepare_coff<T>(g, shape, ld, st));
-  StepArgs<T> a{};
-  a.rowptr = g->rptr.as<int>();
-  a.col = g->rcol.as<int>();
-  a.val = g->fval.as<T>();
-  a.N = N;
-  a.ld = ld;
-  a.curbytes = (u32)(U * sizeof(T));
+  StepArgs<T> a = step_base<T>(g, ld, y, ldy);
   a.nf = nf;
   a.racc = racc;
-  a.y = y;
-  a.ldy = ldy;
-  a.perm = perm;
   for (int k = 1; k <= K; ++k) {
     const PlanStep& ps = plan[(size_t)k - 1];
     if (tile_ok) {
@@ -2059,31 +2077,71 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
     a.wts = ctx->ws_w.as<T>() + (size_t)(k - 1) * nf * 3;
     launch_step<T>(a, shape, opt, st, g->coff.as<unsigned>());
   }
-  if (!cap) HIPCHK(hipEventRecord(e2, st));
+  if (!cap) HIPCHK(hipEventRecord(ev[2], st));
   if (deferred) {
-    int cvec = shape.vec;
-    while (cvec > 1 && ((ldy % cvec) != 0 || (((uintptr_t)y / sizeof(T)) % cvec) != 0)) cvec /= 2;
     launch_combine<T>(slots, M, SU, ctx->ws_w.as<T>(), M, nf, N, ld, y, ldy, (size_t)N * ldy, perm,
-                      padded ? 1 : cvec, st, ldw);
+                      padded ? 1 : vec_cap(shape.vec, ldy, y), st, ldw);
   } else if (padded && final_to_y) {
     const unsigned nb = (unsigned)std::min<size_t>(((size_t)N * ld + 255) / 256, 65536);
     hipLaunchKernelGGL((k_permute_out_pad<T>), dim3(nb), dim3(256), 0, st, racc, ldw, y, ldy, ld, N, perm);
   }
   if (!cap) {
-    HIPCHK(hipEventRecord(e3, st));
+    HIPCHK(hipEventRecord(ev[3], st));
     HIPCHK(hipGetLastError());
   }
   return GSPX_OK;
 }
 
 template <typename T>
-static int run_batch_synthesis(gspx_graph* g, int nf, int M, const std::vector<double>& cp,
+static int run_synthesis_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp,
                                const T* x, size_t plane_x, unsigned ldx, T* y, unsigned ldy,
                                unsigned ld, size_t& ev_idx);
 
-template <typename T>
-static int filter_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs,
-                        int64_t Nsig, const T* x, T* y, int mode);
+// Signals per column batch of a device call: bounded by the 2 GiB buffer-descriptor window, by the workspace budget
+// (`panels` workspace columns of N elements per signal) and by max_batch.  A call of several batches gets widths that
+// are multiples of 4: batch starts stay 16-byte friendly.
+static int batch_width(const gspx_graph* g, size_t elt, size_t panels, int64_t Nsig, int64_t* width) {
+  const Options& opt = g->ctx->opt;
+  const size_t rowb = (size_t)g->N * elt;
+  int64_t max_ld = (int64_t)((((size_t)1 << 31) - 65536) / rowb);
+  if (max_ld < 1)
+    return set_err(GSPX_ERR_INVALID, "graph too large: one signal column exceeds 2 GiB");
+  const size_t budget = (size_t)std::max<int64_t>(opt.ws_limit_mb, 1) << 20;
+  max_ld = std::min<int64_t>(max_ld, std::max<int64_t>(1, (int64_t)(budget / (rowb * panels))));
+  if (opt.max_batch > 0) max_ld = std::min<int64_t>(max_ld, opt.max_batch);
+  if (max_ld < Nsig && max_ld >= 4) max_ld &= ~(int64_t)3;
+  *width = max_ld;
+  return GSPX_OK;
+}
+
+// The column batches of a device call: batch(c0, ld, ev_idx) runs signals [c0, c0 + ld) and takes its pool events
+// from batch_events.  Then the call's device time, the per-phase sums and the steps run (`steps` per batch) go to
+// ctx->timing[0..4].
+template <typename Batch>
+static int run_batches(gspx_graph* g, int64_t Nsig, int64_t width, int steps, const Batch& batch) {
+  gspx_ctx* ctx = g->ctx;
+  size_t ev_idx = 0;
+  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+  for (int64_t c0 = 0; c0 < Nsig; c0 += width)
+    CHK(batch(c0, (unsigned)std::min<int64_t>(width, Nsig - c0), ev_idx));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  ctx->timing[0] = ms;
+  double phase[3] = {0, 0, 0};  // copy in, steps, combine / copy out
+  for (size_t i = 0; i + 3 < ev_idx; i += 4)
+    for (size_t j = 0; j < 3; ++j) {
+      float t = 0;
+      HIPCHK(hipEventElapsedTime(&t, ctx->ev_pool[i + j], ctx->ev_pool[i + j + 1]));
+      phase[j] += t;
+    }
+  ctx->timing[1] = phase[1];
+  ctx->timing[2] = (double)(ev_idx / 4) * steps;
+  ctx->timing[3] = phase[0];
+  ctx->timing[4] = phase[2];
+  return GSPX_OK;
+}
 
 template <typename T>
 static int filter_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs,
@@ -2101,20 +2159,11 @@ static int filter_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double*
   const int K = M - 1;
   const bool analysis = mode == GSPX_ANALYSIS;
   bool deferred = analysis && (opt.combine == 2 || (opt.combine == 0 && Nf >= 2));
-
-  // signals per batch: bounded by the 2 GiB buffer-descriptor window and the workspace budget
-  const size_t rowb = (size_t)N * sizeof(T);
-  int64_t max_ld = (int64_t)((((size_t)1 << 31) - 65536) / rowb);
-  if (max_ld < 1)
-    return set_err(GSPX_ERR_INVALID, "graph too large: one signal column exceeds 2 GiB");
+  // workspace per signal: M kept panels (deferred combine) or two panels and Nf accumulators
   const size_t budget = (size_t)std::max<int64_t>(opt.ws_limit_mb, 1) << 20;
-  auto ws_per_col = [&](bool def) {
-    return rowb * (def ? (size_t)M : (size_t)(2 + Nf));
-  };
-  if (deferred && ws_per_col(true) * (size_t)std::min<int64_t>(Nsig, 4) > budget) deferred = false;
-  max_ld = std::min<int64_t>(max_ld, std::max<int64_t>(1, (int64_t)(budget / ws_per_col(deferred))));
-  if (opt.max_batch > 0) max_ld = std::min<int64_t>(max_ld, opt.max_batch);
-  if (max_ld < Nsig && max_ld >= 4) max_ld &= ~(int64_t)3;  // keep batch starts 16-byte friendly
+  if (deferred && (size_t)N * sizeof(T) * M * (size_t)std::min<int64_t>(Nsig, 4) > budget) deferred = false;
+  int64_t max_ld = 0;
+  CHK(batch_width(g, sizeof(T), deferred ? (size_t)M : (size_t)(2 + Nf), Nsig, &max_ld));
 
   // ---- hipGraph replay: an analysis call that repeats the previous one exactly (same graph, lmax,
   // coefficients, pointers, options) is recorded once and replayed as one graph launch - K + 1
@@ -2187,50 +2236,23 @@ static int filter_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double*
   if (ctx->graph_exec && ctx->graph_key != key) replay_reset(ctx);
   ctx->seen_key = key;  // empty when graph mode is off
 
-  size_t ev_idx = 0;
-  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
   const size_t plane_x = (size_t)N * Nsig;  // synthesis: x is [Nf][N][Nsig]
-  for (int64_t c0 = 0; c0 < Nsig; c0 += max_ld) {
-    const unsigned ld = (unsigned)std::min<int64_t>(max_ld, Nsig - c0);
-    if (analysis) {
-      CHK(run_batch<T>(g, Nf, M, cp, x + c0, (unsigned)Nsig, y + c0, (unsigned)Nsig, ld, deferred,
-                       false, true, ev_idx));
-    } else {
-      // out = sum_f p_f(L) s_f  (filter.py:317-321)
-      if (opt.synthesis == 1) {
-        // the reference's scheme: one single-filter recurrence per feature, accumulated on
-        // device; only the last one writes y (K*Nf sparse products)
-        for (int f = 0; f < Nf; ++f) {
-          std::vector<double> cf(cp.begin() + (size_t)f * M, cp.begin() + (size_t)(f + 1) * M);
-          CHK(run_batch<T>(g, 1, M, cf, x + (size_t)f * plane_x + c0, (unsigned)Nsig, y + c0,
-                           (unsigned)Nsig, ld, false, f > 0, f == Nf - 1, ev_idx));
-        }
-      } else {
-        CHK(run_batch_synthesis<T>(g, Nf, M, cp, x + c0, plane_x, (unsigned)Nsig, y + c0,
-                                   (unsigned)Nsig, ld, ev_idx));
-      }
+  return run_batches(g, Nsig, max_ld, K, [&](int64_t c0, unsigned ld, size_t& ev_idx) -> int {
+    if (analysis)
+      return run_batch<T>(g, Nf, M, cp, x + c0, (unsigned)Nsig, y + c0, (unsigned)Nsig, ld, deferred, false, true,
+                          ev_idx);
+    // out = sum_f p_f(L) s_f  (filter.py:317-321)
+    if (opt.synthesis != 1)
+      return run_synthesis_batch<T>(g, Nf, M, cp, x + c0, plane_x, (unsigned)Nsig, y + c0, (unsigned)Nsig, ld, ev_idx);
+    // the reference's scheme: one single-filter recurrence per feature, accumulated on
+    // device; only the last one writes y (K*Nf sparse products)
+    for (int f = 0; f < Nf; ++f) {
+      std::vector<double> cf(cp.begin() + (size_t)f * M, cp.begin() + (size_t)(f + 1) * M);
+      CHK(run_batch<T>(g, 1, M, cf, x + (size_t)f * plane_x + c0, (unsigned)Nsig, y + c0, (unsigned)Nsig, ld, false,
+                       f > 0, f == Nf - 1, ev_idx));
     }
-  }
-  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-  ctx->timing[0] = ms;
-  double t_perm = 0, t_steps = 0, t_comb = 0;
-  for (size_t i = 0; i + 3 < ev_idx; i += 4) {
-    float a = 0, b = 0, c = 0;
-    HIPCHK(hipEventElapsedTime(&a, ctx->ev_pool[i], ctx->ev_pool[i + 1]));
-    HIPCHK(hipEventElapsedTime(&b, ctx->ev_pool[i + 1], ctx->ev_pool[i + 2]));
-    HIPCHK(hipEventElapsedTime(&c, ctx->ev_pool[i + 2], ctx->ev_pool[i + 3]));
-    t_perm += a;
-    t_steps += b;
-    t_comb += c;
-  }
-  ctx->timing[1] = t_steps;
-  ctx->timing[2] = (double)(ev_idx / 4) * K;
-  ctx->timing[3] = t_perm;
-  ctx->timing[4] = t_comb;
-  return GSPX_OK;
+    return GSPX_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2243,7 +2265,7 @@ static int filter_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double*
 // Nf*(3 2/3).  Same polynomial, different summation order: agrees to rounding.
 // ------------------------------------------------------------------------------------------------
 template <typename T>
-static int run_batch_synthesis(gspx_graph* g, int nf, int M, const std::vector<double>& cp,
+static int run_synthesis_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp,
                                const T* x, size_t plane_x, unsigned ldx, T* y, unsigned ldy,
                                unsigned ld, size_t& ev_idx) {
   gspx_ctx* ctx = g->ctx;
@@ -2251,20 +2273,12 @@ static int run_batch_synthesis(gspx_graph* g, int nf, int M, const std::vector<d
   hipStream_t st = ctx->stream;
   const int N = (int)g->N;
   const int K = M - 1;
-  // (rows that are not made of 16-byte pieces: padded work panels on the tile kernels, as in run_batch)
-  constexpr unsigned TVEC = 16 / (unsigned)sizeof(T);
-  const unsigned ldp = (ld + TVEC - 1) / TVEC * TVEC;
-  const bool tile_direct = tile_usable<T>(g, opt, ld, y, ldy) && (size_t)nf * N * ld * sizeof(T) < ((size_t)1 << 31);
-  const bool pad_pays = opt.tile_pad == 2 || ld >= 2 ||
-                        (size_t)g->nnz_int * (sizeof(T) + 4) >= ((size_t)20 << 20);
-  const bool padded = !tile_direct && opt.tile_pad && pad_pays && tile_geometry<T>(g, opt, ldp) &&
-                      (size_t)nf * N * ldp * sizeof(T) < ((size_t)1 << 31);
-  const unsigned ldw = padded ? ldp : ld;
+  // (padded work panels as in run_batch; the tile launches span all nf input panels)
+  const WorkPanels wp = work_panels<T>(g, opt, true, (size_t)nf, ld, y, ldy);
+  const bool padded = wp.padded;
+  const unsigned ldw = wp.ldw;
   const size_t U = (size_t)N * ldw;
-  int veccap = 4;
-  while (veccap > 1 && ((ldy % veccap) != 0 || (((uintptr_t)y / sizeof(T)) % veccap) != 0))
-    veccap /= 2;
-  const Shape shape = choose_shape(opt, sizeof(T), ld, veccap);
+  const Shape shape = choose_shape(opt, sizeof(T), ld, vec_cap(4, ldy, y));
   const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
 
   // weights [K+1][nf]: w[k][f] = c'_fk  (c'_f0 already halved)
@@ -2279,10 +2293,8 @@ static int run_batch_synthesis(gspx_graph* g, int nf, int M, const std::vector<d
   T* S = ctx->ws_r.as<T>();
   T* B[2] = {ctx->ws_t.as<T>(), ctx->ws_t.as<T>() + U};
 
-  hipEvent_t e0 = pool_event(ctx, ++ev_idx), e1 = pool_event(ctx, ++ev_idx),
-             e2 = pool_event(ctx, ++ev_idx), e3 = pool_event(ctx, ++ev_idx);
-  if (!e0 || !e1 || !e2 || !e3) return set_err(GSPX_ERR_HIP, "hipEventCreate failed");
-  HIPCHK(hipEventRecord(e0, st));
+  hipEvent_t ev[4];
+  CHK(batch_events(ctx, ev_idx, ev));
   for (int f = 0; f < nf; ++f) {
     const T* xf = x + (size_t)f * plane_x;
     if (padded) {
@@ -2290,29 +2302,17 @@ static int run_batch_synthesis(gspx_graph* g, int nf, int M, const std::vector<d
       hipLaunchKernelGGL((k_permute_in_pad<T>), dim3(nbp), dim3(256), 0, st, xf, ldx, S + (size_t)f * U, ldw, ld, N, perm);
       continue;
     }
-    int pvec = shape.vec;
-    while (pvec > 1 && ((ldx % pvec) != 0 || (((uintptr_t)xf / sizeof(T)) % pvec) != 0)) pvec /= 2;
-    launch_permute_in<T>(xf, ldx, S + (size_t)f * U, ld, N, perm, pvec, st);
+    launch_permute_in<T>(xf, ldx, S + (size_t)f * U, ld, N, perm, vec_cap(shape.vec, ldx, xf), st);
   }
-  HIPCHK(hipEventRecord(e1, st));
+  HIPCHK(hipEventRecord(ev[1], st));
 
   CHK(prepare_coff<T>(g, shape, ld, st));
-  StepArgs<T> a{};
-  a.rowptr = g->rptr.as<int>();
-  a.col = g->rcol.as<int>();
-  a.val = g->fval.as<T>();
-  a.N = N;
-  a.ld = ld;
-  a.curbytes = (u32)(U * sizeof(T));
+  StepArgs<T> a = step_base<T>(g, ld, y, ldy);
   a.nf = 1;
   a.nin = nf;
   a.racc = S;
-  a.y = y;
-  a.ldy = ldy;
-  a.perm = perm;
-  a.beta = T(0);
   // (nf input panels: the buffer window of the tile kernel spans all of them)
-  const bool tile_ok = tile_direct || padded;
+  const bool tile_ok = wp.tile_direct || padded;
   for (int k = K; k >= 0; --k) {
     if (tile_ok) {
       TileArgs<T> t{};
@@ -2356,12 +2356,12 @@ static int run_batch_synthesis(gspx_graph* g, int nf, int M, const std::vector<d
     a.reverse = (opt.alternate_sweep && (k & 1)) ? 1 : 0;
     launch_step<T>(a, shape, opt, st, g->coff.as<unsigned>());
   }
-  HIPCHK(hipEventRecord(e2, st));
+  HIPCHK(hipEventRecord(ev[2], st));
   if (padded) {
     const unsigned nbp = (unsigned)std::min<size_t>(((size_t)N * ld + 255) / 256, 65536);
     hipLaunchKernelGGL((k_permute_out_pad<T>), dim3(nbp), dim3(256), 0, st, B[0], ldw, y, ldy, ld, N, perm);
   }
-  HIPCHK(hipEventRecord(e3, st));
+  HIPCHK(hipEventRecord(ev[3], st));
   HIPCHK(hipGetLastError());
   return GSPX_OK;
 }
@@ -2383,17 +2383,14 @@ static int run_batch_synthesis(gspx_graph* g, int nf, int M, const std::vector<d
 // F = (2/a1)(L - a2 I) has its spectrum in [-2, 2]: a factor (t - r) of a polynomial in t = F/2 is scale 1/2, beta -r.
 // A step whose gamma is 0 reads no third panel at all: gather h_s, write h_{s+1} - two panel passes.
 template <typename T>
-static int run_batch_program(gspx_graph* g, int S, const double* sc, const double* be, const double* ga, bool old_is_x,
+static int run_program_batch(gspx_graph* g, int S, const double* sc, const double* be, const double* ga, bool old_is_x,
                              const T* x, unsigned ldx, T* y, unsigned ldy, unsigned ld, size_t& ev_idx) {
   gspx_ctx* ctx = g->ctx;
   Options opt = ctx->opt;
   hipStream_t st = ctx->stream;
   const int N = (int)g->N;
   const size_t U = (size_t)N * ld;
-  int veccap = 4;
-  while (veccap > 1 && ((ldy % veccap) != 0 || (((uintptr_t)y / sizeof(T)) % veccap) != 0))
-    veccap /= 2;
-  const Shape shape = choose_shape(opt, sizeof(T), ld, veccap);
+  const Shape shape = choose_shape(opt, sizeof(T), ld, vec_cap(4, ldy, y));
   const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
 
   const T hw[3] = {T(1), T(0), T(0)};  // final step of the plain kernels: y = 1 * h
@@ -2405,28 +2402,15 @@ static int run_batch_program(gspx_graph* g, int S, const double* sc, const doubl
   T* X = ctx->ws_t.as<T>();
   T* H[2] = {X + U, old_is_x ? X + 2 * U : X};  // product form: ping-pong between the second panel and X itself
 
-  hipEvent_t e0 = pool_event(ctx, ++ev_idx), e1 = pool_event(ctx, ++ev_idx),
-             e2 = pool_event(ctx, ++ev_idx), e3 = pool_event(ctx, ++ev_idx);
-  if (!e0 || !e1 || !e2 || !e3) return set_err(GSPX_ERR_HIP, "hipEventCreate failed");
-  HIPCHK(hipEventRecord(e0, st));
-  int pvec = shape.vec;
-  while (pvec > 1 && ((ldx % pvec) != 0 || (((uintptr_t)x / sizeof(T)) % pvec) != 0)) pvec /= 2;
-  launch_permute_in<T>(x, ldx, X, ld, N, perm, pvec, st);
-  HIPCHK(hipEventRecord(e1, st));
+  hipEvent_t ev[4];
+  CHK(batch_events(ctx, ev_idx, ev));
+  launch_permute_in<T>(x, ldx, X, ld, N, perm, vec_cap(shape.vec, ldx, x), st);
+  HIPCHK(hipEventRecord(ev[1], st));
 
   CHK(prepare_coff<T>(g, shape, ld, st));
-  StepArgs<T> a{};
-  a.rowptr = g->rptr.as<int>();
-  a.col = g->rcol.as<int>();
-  a.val = g->fval.as<T>();
-  a.N = N;
-  a.ld = ld;
-  a.curbytes = (u32)(U * sizeof(T));
+  StepArgs<T> a = step_base<T>(g, ld, y, ldy);
   a.nf = 1;
   a.racc = H[0];  // never read (flush == 1) - any valid panel
-  a.y = y;
-  a.ldy = ldy;
-  a.perm = perm;
   a.wts = ctx->ws_w.as<T>();
   const bool tile_ok = tile_usable<T>(g, opt, ld, y, ldy);
   for (int s = 0; s < S; ++s) {
@@ -2465,8 +2449,8 @@ static int run_batch_program(gspx_graph* g, int S, const double* sc, const doubl
     a.reverse = (opt.alternate_sweep && (s & 1)) ? 1 : 0;
     launch_step<T>(a, shape, opt, st, g->coff.as<unsigned>());
   }
-  HIPCHK(hipEventRecord(e2, st));
-  HIPCHK(hipEventRecord(e3, st));
+  HIPCHK(hipEventRecord(ev[2], st));
+  HIPCHK(hipEventRecord(ev[3], st));
   HIPCHK(hipGetLastError());
   return GSPX_OK;
 }
@@ -2475,49 +2459,26 @@ template <typename T>
 static int program_dev_t(gspx_graph* g, double lmax, int S, const double* sc, const double* be, const double* ga,
                          bool old_is_x, int64_t Nsig, const T* x, T* y) {
   gspx_ctx* ctx = g->ctx;
-  const Options& opt = ctx->opt;
-  const int64_t N = g->N;
+  replay_reset(ctx);  // (a program rewrites the weights and panels a recorded filter call replays from)
   for (int i = 0; i < 5; ++i) ctx->timing[i] = 0;
-  if (N == 0 || Nsig == 0) return GSPX_OK;
+  if (g->N == 0 || Nsig == 0) return GSPX_OK;
   CHK(ensure_factor<T>(g, lmax));
-  const size_t rowb = (size_t)N * sizeof(T);
-  int64_t max_ld = (int64_t)((((size_t)1 << 31) - 65536) / rowb);
-  if (max_ld < 1)
-    return set_err(GSPX_ERR_INVALID, "graph too large: one signal column exceeds 2 GiB");
-  const size_t budget = (size_t)std::max<int64_t>(opt.ws_limit_mb, 1) << 20;
-  max_ld = std::min<int64_t>(max_ld, std::max<int64_t>(1, (int64_t)(budget / (rowb * 3))));
-  if (opt.max_batch > 0) max_ld = std::min<int64_t>(max_ld, opt.max_batch);
-  if (max_ld < Nsig && max_ld >= 4) max_ld &= ~(int64_t)3;
-  size_t ev_idx = 0;
-  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-  for (int64_t c0 = 0; c0 < Nsig; c0 += max_ld) {
-    const unsigned ld = (unsigned)std::min<int64_t>(max_ld, Nsig - c0);
-    CHK(run_batch_program<T>(g, S, sc, be, ga, old_is_x, x + c0, (unsigned)Nsig, y + c0, (unsigned)Nsig, ld, ev_idx));
-  }
-  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-  ctx->timing[0] = ms;
-  double t_perm = 0, t_steps = 0;
-  for (size_t i = 0; i + 3 < ev_idx; i += 4) {
-    float p = 0, q = 0;
-    HIPCHK(hipEventElapsedTime(&p, ctx->ev_pool[i], ctx->ev_pool[i + 1]));
-    HIPCHK(hipEventElapsedTime(&q, ctx->ev_pool[i + 1], ctx->ev_pool[i + 2]));
-    t_perm += p;
-    t_steps += q;
-  }
-  ctx->timing[1] = t_steps;
-  ctx->timing[2] = (double)(ev_idx / 4) * S;
-  ctx->timing[3] = t_perm;
+  int64_t max_ld = 0;
+  CHK(batch_width(g, sizeof(T), 3, Nsig, &max_ld));
+  CHK(run_batches(g, Nsig, max_ld, S, [&](int64_t c0, unsigned ld, size_t& ev_idx) {
+    return run_program_batch<T>(g, S, sc, be, ga, old_is_x, x + c0, (unsigned)Nsig, y + c0, (unsigned)Nsig, ld, ev_idx);
+  }));
+  ctx->timing[4] = 0;  // no combine: the last step stores y
   return GSPX_OK;
 }
 
-// the Newton form p(t) = sum_j d_j prod_{i<j} (t - r_i) by Horner, as a program: h <- (t - r_j) h + d_j x, j = K-1 .. 0
-template <typename T>
-static int newton_dev_t(gspx_graph* g, double lmax, int K, const double* nodes, const double* dc,
-                        int64_t Nsig, const T* x, T* y) {
-  std::vector<double> sc((size_t)K), be((size_t)K), ga((size_t)K);
+// the Newton form p(t) = sum_j d_j prod_{i<j} (t - r_i) by Horner, as a program with o_s = x (old_is_x):
+// h <- (t - r_j) h + d_j x, j = K-1 .. 0
+static void horner_program(int K, const double* nodes, const double* dc, std::vector<double>& sc,
+                           std::vector<double>& be, std::vector<double>& ga) {
+  sc.assign((size_t)K, 0.0);
+  be.assign((size_t)K, 0.0);
+  ga.assign((size_t)K, 0.0);
   for (int s = 0; s < K; ++s) {
     const int j = K - 1 - s;
     if (s == 0) {  // h_1 = d_K (t - r_{K-1}) x + d_{K-1} x
@@ -2530,11 +2491,35 @@ static int newton_dev_t(gspx_graph* g, double lmax, int K, const double* nodes, 
       ga[(size_t)s] = dc[j];
     }
   }
-  return program_dev_t<T>(g, lmax, K, sc.data(), be.data(), ga.data(), true, Nsig, x, y);
+}
+
+// a device call on the graph's element type: run(x, y, Nsig) with x, y typed; kernel_ms: its device time
+template <typename Run>
+static int device_call(gspx_graph* g, int64_t Nsig, const void* x, void* y, double* kernel_ms, const Run& run) {
+  HIPCHK(hipSetDevice(g->ctx->device));
+  const int rc = g->dtype == GSPX_F32 ? run((const float*)x, (float*)y, Nsig) : run((const double*)x, (double*)y, Nsig);
+  if (rc == GSPX_OK && kernel_ms) *kernel_ms = g->ctx->timing[0];
+  return rc;
+}
+
+static int check_program_args(gspx_graph* g, double lmax, int S, const double* scale, const double* beta,
+                              const double* gamma, int64_t Nsig, const void* x, void* y) {
+  if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
+  if (S < 1) return set_err(GSPX_ERR_COEFF, "The coefficients have an invalid shape");
+  if (!scale || !beta || !gamma) return set_err(GSPX_ERR_INVALID, "null program");
+  if (Nsig < 0) return set_err(GSPX_ERR_INVALID, "negative number of signals");
+  if (!(lmax > 0.0) || !std::isfinite(lmax))
+    return set_err(GSPX_ERR_INVALID, "lmax must be positive and finite (got %g)", lmax);
+  if (Nsig > 0 && g->N > 0 && (!x || !y)) return set_err(GSPX_ERR_INVALID, "null signal pointer");
+  for (int i = 0; i < S; ++i)
+    if (!std::isfinite(scale[i]) || !std::isfinite(beta[i]) || !std::isfinite(gamma[i]))
+      return set_err(GSPX_ERR_INVALID, "non-finite program coefficient");
+  if (Nsig >= ((int64_t)1 << 31) / 16) return set_err(GSPX_ERR_INVALID, "too many signals");
+  return GSPX_OK;
 }
 
 // A polynomial of the scaled operator t = (2 / lmax) L - I evaluated as a PROGRAM of S steps on device panels
-// (see run_batch_program): h_0 = x; h_{s+1} = scale_s (2 t) h_s + beta_s h_s + gamma_s o_s; y = h_S.  old_is_x != 0: o_s = x
+// (see run_program_batch): h_0 = x; h_{s+1} = scale_s (2 t) h_s + beta_s h_s + gamma_s o_s; y = h_S.  old_is_x != 0: o_s = x
 // (the Newton form); 0: o_s = h_{s-1}, gamma_0 ignored (the PRODUCT form: a real root r of the polynomial is one step
 // with scale sigma / 2, beta -sigma r, gamma 0 - two panel passes -, a conjugate pair a +- ib two steps, the second with
 // gamma sigma^2 b^2 - three passes).  pygsp_amd.filters.cheb_to_product builds such programs from Chebyshev coefficients.
@@ -2542,78 +2527,106 @@ extern "C" int gspx_poly_program_dev(gspx_graph* g, double lmax, int S, const do
                                      const double* gamma, int old_is_x, int64_t Nsig, const void* x_dev, void* y_dev,
                                      double* kernel_ms) {
   if (g) replay_reset(g->ctx);
-  if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
-  if (S < 1) return set_err(GSPX_ERR_COEFF, "The coefficients have an invalid shape");
-  if (!scale || !beta || !gamma) return set_err(GSPX_ERR_INVALID, "null program");
-  if (Nsig < 0) return set_err(GSPX_ERR_INVALID, "negative number of signals");
-  if (!(lmax > 0.0) || !std::isfinite(lmax))
-    return set_err(GSPX_ERR_INVALID, "lmax must be positive and finite (got %g)", lmax);
-  if (Nsig > 0 && g->N > 0 && (!x_dev || !y_dev)) return set_err(GSPX_ERR_INVALID, "null signal pointer");
-  for (int i = 0; i < S; ++i)
-    if (!std::isfinite(scale[i]) || !std::isfinite(beta[i]) || !std::isfinite(gamma[i]))
-      return set_err(GSPX_ERR_INVALID, "non-finite program coefficient");
-  if (Nsig >= ((int64_t)1 << 31) / 16) return set_err(GSPX_ERR_INVALID, "too many signals");
-  HIPCHK(hipSetDevice(g->ctx->device));
-  int rc = g->dtype == GSPX_F32
-               ? program_dev_t<float>(g, lmax, S, scale, beta, gamma, old_is_x != 0, Nsig, (const float*)x_dev, (float*)y_dev)
-               : program_dev_t<double>(g, lmax, S, scale, beta, gamma, old_is_x != 0, Nsig, (const double*)x_dev,
-                                       (double*)y_dev);
-  if (rc == GSPX_OK && kernel_ms) *kernel_ms = g->ctx->timing[0];
-  return rc;
+  CHK(check_program_args(g, lmax, S, scale, beta, gamma, Nsig, x_dev, y_dev));
+  return device_call(g, Nsig, x_dev, y_dev, kernel_ms, [&](auto x, auto y, int64_t n) {
+    return program_dev_t(g, lmax, S, scale, beta, gamma, old_is_x != 0, n, x, y);
+  });
 }
 
-
-extern "C" int gspx_newton_filter_dev(gspx_graph* g, double lmax, int K, const double* nodes,
-                                      const double* dcoef, int64_t Nsig, const void* x_dev,
-                                      void* y_dev, double* kernel_ms) {
-  if (g) replay_reset(g->ctx);
+static int check_newton_args(gspx_graph* g, double lmax, int K, const double* nodes, const double* dcoef,
+                             int64_t Nsig, const void* x, void* y) {
   if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
   if (K < 1) return set_err(GSPX_ERR_COEFF, "The coefficients have an invalid shape");
   if (!nodes || !dcoef) return set_err(GSPX_ERR_INVALID, "null nodes / coefficients");
   if (Nsig < 0) return set_err(GSPX_ERR_INVALID, "negative number of signals");
   if (!(lmax > 0.0) || !std::isfinite(lmax))
     return set_err(GSPX_ERR_INVALID, "lmax must be positive and finite (got %g)", lmax);
-  if (Nsig > 0 && g->N > 0 && (!x_dev || !y_dev))
+  if (Nsig > 0 && g->N > 0 && (!x || !y))
     return set_err(GSPX_ERR_INVALID, "null signal pointer");
   for (int i = 0; i < K; ++i)
     if (!std::isfinite(nodes[i])) return set_err(GSPX_ERR_INVALID, "non-finite node");
   for (int i = 0; i <= K; ++i)
     if (!std::isfinite(dcoef[i])) return set_err(GSPX_ERR_INVALID, "non-finite coefficient");
   if (Nsig >= ((int64_t)1 << 31) / 16) return set_err(GSPX_ERR_INVALID, "too many signals");
-  HIPCHK(hipSetDevice(g->ctx->device));
-  int rc = g->dtype == GSPX_F32
-               ? newton_dev_t<float>(g, lmax, K, nodes, dcoef, Nsig, (const float*)x_dev,
-                                     (float*)y_dev)
-               : newton_dev_t<double>(g, lmax, K, nodes, dcoef, Nsig, (const double*)x_dev,
-                                      (double*)y_dev);
-  if (rc == GSPX_OK && kernel_ms) *kernel_ms = g->ctx->timing[0];
-  return rc;
+  return GSPX_OK;
 }
 
+extern "C" int gspx_newton_filter_dev(gspx_graph* g, double lmax, int K, const double* nodes,
+                                      const double* dcoef, int64_t Nsig, const void* x_dev,
+                                      void* y_dev, double* kernel_ms) {
+  if (g) replay_reset(g->ctx);
+  CHK(check_newton_args(g, lmax, K, nodes, dcoef, Nsig, x_dev, y_dev));
+  std::vector<double> sc, be, ga;
+  horner_program(K, nodes, dcoef, sc, be, ga);
+  return device_call(g, Nsig, x_dev, y_dev, kernel_ms, [&](auto x, auto y, int64_t n) {
+    return program_dev_t(g, lmax, K, sc.data(), be.data(), ga.data(), true, n, x, y);
+  });
+}
+
+#include "gspx_hostpipe.hip.h"
+
+// What the host-array entry points share, after the checks the caller makes up front.  An empty call does nothing;
+// `prepare` (the checks that come after the empty-call test, and any setup) runs next.  A large call is pipelined in
+// column batches (gspx_hostpipe.hip.h); any other - or one the pipeline steps aside for - is one copy in through io_x,
+// run(x, y, Nsig) on the device copies, one copy out through io_y.  x / y hold in_planes / out_planes [N][Nsig] planes.
+template <typename Prepare, typename Run>
+static int host_call(gspx_graph* g, int64_t Nsig, int in_planes, int out_planes, const void* x_host, void* y_host,
+                     double* kernel_ms, const Prepare& prepare, const Run& run) {
+  gspx_ctx* ctx = g->ctx;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (g->N == 0 || Nsig <= 0) {
+    if (kernel_ms) *kernel_ms = 0;
+    return GSPX_OK;
+  }
+  CHK(prepare());
+  const size_t e = elt_size(g->dtype);
+  std::vector<int64_t> widths;
+  int threads = 1;
+  host_pipeline_shape(ctx->opt, e, g->N, Nsig, in_planes + out_planes, &widths, &threads);
+  if (widths.size() >= 2) {
+    if (!ctx->pipe) ctx->pipe = new HostPipe();
+    replay_reset(ctx);
+    const int rc = g->dtype == GSPX_F32
+                       ? filter_host_pipelined<float>(g, Nsig, in_planes, out_planes, (const float*)x_host,
+                                                      (float*)y_host, widths, threads, kernel_ms, run)
+                       : filter_host_pipelined<double>(g, Nsig, in_planes, out_planes, (const double*)x_host,
+                                                       (double*)y_host, widths, threads, kernel_ms, run);
+    if (rc != GSPX_HOSTPIPE_UNAVAILABLE) return rc;
+    // an in-place call, or no pinned / device staging memory to be had: the one-shot form below
+  }
+  if (ctx->pipe) {  // this host call is not pipelined: no stage times, no timeline of an earlier call
+    ctx->pipe->timing[6] = 0;
+    ctx->pipe->timeline.clear();
+  }
+  const size_t n_in = (size_t)in_planes * g->N * Nsig * e, n_out = (size_t)out_planes * g->N * Nsig * e;
+  CHK(ctx->io_x.ensure(n_in));
+  CHK(ctx->io_y.ensure(n_out));
+  HIPCHK(hipMemcpyAsync(ctx->io_x.p, x_host, n_in, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  CHK(device_call(g, Nsig, ctx->io_x.p, ctx->io_y.p, kernel_ms, run));
+  HIPCHK(hipMemcpyAsync(y_host, ctx->io_y.p, n_out, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return GSPX_OK;
+}
+
+// gspx_newton_filter_dev with host arrays
 extern "C" int gspx_newton_filter(gspx_graph* g, double lmax, int K, const double* nodes,
                                   const double* dcoef, int64_t Nsig, const void* x_host,
                                   void* y_host, double* kernel_ms) {
   if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
   if (Nsig > 0 && g->N > 0 && (!x_host || !y_host))
     return set_err(GSPX_ERR_INVALID, "null signal pointer");
-  gspx_ctx* ctx = g->ctx;
-  HIPCHK(hipSetDevice(ctx->device));
-  const size_t n = (size_t)g->N * (size_t)std::max<int64_t>(Nsig, 0) * elt_size(g->dtype);
-  if (n == 0) {
-    if (kernel_ms) *kernel_ms = 0;
-    return K < 1 ? set_err(GSPX_ERR_COEFF, "The coefficients have an invalid shape") : GSPX_OK;
-  }
-  CHK(ctx->io_x.ensure(n));
-  CHK(ctx->io_y.ensure(n));
-  HIPCHK(hipMemcpyAsync(ctx->io_x.p, x_host, n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  CHK(gspx_newton_filter_dev(g, lmax, K, nodes, dcoef, Nsig, ctx->io_x.p, ctx->io_y.p, kernel_ms));
-  HIPCHK(hipMemcpyAsync(y_host, ctx->io_y.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return GSPX_OK;
+  if (K < 1) return set_err(GSPX_ERR_COEFF, "The coefficients have an invalid shape");
+  std::vector<double> sc, be, ga;
+  auto prepare = [&]() -> int {
+    CHK(check_newton_args(g, lmax, K, nodes, dcoef, Nsig, x_host, y_host));
+    horner_program(K, nodes, dcoef, sc, be, ga);
+    return GSPX_OK;
+  };
+  return host_call(g, Nsig, 1, 1, x_host, y_host, kernel_ms, prepare, [&](auto x, auto y, int64_t n) {
+    return program_dev_t(g, lmax, K, sc.data(), be.data(), ga.data(), true, n, x, y);
+  });
 }
-
-#include "gspx_hostpipe.hip.h"
 
 static int check_filter_args(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs,
                              int64_t Nsig, const void* x, void* y, int mode) {
@@ -2637,108 +2650,33 @@ extern "C" int gspx_cheby_filter_dev(gspx_graph* g, double lmax, int Nf, int M,
                                      const double* coeffs, int64_t Nsig, const void* x_dev,
                                      void* y_dev, int mode, double* kernel_ms) {
   CHK(check_filter_args(g, lmax, Nf, M, coeffs, Nsig, x_dev, y_dev, mode));
-  HIPCHK(hipSetDevice(g->ctx->device));
-  int rc = g->dtype == GSPX_F32
-               ? filter_dev_t<float>(g, lmax, Nf, M, coeffs, Nsig, (const float*)x_dev,
-                                     (float*)y_dev, mode)
-               : filter_dev_t<double>(g, lmax, Nf, M, coeffs, Nsig, (const double*)x_dev,
-                                      (double*)y_dev, mode);
-  if (rc == GSPX_OK && kernel_ms) *kernel_ms = g->ctx->timing[0];
-  return rc;
+  return device_call(g, Nsig, x_dev, y_dev, kernel_ms, [&](auto x, auto y, int64_t n) {
+    return filter_dev_t(g, lmax, Nf, M, coeffs, n, x, y, mode);
+  });
 }
 
 extern "C" int gspx_cheby_filter(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs,
                                  int64_t Nsig, const void* x_host, void* y_host, int mode,
                                  double* kernel_ms) {
   CHK(check_filter_args(g, lmax, Nf, M, coeffs, Nsig, x_host, y_host, mode));
-  gspx_ctx* ctx = g->ctx;
-  HIPCHK(hipSetDevice(ctx->device));
-  const size_t e = elt_size(g->dtype);
-  const size_t n_in = (size_t)g->N * (size_t)Nsig * (mode == GSPX_ANALYSIS ? 1 : (size_t)Nf);
-  const size_t n_out = (size_t)g->N * (size_t)Nsig * (mode == GSPX_ANALYSIS ? (size_t)Nf : 1);
-  if (n_in == 0 || n_out == 0) {
-    if (kernel_ms) *kernel_ms = 0;
-    return GSPX_OK;
-  }
-  {  // large calls: column batches pipelined over pinned staging buffers (gspx_hostpipe.hip.h)
-    std::vector<int64_t> widths;
-    int threads = 1;
-    host_pipeline_shape(ctx->opt, e, g->N, Nsig, Nf + 1, &widths, &threads);
-    if (widths.size() >= 2) {
-      if (!ctx->pipe) ctx->pipe = new HostPipe();
-      replay_reset(ctx);
-      const int rc = g->dtype == GSPX_F32
-                         ? filter_host_pipelined<float>(g, lmax, Nf, M, coeffs, Nsig, (const float*)x_host,
-                                                        (float*)y_host, mode, widths, threads, kernel_ms)
-                         : filter_host_pipelined<double>(g, lmax, Nf, M, coeffs, Nsig, (const double*)x_host,
-                                                         (double*)y_host, mode, widths, threads, kernel_ms);
-      if (rc != GSPX_HOSTPIPE_UNAVAILABLE) return rc;
-      // an in-place call, or no pinned / device staging memory to be had: the one-shot form below
-    }
-    if (ctx->pipe) {  // the last host call was not pipelined: no stage times, no timeline of an earlier call
-      ctx->pipe->timing[6] = 0;
-      ctx->pipe->timeline.clear();
-    }
-  }
-  CHK(ctx->io_x.ensure(n_in * e));
-  CHK(ctx->io_y.ensure(n_out * e));
-  HIPCHK(hipMemcpyAsync(ctx->io_x.p, x_host, n_in * e, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  CHK(gspx_cheby_filter_dev(g, lmax, Nf, M, coeffs, Nsig, ctx->io_x.p, ctx->io_y.p, mode,
-                            kernel_ms));
-  HIPCHK(hipMemcpyAsync(y_host, ctx->io_y.p, n_out * e, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return GSPX_OK;
+  const bool analysis = mode == GSPX_ANALYSIS;
+  return host_call(g, Nsig, analysis ? 1 : Nf, analysis ? Nf : 1, x_host, y_host, kernel_ms,
+                   [] { return (int)GSPX_OK; }, [&](auto x, auto y, int64_t n) {
+                     return filter_dev_t(g, lmax, Nf, M, coeffs, n, x, y, mode);
+                   });
 }
 
-// gspx_poly_program_dev with host arrays: pipelined in column batches like gspx_cheby_filter when the call is large,
-// else one copy in, the program, one copy out
+// gspx_poly_program_dev with host arrays
 extern "C" int gspx_poly_program(gspx_graph* g, double lmax, int S, const double* scale, const double* beta,
                                  const double* gamma, int old_is_x, int64_t Nsig, const void* x_host, void* y_host,
                                  double* kernel_ms) {
   if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
   if (Nsig > 0 && g->N > 0 && (!x_host || !y_host)) return set_err(GSPX_ERR_INVALID, "null signal pointer");
-  gspx_ctx* ctx = g->ctx;
-  HIPCHK(hipSetDevice(ctx->device));
-  const size_t n = (size_t)g->N * (size_t)std::max<int64_t>(Nsig, 0) * elt_size(g->dtype);
-  if (n == 0) {
-    if (kernel_ms) *kernel_ms = 0;
-    return S < 1 ? set_err(GSPX_ERR_COEFF, "The coefficients have an invalid shape") : GSPX_OK;
-  }
-  if (S >= 1 && scale && beta && gamma && lmax > 0.0 && std::isfinite(lmax)) {
-    // large calls: the same column batches pipelined over pinned staging as gspx_cheby_filter, the program on each batch
-    bool finite = true;
-    for (int i = 0; i < S; ++i) finite = finite && std::isfinite(scale[i]) && std::isfinite(beta[i]) && std::isfinite(gamma[i]);
-    std::vector<int64_t> widths;
-    int threads = 1;
-    host_pipeline_shape(ctx->opt, elt_size(g->dtype), g->N, Nsig, 2, &widths, &threads);
-    if (finite && widths.size() >= 2) {
-      if (!ctx->pipe) ctx->pipe = new HostPipe();
-      replay_reset(ctx);
-      const BatchProgram prog{S, scale, beta, gamma, old_is_x != 0};
-      const double dummy[2] = {1.0, 0.0};  // (the pipeline's own argument list: unused while batch_program is set)
-      ctx->batch_program = &prog;
-      const int rc = g->dtype == GSPX_F32
-                         ? filter_host_pipelined<float>(g, lmax, 1, 2, dummy, Nsig, (const float*)x_host, (float*)y_host,
-                                                        GSPX_ANALYSIS, widths, threads, kernel_ms)
-                         : filter_host_pipelined<double>(g, lmax, 1, 2, dummy, Nsig, (const double*)x_host,
-                                                         (double*)y_host, GSPX_ANALYSIS, widths, threads, kernel_ms);
-      ctx->batch_program = nullptr;
-      if (rc != GSPX_HOSTPIPE_UNAVAILABLE) return rc;
-    }
-  }
-  if (ctx->pipe) {  // this host call is not pipelined: no stage times, no timeline of an earlier call
-    ctx->pipe->timing[6] = 0;
-    ctx->pipe->timeline.clear();
-  }
-  CHK(ctx->io_x.ensure(n));
-  CHK(ctx->io_y.ensure(n));
-  HIPCHK(hipMemcpyAsync(ctx->io_x.p, x_host, n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  CHK(gspx_poly_program_dev(g, lmax, S, scale, beta, gamma, old_is_x, Nsig, ctx->io_x.p, ctx->io_y.p, kernel_ms));
-  HIPCHK(hipMemcpyAsync(y_host, ctx->io_y.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return GSPX_OK;
+  if (S < 1) return set_err(GSPX_ERR_COEFF, "The coefficients have an invalid shape");
+  auto prepare = [&] { return check_program_args(g, lmax, S, scale, beta, gamma, Nsig, x_host, y_host); };
+  return host_call(g, Nsig, 1, 1, x_host, y_host, kernel_ms, prepare, [&](auto x, auto y, int64_t n) {
+    return program_dev_t(g, lmax, S, scale, beta, gamma, old_is_x != 0, n, x, y);
+  });
 }
 
 // host-only: the column batches and thread count the pipelined host-pointer call would use (for schedule tests)

@@ -1,5 +1,5 @@
-// gspx_hostpipe.hip.h - the host-pointer entry point (gspx_cheby_filter) as a five-stage pipeline over
-// signal-column batches.  Included by gspx.hip.
+// gspx_hostpipe.hip.h - the host-pointer entry points (gspx_cheby_filter, gspx_poly_program, gspx_newton_filter) as a
+// five-stage pipeline over signal-column batches.  Included by gspx.hip; its host_call decides which calls take it.
 //
 // What a plugin-mode caller of pygsp/filters/filter.py:146-328 hands over is pageable numpy memory: round 2
 // copied the whole input (pageable hipMemcpyAsync: the runtime stages it on one thread), ran the kernels,
@@ -52,11 +52,11 @@ static inline void copy_rows(unsigned char* dst, size_t dpitch, const unsigned c
 
 #define GSPX_HOSTPIPE_UNAVAILABLE (-1) /* internal: the pipeline could not get its staging buffers */
 
-// `widths`: the signal columns of each batch, in order (they add up to Nsig)
-template <typename T>
-static int filter_host_pipelined(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs, int64_t Nsig,
-                                 const T* x, T* y, int mode, const std::vector<int64_t>& widths, int nthreads,
-                                 double* kernel_ms) {
+// x / y: in_planes / out_planes planes of [N][Nsig]; `widths`: the signal columns of each batch, in order (they add up
+// to Nsig); run(x, y, w): the device call on a compact batch of w columns (filter_dev_t or program_dev_t)
+template <typename T, typename Run>
+static int filter_host_pipelined(gspx_graph* g, int64_t Nsig, int in_planes, int out_planes, const T* x, T* y,
+                                 const std::vector<int64_t>& widths, int nthreads, double* kernel_ms, const Run& run) {
   gspx_ctx* ctx = g->ctx;
   HostPipe& hp = *ctx->pipe;
   if (hp.init() != GSPX_OK) {
@@ -64,8 +64,6 @@ static int filter_host_pipelined(gspx_graph* g, double lmax, int Nf, int M, cons
     return GSPX_HOSTPIPE_UNAVAILABLE;
   }
   const int64_t N = g->N;
-  const bool analysis = mode == GSPX_ANALYSIS;
-  const int in_planes = analysis ? 1 : Nf, out_planes = analysis ? Nf : 1;
   const int nb = (int)widths.size();
   std::vector<int64_t> col0((size_t)nb, 0);
   for (int b = 1; b < nb; ++b) col0[(size_t)b] = col0[(size_t)b - 1] + widths[(size_t)b - 1];
@@ -231,10 +229,7 @@ static int filter_host_pipelined(gspx_graph* g, double lmax, int Nf, int M, cons
     if (!wait_for([&] { return issued >= b + 1 && shipped >= b - 1; })) break;
     if (hipfail(hipStreamWaitEvent(ctx->stream, hp.h2d_ev[s], 0), "hipStreamWaitEvent")) break;
     stamp(b, 2);
-    const BatchProgram* bp = ctx->batch_program;  // (gspx_poly_program: a polynomial program on every batch)
-    const int rc = bp ? program_dev_t<T>(g, lmax, bp->S, bp->sc, bp->be, bp->ga, bp->old_is_x, width_of(b),
-                                         (const T*)hp.dx[s].p, (T*)hp.dy[so].p)
-                      : filter_dev_t<T>(g, lmax, Nf, M, coeffs, width_of(b), (const T*)hp.dx[s].p, (T*)hp.dy[so].p, mode);
+    const int rc = run((const T*)hp.dx[s].p, (T*)hp.dy[so].p, width_of(b));
     if (rc != GSPX_OK) {
       fail(rc);
       break;

@@ -31,11 +31,7 @@ static int spmm_internal(gspx_graph* g, const T* vals, T scale, T beta, const T*
     t.final = y ? 1 : 0;
     return launch_step_tile<T>(g, opt, t, ld, ctx->stream, vals);
   }
-  int veccap = 4;
-  if (y)
-    while (veccap > 1 && ((ldy % veccap) != 0 || (((uintptr_t)y / sizeof(T)) % veccap) != 0))
-      veccap /= 2;
-  const Shape shape = choose_shape(opt, sizeof(T), ld, veccap);
+  const Shape shape = choose_shape(opt, sizeof(T), ld, y ? vec_cap(4, ldy, y) : 4);
   CHK(prepare_coff<T>(g, shape, ld, ctx->stream));
   StepArgs<T> a{};
   a.rowptr = g->rptr.as<int>();
@@ -71,12 +67,7 @@ static int64_t ops_max_ld(gspx_graph* g, size_t elt, int panels) {
 
 template <typename T> static int permute_panel(gspx_graph* g, const T* x, unsigned ldx, T* out,
                                                unsigned ld, const int* perm) {
-  int pvec = 4;
-  if (sizeof(T) == 8) pvec = 2;
-  while (pvec > 1 && ((ldx % pvec) != 0 || (ld % pvec) != 0 ||
-                      (((uintptr_t)x / sizeof(T)) % pvec) != 0 ||
-                      (((uintptr_t)out / sizeof(T)) % pvec) != 0))
-    pvec /= 2;
+  const int pvec = vec_cap(vec_cap(sizeof(T) == 8 ? 2 : 4, ldx, x), ld, out);  // (x rows and out rows aligned)
   launch_permute_in<T>(x, ldx, out, ld, (int)g->N, perm, pvec, g->ctx->stream);
   return GSPX_OK;
 }

@@ -252,6 +252,17 @@ def test_programs_on_host_arrays_are_pipelined_like_the_recurrence(ctx, dtype):
         ctx.set_option("host_pipeline", 1)
         assert np.array_equal(y_pipe, y_one), name
         assert rel_err(y_pipe[:, :2], ref) < BAR[np.dtype(dtype)] / 10, name
+    # gspx_newton_filter builds the same Horner program: pipelined the same way, the same bytes as the program
+    nodes, d = filters.cheb_to_newton(c)
+    ctx.set_option("host_pipeline", 2)
+    yn_pipe, _ = dev.newton_filter(nodes, d, x, G.lmax)
+    stages = ctx.last_host_timing()
+    assert stages is not None and stages["batches"] >= 2
+    ctx.set_option("host_pipeline", 0)
+    yn_one, _ = dev.newton_filter(nodes, d, x, G.lmax)
+    assert ctx.last_host_timing() is None
+    ctx.set_option("host_pipeline", 1)
+    assert np.array_equal(yn_pipe, yn_one) and np.array_equal(yn_pipe, y_pipe)
     # through the API: evaluation='auto' on numpy arrays
     y = filters.Heat(G, 10).filter(x, order=40, evaluation="auto")
     assert G._gspx_last_evaluation == "product" and rel_err(y[:, :2], ref) < BAR[np.dtype(dtype)] / 10

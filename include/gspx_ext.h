@@ -235,6 +235,13 @@ int gspx_graph_download_perm(gspx_graph* g, int32_t* perm);
  * GSPX_F64), queued on the context's stream: the input of Filter.compute_frame (filter.py:593-600 filters
  * np.identity(N)) produced where it is consumed. */
 int gspx_identity_panel_dev(gspx_ctx* ctx, int dtype, int64_t N, int64_t j0, int64_t w, void* out_dev);
+/* Squared column norms of a filterbank applied to DEVICE signals, without its outputs: out (HOST, Nf x Nsig fp64)
+ * [f][j] = sum_n ((p_f(L) x)[n][j])^2.  Arguments as gspx_cheby_filter_dev in analysis mode, M <= 256.  Every output
+ * element is formed, squared and summed in fp64 for both graph dtypes; identical calls give identical bits.  With the
+ * identity panels of gspx_identity_panel_dev: the row norms of Filter.compute_frame (pygsp.features.compute_norm_tig,
+ * compute_spectrogram) without the frame. */
+int gspx_cheby_sqnorms_dev(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs, int64_t Nsig,
+                           const void* x_dev, double* out, double* kernel_ms);
 
 /* PCI address ("0000:c1:00.0", NUL-terminated) of HIP device `device`: what a host driver needs to find the NUMA
  * node the GPU hangs off (/sys/bus/pci/devices/<address>/numa_node) and pin the thread - and the packing threads

@@ -414,6 +414,7 @@ struct gspx_ctx {
   DevMem ws_w;      // per-step flush weights / combine coefficients
   DevMem io_x, io_y;  // staging for the host-pointer entry point
   DevMem ws_spec;     // small matrices and reduction partials of the panel primitives (gspx_spectral.hip.h)
+  DevMem ws_sq, ws_sqp;  // column norms: coefficients and norms | workgroup partials (gspx_cheby_sqnorms_dev)
   HostPipe* pipe = nullptr;  // its pipelined form (created on first use)
   CopyStage* copy = nullptr; // staged transfers of large buffers (created on first use)
   bool counted = false;      // this context is in g_live_ctx
@@ -588,6 +589,8 @@ extern "C" int gspx_ctx_destroy(gspx_ctx* ctx) {
   ctx->io_x.release();
   ctx->io_y.release();
   ctx->ws_spec.release();
+  ctx->ws_sq.release();
+  ctx->ws_sqp.release();
   if (ctx->pipe) {
     ctx->pipe->destroy();
     delete ctx->pipe;
@@ -1688,6 +1691,54 @@ static void launch_combine(const T* slots, int nslots, size_t slot_stride, const
                                 perm, st, pitch);
 }
 
+// The squared column norms of a deferred batch instead of its outputs (gspx_cheby_sqnorms_dev): cf [k][ldc] fp64
+// coefficients (c'_f0 halved, zero beyond Nf), out [Nf][ldo] fp64 at the batch's first column, part the workgroup
+// partials (sqnorm_parts doubles at the call's widest batch).
+struct SqNorms {
+  const double* cf;
+  int ldc, nf;
+  double* out;
+  size_t ldo;
+  double* part;
+};
+static const int SQ_PASS = 128;  // filters per pass over the stack
+static int sqnorm_cwl(unsigned w) {  // log2 of the columns of a tile: the batch width up to 64, a power of two
+  int l = 0;
+  while (l < 6 && (1u << l) < w) ++l;
+  return l;
+}
+static int sqnorm_gx(const gspx_ctx* ctx, int N, unsigned w) {  // workgroups along the rows
+  const int cwl = sqnorm_cwl(w);
+  const int64_t tiles = ((int64_t)N + (64 >> cwl) - 1) / (64 >> cwl);
+  const int64_t gy = ((int64_t)w + (1 << cwl) - 1) >> cwl;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (4 * (int64_t)ctx->cu_count + gy - 1) / gy));
+}
+static size_t sqnorm_parts(const gspx_ctx* ctx, int N, unsigned w) {
+  return (size_t)sqnorm_gx(ctx, N, w) * SQ_PASS * w;
+}
+
+template <typename T>
+static int launch_combine_sqnorm(gspx_ctx* ctx, const T* slots, int nslots, size_t slot_stride, unsigned pitch, int N,
+                                 unsigned w, const SqNorms& sq, hipStream_t st) {
+  const size_t lds = (size_t)nslots * 64 * sizeof(double);
+  const int cwl = sqnorm_cwl(w);
+  const dim3 grid((unsigned)sqnorm_gx(ctx, N, w), (w + (1u << cwl) - 1) >> cwl);
+  for (int f0 = 0; f0 < sq.nf; f0 += SQ_PASS) {
+    const int here = std::min(SQ_PASS, sq.nf - f0);
+    const int fb = here <= 8 ? 2 : here <= 32 ? 8 : 32;  // filters per wave: 4 waves cover the pass
+    typedef void (*kern_t)(const T*, int, size_t, u32, int, int, int, const double*, int, double*);
+    const kern_t kern = fb == 2 ? k_combine_sqnorm<T, 2> : fb == 8 ? k_combine_sqnorm<T, 8> : k_combine_sqnorm<T, 32>;
+    if (lds > ((size_t)64 << 10))
+      HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, slots, nslots, slot_stride, (u32)pitch, N, (int)w, cwl,
+                       sq.cf + f0, sq.ldc, sq.part);
+    const int64_t n = (int64_t)here * w;
+    hipLaunchKernelGGL(k_sqnorm_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sq.part, (int)grid.x,
+                       4 * fb, here, (int)w, sq.out + (size_t)f0 * sq.ldo, sq.ldo);
+  }
+  return GSPX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the filter
 // ------------------------------------------------------------------------------------------------
@@ -1945,7 +1996,7 @@ static int batch_events(gspx_ctx* ctx, size_t& ev_idx, hipEvent_t ev[4]) {
 template <typename T>
 static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp, const T* x,
                      unsigned ldx, T* y, unsigned ldy, unsigned ld, bool deferred,
-                     bool acc_existing, bool final_to_y, size_t& ev_idx) {
+                     bool acc_existing, bool final_to_y, size_t& ev_idx, const SqNorms* sq = nullptr) {
   gspx_ctx* ctx = g->ctx;
   const Options& opt = ctx->opt;
   hipStream_t st = ctx->stream;
@@ -2078,7 +2129,9 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
     launch_step<T>(a, shape, opt, st, g->coff.as<unsigned>());
   }
   if (!cap) HIPCHK(hipEventRecord(ev[2], st));
-  if (deferred) {
+  if (deferred && sq) {  // the squared column norms in place of the outputs (rows in any order: no perm)
+    CHK(launch_combine_sqnorm<T>(ctx, slots, M, SU, ldw, N, ld, *sq, st));
+  } else if (deferred) {
     launch_combine<T>(slots, M, SU, ctx->ws_w.as<T>(), M, nf, N, ld, y, ldy, (size_t)N * ldy, perm,
                       padded ? 1 : vec_cap(shape.vec, ldy, y), st, ldw);
   } else if (padded && final_to_y) {
@@ -2664,6 +2717,63 @@ extern "C" int gspx_cheby_filter(gspx_graph* g, double lmax, int Nf, int M, cons
                    [] { return (int)GSPX_OK; }, [&](auto x, auto y, int64_t n) {
                      return filter_dev_t(g, lmax, Nf, M, coeffs, n, x, y, mode);
                    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Squared column norms of a filterbank applied to device signals (features.compute_norm_tig / compute_spectrogram):
+// the deferred plan for every Nf, Nf = 1 included, and per column batch k_combine_sqnorm over the kept slots in place
+// of k_combine.  Nothing of size Nf x N x w exists: the workspaces are the M slots, the coefficient table, the Nf x Nsig
+// norms and the workgroup partials.  out: HOST, Nf x Nsig.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+static int sqnorms_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs, int64_t Nsig, const T* x,
+                         double* out) {
+  gspx_ctx* ctx = g->ctx;
+  const int64_t N = g->N;
+  for (int i = 0; i < 5; ++i) ctx->timing[i] = 0;
+  if (Nsig == 0) return GSPX_OK;
+  if (N == 0) {
+    std::fill(out, out + (size_t)Nf * Nsig, 0.0);
+    return GSPX_OK;
+  }
+  int64_t width = 0;
+  CHK(batch_width(g, sizeof(T), (size_t)M, Nsig, &width));
+  std::vector<double> cp;
+  halve_c0(Nf, M, coeffs, cp);
+  const int ldc = (Nf + SQ_PASS - 1) / SQ_PASS * SQ_PASS;  // [k][ldc], zero beyond Nf: a pass never reads past it
+  std::vector<double> hc((size_t)M * ldc, 0.0);
+  for (int f = 0; f < Nf; ++f)
+    for (int k = 0; k < M; ++k) hc[(size_t)k * ldc + f] = cp[(size_t)f * M + k];
+  const size_t cbytes = (hc.size() * sizeof(double) + 255) / 256 * 256, obytes = (size_t)Nf * Nsig * sizeof(double);
+  const int64_t first = std::min<int64_t>(width, Nsig), last = Nsig - (Nsig - 1) / width * width;
+  const size_t parts = std::max(sqnorm_parts(ctx, (int)N, (unsigned)first), sqnorm_parts(ctx, (int)N, (unsigned)last));
+  CHK(ctx->ws_sq.ensure(cbytes + obytes + 256));
+  CHK(ctx->ws_sqp.ensure(parts * sizeof(double) + 256));
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipMemcpyAsync(ctx->ws_sq.p, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));  // hc is a stack-owned staging buffer
+  CHK(ensure_factor<T>(g, lmax));
+  double* outd = (double*)((char*)ctx->ws_sq.p + cbytes);
+  const SqNorms sq{ctx->ws_sq.as<double>(), ldc, Nf, outd, (size_t)Nsig, ctx->ws_sqp.as<double>()};
+  CHK(run_batches(g, Nsig, width, M - 1, [&](int64_t c0, unsigned ld, size_t& ev_idx) -> int {
+    SqNorms b = sq;
+    b.out = outd + c0;
+    return run_batch<T>(g, Nf, M, cp, x + c0, (unsigned)Nsig, (T*)nullptr, ld, ld, true, false, false, ev_idx, &b);
+  }));
+  HIPCHK(hipMemcpyAsync(out, outd, obytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return GSPX_OK;
+}
+
+extern "C" int gspx_cheby_sqnorms_dev(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs, int64_t Nsig,
+                                      const void* x_dev, double* out, double* kernel_ms) {
+  if (g) replay_reset(g->ctx);
+  CHK(check_filter_args(g, lmax, Nf, M, coeffs, Nsig, x_dev, out, GSPX_ANALYSIS));
+  if (M > 256) return set_err(GSPX_ERR_INVALID, "gspx_cheby_sqnorms_dev: at most 256 coefficients per filter");
+  if (Nsig > 0 && !out) return set_err(GSPX_ERR_INVALID, "gspx_cheby_sqnorms_dev: null output");
+  return device_call(g, Nsig, x_dev, out, kernel_ms, [&](auto x, auto, int64_t n) {
+    return sqnorms_dev_t(g, lmax, Nf, M, coeffs, n, x, out);
+  });
 }
 
 // gspx_poly_program_dev with host arrays

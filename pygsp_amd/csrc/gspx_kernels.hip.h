@@ -886,6 +886,79 @@ __global__ __launch_bounds__(256) void k_combine(const T* __restrict__ slots, in
 }
 
 // ---------------------------------------------------------------------------------------------
+// Squared column norms of a filterbank straight from the kept slots (features.compute_norm_tig and
+// compute_spectrogram):   s[f][j] = sum_rows ( sum_k c'_fk T_k[row][j] )^2,   f < 4 FB, j < w.
+// Every y element is formed, squared and summed in fp64 - never c^T G c with the Gram matrix of the T_k,
+// which cancels badly for the narrow atoms of a spectrogram.  No y panel is ever written.
+// A workgroup stages a tile of 64 elements (64 >> cwl rows x 2^cwl columns, 0 outside the batch) of all
+// nslots slots in LDS, as fp64, so the stack is read once for the whole bank; wave fg then forms filters
+// [fg FB, fg FB + FB) of the tile with VALU FMAs whose coefficient operand is wave-uniform (cf: [k][ldc]
+// fp64, read through the scalar cache).  At ~25 flop per stack byte for 100 filters this is compute
+// bound; on gfx950 v_fma_f64 and v_mfma_f64_16x16x4f64 have the same peak rate (profiles/features.md).
+// Rows of one column are summed in registers, then across the wave by a fixed butterfly; every
+// workgroup writes its own partials part[blockIdx.x][f][j] (k_sqnorm_reduce sums them in a fixed order):
+// no atomics, identical calls give identical bits.
+// ---------------------------------------------------------------------------------------------
+template <typename T, int FB>
+__global__ __launch_bounds__(256) void k_combine_sqnorm(const T* __restrict__ slots, int nslots,
+                                                        size_t slot_stride, u32 pitch, int N, int w, int cwl,
+                                                        const double* __restrict__ cf, int ldc,
+                                                        double* __restrict__ part) {
+  extern __shared__ double sq_tile[];  // [nslots][64]
+  const int e = threadIdx.x & 63;
+  const int fg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cw = 1 << cwl;
+  const int rpt = 64 >> cwl;  // rows per tile
+  const int cbase = blockIdx.y * cw;
+  const int col = cbase + (e & (cw - 1));
+  const double* __restrict__ c = cf + fg * FB;
+  double acc[FB];
+#pragma unroll
+  for (int f = 0; f < FB; ++f) acc[f] = 0.0;
+  for (int r0 = blockIdx.x * rpt; r0 < N; r0 += gridDim.x * rpt) {
+    for (int i = threadIdx.x; i < nslots * 64; i += 256) {
+      const int k = i >> 6, ee = i & 63;
+      const int row = r0 + (ee >> cwl), cc = cbase + (ee & (cw - 1));
+      double v = 0.0;
+      if (row < N && cc < w) v = (double)slots[(size_t)k * slot_stride + (size_t)row * pitch + cc];
+      sq_tile[i] = v;
+    }
+    __syncthreads();
+    double y[FB];
+#pragma unroll
+    for (int f = 0; f < FB; ++f) y[f] = 0.0;
+    for (int k = 0; k < nslots; ++k) {
+      const double t = sq_tile[k * 64 + e];
+      const double* __restrict__ ck = c + (size_t)k * ldc;
+#pragma unroll
+      for (int f = 0; f < FB; ++f) y[f] = fma(ck[f], t, y[f]);
+    }
+#pragma unroll
+    for (int f = 0; f < FB; ++f) acc[f] = fma(y[f], y[f], acc[f]);
+    __syncthreads();
+  }
+  for (int off = cw; off < 64; off <<= 1) {
+#pragma unroll
+    for (int f = 0; f < FB; ++f) acc[f] += __shfl_xor(acc[f], off);
+  }
+  if ((e >> cwl) == 0 && col < w) {
+#pragma unroll
+    for (int f = 0; f < FB; ++f) part[((size_t)blockIdx.x * (4 * FB) + fg * FB + f) * w + col] = acc[f];
+  }
+}
+
+// s[f][j] = sum over the nparts workgroup partials of k_combine_sqnorm, in partial order; out row pitch ldo
+__global__ __launch_bounds__(256) void k_sqnorm_reduce(const double* __restrict__ part, int nparts, int ldp, int nf,
+                                                       int w, double* __restrict__ out, size_t ldo) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)nf * w) return;
+  const int f = (int)(i / w), col = (int)(i - (int64_t)f * w);
+  double s = 0.0;
+  for (int b = 0; b < nparts; ++b) s += part[((size_t)b * ldp + f) * w + col];
+  out[(size_t)f * ldo + col] = s;
+}
+
+// ---------------------------------------------------------------------------------------------
 // permute-in: T_0[i][c] = x[perm[i]][c0 + c]   (also the plain copy when perm == null)
 // ---------------------------------------------------------------------------------------------
 template <typename T, int VEC>

@@ -881,6 +881,18 @@ class DeviceGraph:
             ctypes.c_void_p(y_ptr), mode, ctypes.byref(ms))
         return ms.value
 
+    def cheby_sqnorms_dev(self, coeffs, x_ptr, nsig, lmax):
+        """Squared column norms of the bank `coeffs` (Nf, M) applied to the device signals at x_ptr (N x nsig):
+        ((Nf, nsig) float64 host array of ||p_f(L) x_j||^2, device milliseconds of the call), without the filtered
+        outputs (gspx_cheby_sqnorms_dev)."""
+        c = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        Nf, M = c.shape
+        out = np.zeros((Nf, int(nsig)))
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_cheby_sqnorms_dev, self._h, float(lmax), Nf, M, _capi.ptr(c), int(nsig),
+                      ctypes.c_void_p(x_ptr), _capi.ptr(out), ctypes.byref(ms))
+        return out, ms.value
+
 
     def tune_placement(self, coeffs, x_ptr, y_ptr, nsig, lmax, candidates=6, stride_mb=0):
         """Draw `candidates` physical backings for the context's streamed workspaces and keep the one on which THIS call

@@ -977,6 +977,42 @@ def frame_panels(bank, order=30, panel=1024, coefficients=None):
     return frame.reshape(Nf * G.N, G.N)
 
 
+def frame_norms(bank, order=30, panel=1024, coefficients=None):
+    """The squared l2 norms of the frame's rows without the frame: (Nf, N), [f, j] = ||p_f(L) delta_j||^2, i.e. row
+    f N + j of compute_frame() squared and summed (features.compute_norm_tig, compute_spectrogram).  Identity panels of
+    `panel` columns are written on the device as in frame_panels and leave as their Nf x w squared column norms
+    (gspx_cheby_sqnorms_dev): neither the frame nor any Nf x N x w output is formed.  `bank`, `coefficients`: as
+    frame_panels."""
+    G, Nf = bank.G, bank.Nf
+    coeffs = _as_coeff_matrix((coefficients or compute_cheby_coeff)(bank, m=order))
+    dev = _device_graph_of(G)
+    norms = np.empty((Nf, G.N))
+    total_ms = 0.0
+    on_device = hasattr(dev, "ctx") and hasattr(dev, "cheby_sqnorms_dev")
+    if on_device:
+        width = max(1, min(panel, G.N))
+        bx = dev.ctx.alloc(max(G.N * width * np.dtype(dev.dtype).itemsize, 16))
+    try:
+        for j0 in range(0, G.N, panel):
+            w = min(panel, G.N - j0)
+            if on_device:
+                dev.ctx.identity_panel(bx, G.N, j0, w, dev.dtype)
+                s, ms = dev.cheby_sqnorms_dev(coeffs, bx.ptr, w, G.lmax)
+            else:  # a stand-in device object (tests): host panel through its array interface, squared here
+                deltas = np.zeros((G.N, w))
+                deltas[j0 + np.arange(w), np.arange(w)] = 1
+                y, ms = dev.cheby_filter(coeffs, deltas, G.lmax, _capi.ANALYSIS)
+                y = np.asarray(y, dtype=np.float64).reshape(Nf, G.N, w)
+                s = np.einsum("fnw,fnw->fw", y, y)
+            norms[:, j0:j0 + w] = s
+            total_ms += ms
+    finally:
+        if on_device:
+            bx.free()
+    _record_timing(G, total_ms)
+    return norms
+
+
 class _HeatKernel:
     """min(exp(-tau x / lmax), 1) / norm; lmax is read from the graph when the kernel is evaluated."""
 

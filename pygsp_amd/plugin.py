@@ -226,9 +226,62 @@ def _patch_lanczos(pygsp_module, wanted):
         delattr(approx, _SAVED_LANCZOS)
 
 
+_SAVED_FEATURES = "_gspx_saved_features"  # (on the features module: compute_norm_tig, compute_spectrogram)
+_FEATURES = ("compute_norm_tig", "compute_spectrogram")
+
+
+def _feature_functions(pygsp_module, saved):
+    """compute_norm_tig and compute_spectrogram of `pygsp_module`'s features module on the device (pygsp_amd.features):
+    its own Filter class and compute_cheby_coeff, the graph's device Laplacian.  Graphs whose size collides with the
+    shape rules (N in {1, Nf}: the identity then reads as a synthesis input, filter.py:270) call the saved originals."""
+    from . import features
+
+    approx = pygsp_module.filters.approximations
+
+    def norms(bank):
+        return _filters.frame_norms(bank, features.ORDER,
+                                    coefficients=lambda b, m: approx.compute_cheby_coeff(b, m=m))
+
+    def compute_norm_tig(g, **kwargs):
+        if g.G.N in (1, g.Nf):
+            return saved["compute_norm_tig"](g, **kwargs)
+        return features._norm_tig(g, norms, **kwargs)
+
+    def compute_spectrogram(G, atom=None, M=100, **kwargs):
+        if G.N == 1:  # (each of the reference's atoms is a bank of one: only N = 1 collides)
+            return saved["compute_spectrogram"](G, atom, M, **kwargs)
+        bank = pygsp_module.filters.Filter(G, features.spectrogram_kernels(G, atom, M))
+        return features._spectrogram(G, bank, norms)
+
+    compute_norm_tig.__doc__ = features.compute_norm_tig.__doc__
+    compute_spectrogram.__doc__ = features.compute_spectrogram.__doc__
+    return {"compute_norm_tig": compute_norm_tig, "compute_spectrogram": compute_spectrogram}
+
+
+def _patch_features(pygsp_module, wanted):
+    """Replace features.compute_norm_tig and compute_spectrogram (wanted), or put back the originals saved by an
+    earlier install (not wanted).  Graph.plot_spectrogram looks compute_spectrogram up at call time and follows."""
+    feats = getattr(pygsp_module, "features", None)
+    if feats is None:
+        if wanted:
+            raise ValueError("features=True: {} has no features module".format(pygsp_module.__name__))
+        return
+    saved = feats.__dict__.get(_SAVED_FEATURES)
+    if wanted:
+        if saved is None:
+            saved = {n: getattr(feats, n) for n in _FEATURES}
+            setattr(feats, _SAVED_FEATURES, saved)
+        for n, fn in _feature_functions(pygsp_module, saved).items():
+            setattr(feats, n, fn)
+    elif saved is not None:
+        for n in _FEATURES:
+            setattr(feats, n, saved[n])
+        delattr(feats, _SAVED_FEATURES)
+
+
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
-            lanczos=False):
+            lanczos=False, features=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -246,7 +299,10 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     `fourier` (default False): also replace ``Graph.compute_fourier_basis`` so that partial requests on large graphs
     run on the device (pygsp_amd.fourier); full bases and small graphs keep the reference's code.
     `lanczos` (default False): also replace ``approximations.lanczos_op`` and the ``pygsp.filters.lanczos_op`` alias
-    with pygsp_amd.filters.lanczos_op (Lanczos filtering on the device, pygsp_amd.lanczos)."""
+    with pygsp_amd.filters.lanczos_op (Lanczos filtering on the device, pygsp_amd.lanczos).
+    `features` (default False): also replace ``pygsp.features.compute_norm_tig`` and ``compute_spectrogram`` with
+    their device forms (pygsp_amd.features: squared column norms of identity panels, no dense frame);
+    ``compute_tig`` already reaches the device through the wrapped ``Filter.compute_frame``."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -282,6 +338,7 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     if graph_cls is not None:
         _patch_graph_class(graph_cls, lmax == "device", bool(fourier))
     _patch_lanczos(pygsp_module, bool(lanczos))
+    _patch_features(pygsp_module, bool(features))
     return pygsp_module
 
 
@@ -312,6 +369,7 @@ def uninstall(pygsp_module=None):
         _config["evaluation"] = None
     approx = pygsp_module.filters.approximations
     _patch_lanczos(pygsp_module, False)
+    _patch_features(pygsp_module, False)
     saved = _restore(approx, ("cheby_op",))
     if saved is None:
         return

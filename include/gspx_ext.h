@@ -109,6 +109,19 @@ int gspx_lanczos_combine_dev(gspx_graph* g, int order, int64_t Nsig, const void*
 int gspx_tikhonov_cg_dev(gspx_graph* g, double tau, const void* mask_dev, int64_t Nsig,
                          const void* y_dev, void* x_dev, double rtol, double atol, int64_t maxiter,
                          int32_t* iterations, double* kernel_ms);
+/* classification_tikhonov_simplex (pygsp/learning.py:111-180): argmin over X (N x n_classes, every row on the
+ * probability simplex) of tau sum(X * L X) + sum_i m_i ||X_i - Y_i||^2, by accelerated forward-backward (FISTA) with
+ * the fixed `step`, started at X_0 = Y; Y is one-hot, zero rows where unmeasured.  float64 graphs only.
+ * labels_dev: N int32 (DEVICE, caller's vertex order), the class 0..n_classes-1 of a measured vertex, -1 for an
+ * unmeasured one (another value: GSPX_ERR_INVALID after one small device pass); n_classes 1..256.  Stopping rule,
+ * tested after every iteration k in this order: obj_k < atol, |obj_k - obj_{k-1}| < dtol, |obj_k - obj_{k-1}| / d <
+ * rtol (d = obj_k, else obj_{k-1}, else 1), ||X_k - X_{k-1}||_F / sqrt(N n_classes) < xtol, k >= maxit (1..1e7); a
+ * negative tolerance disables its criterion.  x_dev: N x n_classes fp64 (DEVICE, caller's order) receives X_niter.
+ * HOST outputs: niter, crit (1 atol, 2 dtol, 3 rtol, 4 xtol, 5 maxit), objective_host (room for maxit + 1 doubles)
+ * obj_0 .. obj_niter.  The same inputs give the same bits on every call. */
+int gspx_tikhonov_simplex_dev(gspx_graph* g, double tau, double step, const int32_t* labels_dev, int n_classes,
+                              double rtol, double atol, double dtol, double xtol, int64_t maxit, void* x_dev,
+                              int64_t* niter, int32_t* crit, double* objective_host, double* kernel_ms);
 /* Differential operator D (L = D D^T) of an UNDIRECTED graph without self loops created from W
  * (pygsp/graphs/difference.py:26-166).  Edges = stored entries (i, j > i) in row-major order, the
  * order of Graph.get_edge_list (graph.py:1019-1029).  Built on the device at first use.

@@ -3273,3 +3273,4 @@ extern "C" int gspx_ctx_tune_placement(gspx_graph* g, double lmax, int M, const 
 #include "gspx_setup.hip.h"
 #include "gspx_spectral.hip.h"
 #include "gspx_lanczos.hip.h"
+#include "gspx_learning.hip.h"

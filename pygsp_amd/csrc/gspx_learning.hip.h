@@ -1,0 +1,423 @@
+// gspx_learning.hip.h - classification_tikhonov_simplex on the device (pygsp_amd/learning.py; the reference's
+// learning.classification_tikhonov_simplex, which drives pyunlocbox's accelerated forward-backward solver).
+//   gspx_tikhonov_simplex_dev   argmin_X tau tr(X^T L X) + sum_i m_i ||X_i - Y_i||^2, every row of X on the
+//                               probability simplex, by FISTA with a fixed step; X is N x C, C = number of classes
+//
+// With f(X) = tau sum(X * LX) + sum_i m_i ||X_i - Y_i||^2, grad f(X) = 2 (m (X - Y) + tau LX) and P the row-wise
+// Euclidean projection onto {x >= 0, sum x = 1}, iteration k (X_0 = V_0 = Y, t_0 = 1) is
+//   X_k = P(V_{k-1} - step grad f(V_{k-1}))
+//   t_k = (1 + sqrt(1 + 4 t_{k-1}^2)) / 2,   b_k = (t_{k-1} - 1) / t_k,   V_k = X_k + b_k (X_k - X_{k-1})
+// and stops on the first of atol / dtol / rtol / xtol / maxit that holds for obj_k = f(X_k) (DESIGN.md,
+// "Simplex-constrained classification").  L is linear, so L V_{k-1} = (1 + b) L X_{k-1} - b L X_{k-2}: one product
+// per iteration, on X_k.  The b_k do not depend on the data and come from the host as launch arguments.
+//
+// Launch k of the loop (all panels N x C fp64 in the graph's INTERNAL vertex order):
+//   k_spx_step_*   X_k from X_{k-1}, X_{k-2}, L X_{k-1}, L X_{k-2} and the labels, row-local; partial sums of
+//                  sum m ||X_k - Y||^2 and ||X_k - X_{k-1}||^2, and of sum X_{k-1} * L X_{k-1} (both read anyway):
+//                  obj_{k-1} is complete only after launch k, so three X buffers rotate and the rule fires on
+//                  X_{k-1} while X_k sits in the third
+//   k_spx_rule     one workgroup: sums the partials in a fixed order, then one thread records obj_{k-1} and applies
+//                  the stopping rule to iteration k - 1 (done flag, niter, criterion)
+//   spmm_internal  L X_k, the engine's product
+// After the done flag is set every step and rule launch returns at once: the host polls the flag every few
+// launches, and what it launches past the stop changes nothing.  Partial sums have one order for a given N and C:
+// the same inputs give the same bits on every call.  Included at the end of gspx.hip.
+#pragma once
+
+namespace gspx {
+
+constexpr int SPX_MAX_CLASSES = 256;
+constexpr int SPX_BLOCKS = 2048;  // fixed grid of the step kernels (grid-stride over rows): one summation order
+constexpr int SPX_POLL = 4;       // the host looks at the done flag every SPX_POLL launches
+constexpr long long SPX_MAXIT_LIMIT = 10000000;  // (the objective sequence is a device array of maxit + 1 doubles)
+
+enum { SPX_ATOL = 1, SPX_DTOL = 2, SPX_RTOL = 3, SPX_XTOL = 4, SPX_MAXIT = 5 };
+
+struct SpxState {     // device resident
+  double data_prev;   // sum m ||X_{k-1} - Y||^2 of the last iterate the rule has not judged yet
+  double dx_prev;     // ||X_{k-1} - X_{k-2}||^2
+  int done;
+  int crit;
+  long long niter;
+  int bad_label;      // a label outside -1..C-1 was seen by k_spx_init
+};
+
+struct SpxStep {
+  const double* A;    // X_{k-1}
+  const double* B;    // X_{k-2} (= A for k = 1)
+  const double* LA;   // L X_{k-1}
+  const double* LB;   // L X_{k-2}
+  const int* lab;     // class per internal row, -1 = unmeasured
+  double* X;          // X_k
+  double* partial;    // [3][gridDim.x]: data term, ||X_k - X_{k-1}||^2, sum X_{k-1} * L X_{k-1}
+  const SpxState* state;
+  int N, C;
+  double b, step, tau;
+  int write;          // 0 on the launch after maxit: only the last objective's dot product is wanted
+};
+
+// labels in the internal order, X_0 = one-hot rows (zero rows for unmeasured vertices)
+__global__ void k_spx_init(const int* __restrict__ labels, const int* __restrict__ perm, int N, int C,
+                           int* __restrict__ lab, double* __restrict__ X0, SpxState* state) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  int l = labels[perm ? perm[i] : i];
+  if (l < -1 || l >= C) {
+    state->bad_label = 1;  // (a plain store of the same value from every offender)
+    l = -1;
+  }
+  lab[i] = l;
+  for (int c = 0; c < C; ++c) X0[(size_t)i * C + c] = c == l ? 1.0 : 0.0;
+}
+
+// the three per-thread sums -> partial[q * gridDim.x + blockIdx.x], wave shuffles then the four waves in order
+__device__ inline void spx_block_sums(double s0, double s1, double s2, double* partial) {
+  __shared__ double ws[3][4];
+  double v[3] = {s0, s1, s2};
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
+  }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    ws[0][w] = v[0];
+    ws[1][w] = v[1];
+    ws[2][w] = v[2];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int q = threadIdx.x;
+    partial[(size_t)q * gridDim.x + blockIdx.x] = (ws[q][0] + ws[q][1]) + (ws[q][2] + ws[q][3]);
+  }
+}
+
+// z = V - step grad f(V) for one entry (y = [c == label], m = [label >= 0])
+__device__ inline double spx_point(const SpxStep& a, double av, double bv, double la, double lb, double m, double y) {
+  const double v = av + a.b * (av - bv);
+  const double lv = (1.0 + a.b) * la - a.b * lb;
+  const double g = 2.0 * (m * (v - y) + a.tau * lv);
+  return v - a.step * g;
+}
+
+// Rows of at most CMAX classes: one row per thread, the row in registers; the projection is Michelot's active-set
+// pass (theta = (sum of the active entries - 1) / their count; drop the entries <= theta; repeat until none drops),
+// exact and sort-free, at most C passes and usually two or three.
+template <int CMAX>
+__global__ __launch_bounds__(256) void k_spx_step_row(SpxStep a) {
+  if (a.state->done) return;
+  const int C = a.C;
+  double sd = 0, sx = 0, ss = 0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < a.N; i += gridDim.x * 256) {
+    const size_t o = (size_t)i * C;
+    const int l = a.lab[i];
+    const double m = l >= 0 ? 1.0 : 0.0;
+    double z[CMAX], xa[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+      if (c < C) {
+        xa[c] = a.A[o + c];
+        ss += xa[c] * a.LA[o + c];
+        if (a.write) z[c] = spx_point(a, xa[c], a.B[o + c], a.LA[o + c], a.LB[o + c], m, c == l ? 1.0 : 0.0);
+      }
+    }
+    if (!a.write) continue;
+    unsigned act = (C >= 32) ? ~0u : ((1u << C) - 1u);
+    double theta = 0;
+    for (int pass = 0; pass < CMAX; ++pass) {
+      double s = 0;
+      int n = 0;
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c)
+        if ((act >> c) & 1u) {
+          s += z[c];
+          ++n;
+        }
+      theta = (s - 1.0) / n;
+      unsigned keep = act;
+#pragma unroll
+      for (int c = 0; c < CMAX; ++c)
+        if (((act >> c) & 1u) && z[c] <= theta) keep &= ~(1u << c);
+      if (keep == act) break;
+      act = keep;
+    }
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+      if (c < C) {
+        const double x = fmax(z[c] - theta, 0.0);
+        a.X[o + c] = x;
+        const double e = x - (c == l ? 1.0 : 0.0);
+        sd += m * (e * e);
+        const double d = x - xa[c];
+        sx += d * d;
+      }
+    }
+  }
+  spx_block_sums(sd, sx, ss, a.partial);
+}
+
+__device__ inline double spx_wave_sum(double v) {  // butterfly: every lane ends with the same bits
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// Rows of 17..64 VPL classes: one row per wave, lane l holds classes l + 64 j (j < VPL); the same Michelot pass with
+// wave sums.
+template <int VPL>
+__global__ __launch_bounds__(256) void k_spx_step_wave(SpxStep a) {
+  if (a.state->done) return;
+  const int C = a.C;
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  double sd = 0, sx = 0, ss = 0;
+  for (int i = wave; i < a.N; i += gridDim.x * 4) {
+    const size_t o = (size_t)i * C;
+    const int l = a.lab[i];
+    const double m = l >= 0 ? 1.0 : 0.0;
+    double z[VPL], xa[VPL];
+    bool act[VPL];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+      const int c = lane + 64 * j;
+      act[j] = c < C;
+      z[j] = 0;
+      xa[j] = 0;
+      if (c < C) {
+        xa[j] = a.A[o + c];
+        ss += xa[j] * a.LA[o + c];
+        if (a.write) z[j] = spx_point(a, xa[j], a.B[o + c], a.LA[o + c], a.LB[o + c], m, c == l ? 1.0 : 0.0);
+      }
+    }
+    if (!a.write) continue;
+    double theta = 0;
+    for (int pass = 0; pass < 64 * VPL; ++pass) {
+      double s = 0, n = 0;
+#pragma unroll
+      for (int j = 0; j < VPL; ++j)
+        if (act[j]) {
+          s += z[j];
+          n += 1.0;
+        }
+      s = spx_wave_sum(s);
+      n = spx_wave_sum(n);
+      theta = (s - 1.0) / n;
+      bool drop = false;
+#pragma unroll
+      for (int j = 0; j < VPL; ++j)
+        if (act[j] && z[j] <= theta) {
+          act[j] = false;
+          drop = true;
+        }
+      if (!__any(drop)) break;
+    }
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+      const int c = lane + 64 * j;
+      if (c < C) {
+        const double x = fmax(z[j] - theta, 0.0);
+        a.X[o + c] = x;
+        const double e = x - (c == l ? 1.0 : 0.0);
+        sd += m * (e * e);
+        const double d = x - xa[j];
+        sx += d * d;
+      }
+    }
+  }
+  spx_block_sums(sd, sx, ss, a.partial);
+}
+
+// After launch k: obj_{k-1} = tau sum(X_{k-1} L X_{k-1}) + data_{k-1}; the rule on iteration k - 1 >= 1; then the
+// sums of X_k wait in the state for the next launch.  One workgroup of 256 threads, thread t sums partials
+// t, t + 256, ... in order, the threads are combined as in spx_block_sums; thread 0 applies the rule.
+__global__ __launch_bounds__(256) void k_spx_rule(SpxState* state, const double* __restrict__ partial, int nb,
+                                                  long long k, double tau, double rtol, double atol, double dtol,
+                                                  double xtol, long long maxit, double nc, double* __restrict__ obj) {
+  if (state->done) return;
+  __shared__ double ws[3][4];
+  double v[3] = {0, 0, 0};
+  for (int b = threadIdx.x; b < nb; b += 256) {
+    v[0] += partial[b];
+    v[1] += partial[(size_t)nb + b];
+    v[2] += partial[(size_t)2 * nb + b];
+  }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    ws[0][threadIdx.x >> 6] = v[0];
+    ws[1][threadIdx.x >> 6] = v[1];
+    ws[2][threadIdx.x >> 6] = v[2];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double data = (ws[0][0] + ws[0][1]) + (ws[0][2] + ws[0][3]);
+  const double dx = (ws[1][0] + ws[1][1]) + (ws[1][2] + ws[1][3]);
+  const double smooth = (ws[2][0] + ws[2][1]) + (ws[2][2] + ws[2][3]);
+  const long long it = k - 1;
+  const double cur = tau * smooth + state->data_prev;
+  obj[it] = cur;
+  if (it >= 1) {
+    const double prev = obj[it - 1];
+    const double diff = fabs(cur - prev);
+    double den = cur;
+    if (den == 0) den = prev;
+    if (den == 0) den = 1.0;
+    int crit = 0;
+    if (atol >= 0 && cur < atol) crit = SPX_ATOL;
+    else if (dtol >= 0 && diff < dtol) crit = SPX_DTOL;
+    else if (rtol >= 0 && diff / den < rtol) crit = SPX_RTOL;
+    else if (xtol >= 0 && sqrt(state->dx_prev) / sqrt(nc) < xtol) crit = SPX_XTOL;
+    else if (it >= maxit) crit = SPX_MAXIT;
+    if (crit) {
+      state->crit = crit;
+      state->niter = it;
+      state->done = 1;
+      return;
+    }
+  }
+  state->data_prev = data;
+  state->dx_prev = dx;
+}
+
+}  // namespace gspx
+
+using gspx::SpxState;
+using gspx::SpxStep;
+
+static int spx_launch_step(const SpxStep& a, int nb, hipStream_t st) {
+  const int C = a.C;
+  if (C <= 2) hipLaunchKernelGGL((gspx::k_spx_step_row<2>), dim3(nb), dim3(256), 0, st, a);
+  else if (C <= 4) hipLaunchKernelGGL((gspx::k_spx_step_row<4>), dim3(nb), dim3(256), 0, st, a);
+  else if (C <= 8) hipLaunchKernelGGL((gspx::k_spx_step_row<8>), dim3(nb), dim3(256), 0, st, a);
+  else if (C <= 16) hipLaunchKernelGGL((gspx::k_spx_step_row<16>), dim3(nb), dim3(256), 0, st, a);
+  else if (C <= 64) hipLaunchKernelGGL((gspx::k_spx_step_wave<1>), dim3(nb), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((gspx::k_spx_step_wave<4>), dim3(nb), dim3(256), 0, st, a);
+  return GSPX_OK;
+}
+
+static int spx_blocks(int64_t N, int C) {  // a function of N and C alone: the partial sums keep one order
+  const int64_t rows_per_block = C <= 16 ? 256 : 4;
+  return (int)std::max<int64_t>(1, std::min<int64_t>(gspx::SPX_BLOCKS, (N + rows_per_block - 1) / rows_per_block));
+}
+
+static int tikhonov_simplex_t(gspx_graph* g, double tau, double step, const int32_t* labels, int C, double rtol,
+                              double atol, double dtol, double xtol, int64_t maxit, double* x, int64_t* niter,
+                              int32_t* crit, double* objective, double* ms) {
+  gspx_ctx* ctx = g->ctx;
+  hipStream_t st = ctx->stream;
+  const int64_t N = g->N;
+  const size_t U = (size_t)N * C;
+  const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
+  const int* iperm = g->has_perm ? g->iperm.as<int>() : nullptr;
+  const int nb = spx_blocks(N, C);
+  DevMem panels, lab, part, obj, state;
+  // panels 256-byte aligned, with room for the product kernels' vector reads past a panel's end
+  const size_t pitch = (U * sizeof(double) + 511) & ~(size_t)255;
+  const size_t pad = 256;
+  CHK(panels.alloc(5 * pitch));
+  CHK(lab.alloc((size_t)N * sizeof(int) + pad));
+  CHK(part.alloc((size_t)3 * nb * sizeof(double)));
+  CHK(obj.alloc((size_t)(maxit + 1) * sizeof(double)));
+  CHK(state.alloc(sizeof(SpxState)));
+  double* X[3];
+  double* LX[2];
+  for (int j = 0; j < 5; ++j) {
+    double* p = (double*)((char*)panels.p + j * pitch);
+    if (j < 3) X[j] = p;
+    else LX[j - 3] = p;
+  }
+  SpxState* sd = (SpxState*)state.p;
+  HIPCHK(hipEventRecord(ctx->ev[0], st));
+  HIPCHK(hipMemsetAsync(state.p, 0, sizeof(SpxState), st));
+  hipLaunchKernelGGL(gspx::k_spx_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, labels, perm, (int)N, C,
+                     lab.as<int>(), X[0], sd);
+  SpxState hs{};
+  HIPCHK(hipMemcpyAsync(&hs, sd, sizeof(SpxState), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (hs.bad_label) return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: a label lies outside -1..n_classes-1");
+  CHK(spmm_internal<double>(g, g->rval.as<double>(), 1.0, 0.0, X[0], LX[0], (unsigned)C, nullptr, 0));
+  SpxStep a{};
+  a.lab = lab.as<int>();
+  a.partial = part.as<double>();
+  a.state = sd;
+  a.N = (int)N;
+  a.C = C;
+  a.step = step;
+  a.tau = tau;
+  double t = 1.0, b = 0.0;  // t_{k-1} and b_{k-1} of launch k (V_0 = X_0: b_0 = 0)
+  for (int64_t k = 1; k <= maxit + 1; ++k) {
+    a.A = X[(k - 1) % 3];
+    a.B = k >= 2 ? X[(k - 2) % 3] : a.A;
+    a.LA = LX[(k - 1) % 2];
+    a.LB = k >= 2 ? LX[(k - 2) % 2] : a.LA;
+    a.X = X[k % 3];
+    a.b = b;
+    a.write = k <= maxit;
+    CHK(spx_launch_step(a, nb, st));
+    hipLaunchKernelGGL(gspx::k_spx_rule, dim3(1), dim3(256), 0, st, sd, part.as<double>(), nb, (long long)k, tau,
+                       rtol, atol, dtol, xtol, (long long)maxit, (double)U, obj.as<double>());
+    if (k <= maxit) CHK(spmm_internal<double>(g, g->rval.as<double>(), 1.0, 0.0, X[k % 3], LX[k % 2], (unsigned)C,
+                                              nullptr, 0));
+    const double tn = (1.0 + std::sqrt(1.0 + 4.0 * t * t)) / 2.0;  // t_k, b_k = (t_{k-1} - 1) / t_k
+    b = (t - 1.0) / tn;
+    t = tn;
+    if (k % gspx::SPX_POLL == 0 && k <= maxit) {
+      int done = 0;
+      HIPCHK(hipMemcpyAsync(&done, &sd->done, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (done) break;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(&hs, sd, sizeof(SpxState), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (!hs.done) return set_err(GSPX_ERR_HIP, "tikhonov_simplex: the stopping rule did not fire");
+  const int64_t n_it = hs.niter;
+  CHK(permute_panel<double>(g, X[n_it % 3], (unsigned)C, x, (unsigned)C, iperm));
+  HIPCHK(hipMemcpyAsync(objective, obj.p, (size_t)(n_it + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  float f = 0;
+  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
+  if (ms) *ms = f;
+  *niter = n_it;
+  *crit = hs.crit;
+  return GSPX_OK;
+}
+
+extern "C" int gspx_tikhonov_simplex_dev(gspx_graph* g, double tau, double step, const int32_t* labels_dev,
+                                         int n_classes, double rtol, double atol, double dtol, double xtol,
+                                         int64_t maxit, void* x_dev, int64_t* niter, int32_t* crit,
+                                         double* objective_host, double* kernel_ms) {
+  if (!(tau > 0) || !std::isfinite(tau)) return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: tau must be positive and finite");
+  if (!(step > 0) || !std::isfinite(step))
+    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: step must be positive and finite");
+  if (maxit < 1 || maxit > gspx::SPX_MAXIT_LIMIT)
+    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: maxit must be 1..%lld (got %lld)",
+                   gspx::SPX_MAXIT_LIMIT, (long long)maxit);
+  if (n_classes < 1 || n_classes > gspx::SPX_MAX_CLASSES)
+    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: n_classes must be 1..%d (got %d)", gspx::SPX_MAX_CLASSES,
+                   n_classes);
+  if (std::isnan(rtol) || std::isnan(atol) || std::isnan(dtol) || std::isnan(xtol))
+    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: a tolerance is NaN (a negative one disables its criterion)");
+  if (!niter || !crit || !objective_host) return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: null host output");
+  if (g) replay_reset(g->ctx);
+  if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
+  if (g->N > 0 && (!labels_dev || !x_dev)) return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: null device pointer");
+  if (g->dtype != GSPX_F64)
+    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: the graph computes in float32; the solver needs the float64 graph");
+  if ((double)g->N * n_classes * sizeof(double) > (double)(((size_t)1 << 31) - 65536))
+    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: an N x n_classes panel exceeds 2 GiB");
+  if (kernel_ms) *kernel_ms = 0;
+  if (g->N == 0) {
+    *niter = 0;
+    *crit = 0;
+    return GSPX_OK;
+  }
+  HIPCHK(hipSetDevice(g->ctx->device));
+  return tikhonov_simplex_t(g, tau, step, labels_dev, n_classes, rtol, atol, dtol, xtol, maxit, (double*)x_dev, niter,
+                            crit, objective_host, kernel_ms);
+}

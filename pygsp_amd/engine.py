@@ -1105,6 +1105,37 @@ def _ops_methods():
             bx.free()
         return (x[:, 0] if one_d else x), iters, ms
 
+    def tikhonov_simplex(self, tau, step, labels, n_classes, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
+        """FISTA on the simplex-constrained Tikhonov problem of learning.classification_tikhonov_simplex
+        (gspx_tikhonov_simplex_dev), on this float64 graph.  labels: N ints in the graph's vertex order, the class
+        0..n_classes-1 of a measured vertex, -1 for an unmeasured one; a tolerance of None is off.  Returns (X (N,
+        n_classes) float64, info) with info = {'niter', 'crit' ('ATOL', 'DTOL', 'RTOL', 'XTOL' or 'MAXIT'),
+        'objective' (obj_0 .. obj_niter), 'ms' (device time)}."""
+        if self.dtype != np.float64:
+            raise ValueError("tikhonov_simplex runs on the float64 device graph")
+        lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
+        if lab.size != self.N:
+            raise ValueError("labels must hold one entry per vertex")
+        n_classes, maxit = int(n_classes), int(maxit)
+        off = lambda v: -1.0 if v is None else float(v)
+        obj = np.zeros(max(maxit, 0) + 1, dtype=np.float64)
+        niter, crit, ms = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0)
+        bl = self.ctx.upload(lab)
+        bx = self.ctx.alloc(max(self.N * max(n_classes, 1) * 8, 16))
+        try:
+            self.ctx.call(_capi.load().gspx_tikhonov_simplex_dev,
+                self._h, float(tau), float(step), ctypes.c_void_p(bl.ptr), n_classes, off(rtol), off(atol), off(dtol),
+                off(xtol), maxit, ctypes.c_void_p(bx.ptr), ctypes.byref(niter), ctypes.byref(crit), _capi.ptr(obj),
+                ctypes.byref(ms))
+            X = bx.download((self.N, n_classes), np.float64)
+        finally:
+            bl.free()
+            bx.free()
+        crits = {1: "ATOL", 2: "DTOL", 3: "RTOL", 4: "XTOL", 5: "MAXIT"}
+        info = {"niter": int(niter.value), "crit": crits.get(crit.value), "objective": obj[:niter.value + 1].copy(),
+                "ms": ms.value}
+        return X, info
+
     def lanczos_basis(self, x, order, breakdown=0.0):
         """The Krylov stacks of gspx_lanczos_krylov_dev for x (N,) or (N, n), n <= 256, on this float64 graph,
         downloaded: (V (N, order[, n]) in the caller's vertex order, alpha (order[, n]), beta (order[, n]: row 0 is
@@ -1185,7 +1216,7 @@ def _ops_methods():
         return _edge_op(self, y, n_edges(self), self.N, div_dev, "div")
 
     for f in (laplacian_apply_dev, laplacian_apply, dirichlet_energy_dev, dirichlet_energy,
-              tikhonov_cg_dev, tikhonov_cg, lanczos_basis, n_edges, edge_list, differential_operator, set_edge_list,
+              tikhonov_cg_dev, tikhonov_cg, tikhonov_simplex, lanczos_basis, n_edges, edge_list, differential_operator, set_edge_list,
               grad_dev, div_dev, grad, div):
         setattr(DeviceGraph, f.__name__, f)
 

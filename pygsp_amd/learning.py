@@ -5,6 +5,10 @@ conjugate gradients (pygsp/learning.py:324-337, one scipy.sparse.linalg.cg call 
 all columns advance together on the GPU with the same recurrence and stopping rule
 (gspx_tikhonov_cg_dev).  The tau = 0 branch of the reference is a direct sparse solve
 (spsolve, learning.py:342-367), not a sparse-product loop: it is not part of this engine and raises.
+
+classification_tikhonov_simplex (learning.py:111-180) keeps every row of the solution on the probability simplex.
+The reference hands it to pyunlocbox's accelerated forward-backward solver; here the same iteration runs on the
+device (gspx_tikhonov_simplex_dev, DESIGN.md "Simplex-constrained classification") and pyunlocbox is not needed.
 """
 import numpy as np
 
@@ -43,3 +47,70 @@ def classification_tikhonov(G, y, M, tau=0, **kwargs):
     """Tikhonov regression of the one-hot encoded labels (learning.py:170-251)."""
     labels, _ = _measured_only(y, M)
     return regression_tikhonov(G, _one_hot(labels), M, tau, **kwargs)
+
+
+SIMPLEX_OPTIONS = ("rtol", "atol", "dtol", "xtol", "maxit", "verbosity")
+SIMPLEX_MAX_CLASSES = 256
+
+
+def simplex_labels(y, M):
+    """(labels, n_classes) of the simplex solver: y copied, zeroed where unmeasured and cast to int (NaN may sit at
+    unmeasured vertices), n_classes = max + 1 of those, labels = the class where measured and -1 elsewhere (learning.py:
+    120-123).  A negative or NaN measured label is a ValueError: the reference would index the last column with it."""
+    keep = np.asarray(M).reshape(-1).astype(bool)
+    yz = np.array(y, dtype=np.float64, copy=True).reshape(-1)
+    yz[~keep] = 0
+    if not np.isfinite(yz).all():
+        raise ValueError("measured labels must be finite")
+    yi = yz.astype(int)
+    if (yi < 0).any():
+        raise ValueError("labels must be >= 0 at measured vertices")
+    n_classes = int(yi.max()) + 1 if yi.size else 1
+    if n_classes > SIMPLEX_MAX_CLASSES:
+        raise ValueError("at most {} classes are supported, got {}".format(SIMPLEX_MAX_CLASSES, n_classes))
+    return np.where(keep, yi, -1).astype(np.int32), n_classes
+
+
+def simplex_step(G, tau):
+    """The reference's fixed step 0.5 / (1 + tau lambda_max) (G.lmax warns and estimates when unset)."""
+    return 0.5 / (1 + tau * G.lmax)
+
+
+def _simplex_device_graph(G):
+    if hasattr(G, "device_graph"):
+        return G.device_graph(np.float64)
+    from . import plugin
+    return plugin.device_graph_for(G, dtype=np.float64)
+
+
+def classification_tikhonov_simplex(G, y, M, tau=0.1, **kwargs):
+    """Classification on the graph by Tikhonov minimisation, every row of the result on the probability simplex
+    (learning.py:111-180): argmin_X tau tr(X^T L X) + sum_i m_i ||X_i - Y_i||^2 subject to X >= 0 and X 1 = 1, Y the
+    one-hot labels (zero rows where unmeasured).  Returns X, (N, n_classes) float64.
+
+    The solver is FISTA with the reference's step 0.5 / (1 + tau G.lmax), started at Y, on the float64 device graph,
+    and stops on the first of these criteria that holds for obj_k = f(X_k): ``atol`` (obj_k < atol), ``dtol``
+    (|obj_k - obj_{k-1}| < dtol), ``rtol`` (the same difference relative to obj_k; default 1e-3), ``xtol``
+    (||X_k - X_{k-1}||_F / sqrt(N n_classes) < xtol) and ``maxit`` (default 200).  atol, dtol and xtol default to
+    None (off); ``verbosity`` is accepted and ignored; any other keyword is a TypeError.  This is meant to be the
+    iteration of pyunlocbox's forward_backward with its default acceleration, driven by solvers.solve; bit parity
+    with pyunlocbox is not claimed and has not been checked.  Unlike the reference, a negative label at a measured
+    vertex is a ValueError (the reference would silently put it in the last class), as are more than 256 classes."""
+    X, _ = simplex_solve(G, y, M, tau, **kwargs)
+    return X
+
+
+def simplex_solve(G, y, M, tau=0.1, **kwargs):
+    """classification_tikhonov_simplex that also returns the solver's info dict (niter, crit, objective, ms)."""
+    unknown = sorted(set(kwargs) - set(SIMPLEX_OPTIONS))
+    if unknown:
+        raise TypeError("classification_tikhonov_simplex() got unexpected keyword argument(s) {}".format(
+            ", ".join(repr(k) for k in unknown)))
+    if tau <= 0:
+        raise ValueError("Tau should be greater than 0.")
+    if np.size(M) != G.n_vertices:
+        raise ValueError("M should be of size [G.n_vertices,]")
+    labels, n_classes = simplex_labels(y, M)
+    opts = {k: kwargs[k] for k in ("rtol", "atol", "dtol", "xtol", "maxit") if k in kwargs}
+    step = simplex_step(G, tau)
+    return _simplex_device_graph(G).tikhonov_simplex(tau, step, labels, n_classes, **opts)

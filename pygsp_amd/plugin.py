@@ -279,9 +279,59 @@ def _patch_features(pygsp_module, wanted):
         delattr(feats, _SAVED_FEATURES)
 
 
+_SAVED_LEARNING = "_gspx_saved_learning"  # (on the learning module: the two functions below)
+_LEARNING = ("classification_tikhonov_simplex", "regression_tikhonov")
+
+
+def _learning_functions(saved):
+    """classification_tikhonov_simplex on the device (pygsp_amd.learning, no pyunlocbox) and regression_tikhonov whose
+    tau > 0 branch with a sparse L runs the device conjugate gradients; tau <= 0 and a dense L call the saved
+    original.  classification_tikhonov looks regression_tikhonov up at call time and follows."""
+    from . import learning
+
+    def regression_tikhonov(G, y, M, tau=0):
+        if not (tau > 0 and sparse.issparse(G.L)):
+            return saved["regression_tikhonov"](G, y, M, tau)
+        keep = np.asarray(M).reshape(-1).astype(bool)
+        y = np.array(y, dtype=np.float64, copy=True)
+        y[~keep] = 0  # (learning.py:326: NaN may sit at unmeasured vertices)
+        # the reference's cg with scipy's defaults: rtol 1e-5, atol 0, maxiter 10 N (learning.py:328-335)
+        solution, _, _ = device_graph_for(G).tikhonov_cg(tau, keep, y)
+        return np.asarray(solution, dtype=np.float64)
+
+    def classification_tikhonov_simplex(G, y, M, tau=0.1, **kwargs):
+        return learning.classification_tikhonov_simplex(G, y, M, tau, **kwargs)
+
+    regression_tikhonov.__doc__ = saved["regression_tikhonov"].__doc__
+    classification_tikhonov_simplex.__doc__ = learning.classification_tikhonov_simplex.__doc__
+    return {"classification_tikhonov_simplex": classification_tikhonov_simplex,
+            "regression_tikhonov": regression_tikhonov}
+
+
+def _patch_learning(pygsp_module, wanted):
+    """Replace learning.classification_tikhonov_simplex and regression_tikhonov (wanted), or put back the originals
+    saved by an earlier install (not wanted)."""
+    learn = getattr(pygsp_module, "learning", None)
+    if learn is None:
+        if wanted:
+            raise ValueError("learning=True: {} has no learning module".format(pygsp_module.__name__))
+        return
+    saved = learn.__dict__.get(_SAVED_LEARNING)
+    if wanted:
+        if saved is None:
+            saved = {n: getattr(learn, n) for n in _LEARNING}
+            setattr(learn, _SAVED_LEARNING, saved)
+        for n, fn in _learning_functions(saved).items():
+            setattr(learn, n, fn)
+    elif saved is not None:
+        for n in _LEARNING:
+            setattr(learn, n, saved[n])
+        delattr(learn, _SAVED_LEARNING)
+
+
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
-            lanczos=False, features=False):
+            lanczos=False, features=False, learning=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -302,7 +352,10 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     with pygsp_amd.filters.lanczos_op (Lanczos filtering on the device, pygsp_amd.lanczos).
     `features` (default False): also replace ``pygsp.features.compute_norm_tig`` and ``compute_spectrogram`` with
     their device forms (pygsp_amd.features: squared column norms of identity panels, no dense frame);
-    ``compute_tig`` already reaches the device through the wrapped ``Filter.compute_frame``."""
+    ``compute_tig`` already reaches the device through the wrapped ``Filter.compute_frame``.
+    `learning` (default False): also replace ``pygsp.learning.classification_tikhonov_simplex`` (on the device, without
+    pyunlocbox) and ``regression_tikhonov`` (tau > 0 with a sparse L: the device conjugate gradients; otherwise the
+    original); ``classification_tikhonov`` looks ``regression_tikhonov`` up at call time and follows."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -339,6 +392,7 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         _patch_graph_class(graph_cls, lmax == "device", bool(fourier))
     _patch_lanczos(pygsp_module, bool(lanczos))
     _patch_features(pygsp_module, bool(features))
+    _patch_learning(pygsp_module, bool(learning))
     return pygsp_module
 
 
@@ -370,6 +424,7 @@ def uninstall(pygsp_module=None):
     approx = pygsp_module.filters.approximations
     _patch_lanczos(pygsp_module, False)
     _patch_features(pygsp_module, False)
+    _patch_learning(pygsp_module, False)
     saved = _restore(approx, ("cheby_op",))
     if saved is None:
         return

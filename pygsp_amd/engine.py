@@ -1,4 +1,5 @@
-"""Thin object layer over the libgspx C-ABI: Context, DeviceBuffer, DeviceGraph.
+"""Thin object layer over the libgspx C-ABI: Context, DeviceBuffer, DeviceArray, Comm, DeviceGraph, DeviceAdjacency
+and the device graph builders (knn_graph, radius_graph, sbm_graph).
 
 Nothing here computes: every numeric result comes out of the HIP kernels in
 pygsp_amd/csrc.  Vertex reordering (a graph-setup step, like building the Laplacian) is the
@@ -88,16 +89,13 @@ class Context:
     # touched from DeviceArray.__del__ (any thread the collector runs on) and from user threads: one lock.
     POOL_BYTES = 8 << 30
 
-    def _pool_state(self):
-        return self._pool_lock
-
     def pooled_bytes(self):
-        with self._pool_state():
+        with self._pool_lock:
             return self._pooled
 
     def take(self, nbytes):
         nbytes = max(int(nbytes), 16)
-        with self._pool_state():
+        with self._pool_lock:
             stack = self._pool.get(nbytes)
             if stack:
                 self._pooled -= nbytes
@@ -105,7 +103,7 @@ class Context:
         return DeviceBuffer(self, nbytes)  # (through call(): trims the pool and retries if the device is full)
 
     def give(self, buf):
-        with self._pool_state():
+        with self._pool_lock:
             if not getattr(buf, "_h", None) or buf.ctx is not self or self._pooled + buf.nbytes > self.POOL_BYTES:
                 buf.free()
                 return
@@ -113,7 +111,7 @@ class Context:
             self._pooled += buf.nbytes
 
     def clear_pool(self):
-        with self._pool_state():
+        with self._pool_lock:
             stacks, self._pool, self._pooled = list(self._pool.values()), {}, 0
         for stack in stacks:
             for buf in stack:
@@ -166,6 +164,10 @@ class Context:
         buf = DeviceBuffer(self, arr.nbytes)
         buf.upload(arr)
         return buf
+
+    def _temporaries(self):
+        """``with ctx._temporaries() as t``: the device buffers of one host-array call (_Temporaries)."""
+        return _Temporaries(self)
 
     def identity_panel(self, buf, N, j0, w, dtype):
         """Write columns [j0, j0 + w) of the N x N identity into `buf` (row-major N x w, on the device)."""
@@ -224,6 +226,36 @@ class DeviceBuffer:
         out = np.empty(shape, dtype=dtype)
         _capi.check(_capi.load().gspx_buf_download(self._h, _capi.ptr(out), out.nbytes))
         return out
+
+
+class _Temporaries:
+    """The DeviceBuffers of one call (Context._temporaries): upload() and alloc() hand them out, and every one of
+    them is freed, in the order they were made, when the ``with`` block ends - also when an exception passes through."""
+
+    def __init__(self, ctx):
+        self.ctx, self._bufs = ctx, []
+
+    def add(self, buf):
+        self._bufs.append(buf)
+        return buf
+
+    def upload(self, arr):
+        return self.add(self.ctx.upload(arr))
+
+    def alloc(self, nbytes):
+        return self.add(self.ctx.alloc(max(int(nbytes), 16)))  # (a zero-size output still gets a valid pointer)
+
+    def keep(self, buf):
+        """`buf` outlives the block: the caller owns it from here on."""
+        self._bufs.remove(buf)
+        return buf
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for buf in self._bufs:
+            buf.free()
 
 
 class DeviceArray:
@@ -445,22 +477,17 @@ def filter_batch(jobs, root_ctx=None):
     errs = []
 
     def work(i):
-        bx = by = None
         try:
             dev, c, x, lmax = jobs[i]
-            c2 = np.atleast_2d(np.asarray(c, dtype=np.float64))
+            c2 = _coeff_matrix(c)
             x = np.ascontiguousarray(x, dtype=dev.dtype)
-            bx = dev.ctx.upload(x)
-            by = dev.ctx.alloc(x.nbytes * c2.shape[0])
-            dev.cheby_filter_dev(c2, bx.ptr, by.ptr, x.shape[1], lmax)
-            outs[i] = (by, (c2.shape[0],) + x.shape, dev.dtype)
-            by = None  # owned by outs from here on
+            with dev.ctx._temporaries() as t:
+                bx = t.upload(x)
+                by = t.add(dev.ctx.alloc(x.nbytes * c2.shape[0]))  # (exactly the bytes gather() concatenates)
+                dev.cheby_filter_dev(c2, bx.ptr, by.ptr, x.shape[1], lmax)
+                outs[i] = (t.keep(by), (c2.shape[0],) + x.shape, dev.dtype)  # owned by outs from here on
         except Exception as e:  # surfaced on the caller's thread
             errs.append(e)
-        finally:
-            for b in (bx, by):
-                if b is not None:
-                    b.free()
 
     by_ctx = {}
     for i, j in enumerate(jobs):
@@ -491,17 +518,48 @@ def filter_batch(jobs, root_ctx=None):
             root.free()
 
 
+def _int32_csr(M):
+    """(indptr, indices) of the scipy CSR matrix M as int32 arrays: its own when they are already."""
+    indptr, indices = M.indptr, M.indices
+    if indptr.dtype != np.int32 or indices.dtype != np.int32:
+        if M.shape[0] >= 2 ** 31 - 1 or M.nnz >= 2 ** 31 - 1:
+            raise ValueError("graph too large for int32 CSR indices")
+        indptr, indices = indptr.astype(np.int32), indices.astype(np.int32)
+    return indptr, indices
+
+
 def _canonical_csr(M):
     M = sparse.csr_matrix(M)
     if not M.has_canonical_format:
         M = M.copy()
         M.sum_duplicates()
-    if M.indices.dtype != np.int32 or M.indptr.dtype != np.int32:
-        if M.shape[0] >= 2 ** 31 - 1 or M.nnz >= 2 ** 31 - 1:
-            raise ValueError("graph too large for int32 CSR indices")
-        M = sparse.csr_matrix((M.data, M.indices.astype(np.int32), M.indptr.astype(np.int32)),
-                              shape=M.shape)
+    indptr, indices = _int32_csr(M)
+    if indptr is not M.indptr:
+        M = sparse.csr_matrix((M.data, indices, indptr), shape=M.shape)
     return M
+
+
+def _lap_code(lap_type):
+    if lap_type not in ("combinatorial", "normalized"):
+        raise ValueError("Unknown Laplacian type {}".format(lap_type))
+    return _capi.LAP_COMBINATORIAL if lap_type == "combinatorial" else _capi.LAP_NORMALIZED
+
+
+def _coeff_matrix(coeffs):
+    """Chebyshev coefficients as the contiguous float64 (Nf, M) matrix libgspx reads; a vector is one filter."""
+    return np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+
+
+def _program_columns(program):
+    """(S, scale, beta, gamma): the rows (scale, beta, gamma) of a polynomial program as three contiguous columns."""
+    prog = np.ascontiguousarray(program, dtype=np.float64).reshape(-1, 3)
+    return (prog.shape[0],) + tuple(np.ascontiguousarray(prog[:, k]) for k in range(3))
+
+
+def _curve_coords(coords, n_vertices):
+    """True when a space-filling curve can order the vertices by `coords`: one row per vertex, at least two columns."""
+    return (coords is not None and np.ndim(coords) == 2 and np.shape(coords)[0] == n_vertices
+            and np.shape(coords)[1] >= 2)
 
 
 def hilbert_order(coords, bits=16):
@@ -541,7 +599,7 @@ def locality_order(W, coords=None, curve="auto", device=0, ctx=None):
     N = W.shape[0]
     if N < 2:
         return None
-    has_coords = coords is not None and np.ndim(coords) == 2 and coords.shape[0] == N and coords.shape[1] >= 2
+    has_coords = _curve_coords(coords, N)
     if has_coords and N >= 4096 and _capi.device_count() > 0:
         # curve keys and their stable argsort (a radix sort) on the device: gspx_curve_order
         hil = curve == "hilbert" or (curve == "auto" and coords.shape[1] == 2)
@@ -631,7 +689,7 @@ def auto_order(W, coords=None, device=0, ctx=None):
     """The internal order `reorder='auto'` picks: Morton order when coordinates exist, otherwise
     reverse Cuthill-McKee - but only if it beats the graph's own order on `locality_score`
     (block-structured graphs such as a sorted SBM are already local; RCM would scramble them)."""
-    has_coords = coords is not None and np.ndim(coords) == 2 and np.shape(coords)[0] == W.shape[0] and np.shape(coords)[1] >= 2
+    has_coords = _curve_coords(coords, W.shape[0])
     if not has_coords and expander_like(W):
         return None  # a random-like graph: no order helps, skip the reverse Cuthill-McKee pass
     perm = locality_order(W, coords, device=device, ctx=ctx)
@@ -652,18 +710,17 @@ class DeviceGraph:
         self.N = int(N)
         self.dtype = np.dtype(dtype)
 
+    # ---- construction --------------------------------------------------------------------------
     @classmethod
     def from_w(cls, W, lap_type="combinatorial", dtype=np.float64, perm=None, ctx=None):
         """graph.py:510-630 on device.  W must be symmetric (undirected)."""
         ctx = ctx or default_context()
-        if lap_type not in ("combinatorial", "normalized"):
-            raise ValueError("Unknown Laplacian type {}".format(lap_type))
+        lap = _lap_code(lap_type)
         W = _canonical_csr(W)
         data = W.data
         if data.dtype not in (np.float32, np.float64):
             data = data.astype(np.float64)  # int64 adjacency (ER/SBM) -> float64, as scipy does
         data = np.ascontiguousarray(data)
-        lap = _capi.LAP_COMBINATORIAL if lap_type == "combinatorial" else _capi.LAP_NORMALIZED
         p = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
         h = ctypes.c_void_p()
         ctx.call(_capi.load().gspx_graph_create_from_w,
@@ -683,16 +740,11 @@ class DeviceGraph:
         is directed or stores explicit zeros - the caller prepares W on the host (graph.py:613-616) and uses
         from_w.  Raises ValueError for NaN / inf entries (the reference's messages) and for a non-canonical CSR."""
         ctx = ctx or default_context()
-        if lap_type not in ("combinatorial", "normalized"):
-            raise ValueError("Unknown Laplacian type {}".format(lap_type))
+        lap = _lap_code(lap_type)
         if not sparse.isspmatrix_csr(W):
             W = sparse.csr_matrix(W)
-        N = W.shape[0]
-        indptr, indices, data = W.indptr, W.indices, W.data
-        if indptr.dtype != np.int32 or indices.dtype != np.int32:
-            if N >= 2 ** 31 - 1 or W.nnz >= 2 ** 31 - 1:
-                raise ValueError("graph too large for int32 CSR indices")
-            indptr, indices = indptr.astype(np.int32), indices.astype(np.int32)
+        N, data = W.shape[0], W.data
+        indptr, indices = _int32_csr(W)
         if data.dtype == np.float32:
             code = _capi.F32
         elif data.dtype == np.float64:
@@ -706,9 +758,8 @@ class DeviceGraph:
         report = np.zeros(12, dtype=np.int64)
         h = ctypes.c_void_p()
         ctx.call(_capi.load().gspx_graph_setup,
-            ctx._h, N, W.nnz, _capi.ptr(c(indptr)), _capi.ptr(c(indices)), _capi.ptr(c(data)), code,
-            _capi.LAP_COMBINATORIAL if lap_type == "combinatorial" else _capi.LAP_NORMALIZED, _capi.dtype_code(dtype),
-            _capi.ptr(xy), d, mode, _capi.ptr(perm_in), _capi.ptr(report), ctypes.byref(h))
+            ctx._h, N, W.nnz, _capi.ptr(c(indptr)), _capi.ptr(c(indices)), _capi.ptr(c(data)), code, lap,
+            _capi.dtype_code(dtype), _capi.ptr(xy), d, mode, _capi.ptr(perm_in), _capi.ptr(report), ctypes.byref(h))
         return (cls(h, ctx, N, dtype) if h.value else None), cls._setup_report(report)
 
     @classmethod
@@ -720,8 +771,7 @@ class DeviceGraph:
         else:
             mode = cls.ORDER_MODES[order]
         if mode in (1, 2, 3):
-            ok = coords is not None and np.ndim(coords) == 2 and np.shape(coords)[0] == N and np.shape(coords)[1] >= 2
-            if ok and N >= 4096:
+            if _curve_coords(coords, N) and N >= 4096:
                 xy = np.ascontiguousarray(coords, dtype=np.float64)
                 d = xy.shape[1]
             else:
@@ -739,15 +789,14 @@ class DeviceGraph:
     def setup_from(cls, adjacency, lap_type="combinatorial", dtype=np.float64, coords=None, order="auto"):
         """The same set-up for a DeviceAdjacency - the W a device builder (knn_graph / radius_graph / sbm_graph with
         keep_on_device=True) left on the device: nothing is downloaded or uploaded (gspx_graph_setup_from_knn)."""
-        if lap_type not in ("combinatorial", "normalized"):
-            raise ValueError("Unknown Laplacian type {}".format(lap_type))
+        lap = _lap_code(lap_type)
         N = adjacency.shape[0]
         mode, xy, d, perm_in = cls._order_args(N, coords, order)
         report = np.zeros(12, dtype=np.int64)
         h = ctypes.c_void_p()
         adjacency.ctx.call(_capi.load().gspx_graph_setup_from_knn,
-            adjacency._h, _capi.LAP_COMBINATORIAL if lap_type == "combinatorial" else _capi.LAP_NORMALIZED,
-            _capi.dtype_code(dtype), _capi.ptr(xy), d, mode, _capi.ptr(perm_in), _capi.ptr(report), ctypes.byref(h))
+            adjacency._h, lap, _capi.dtype_code(dtype), _capi.ptr(xy), d, mode, _capi.ptr(perm_in), _capi.ptr(report),
+            ctypes.byref(h))
         return (cls(h, adjacency.ctx, N, dtype) if h.value else None), cls._setup_report(report)
 
     def lmax_bounds(self):
@@ -852,7 +901,7 @@ class DeviceGraph:
         analysis:  x (N, Nsig)      -> (Nf, N, Nsig)
         synthesis: x (Nf, N, Nsig)  -> (N, Nsig)
         Returns (y, kernel_ms)."""
-        c = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        c = _coeff_matrix(coeffs)
         Nf, M = c.shape
         x = np.ascontiguousarray(x, dtype=self.dtype)
         if mode == _capi.ANALYSIS:
@@ -873,7 +922,7 @@ class DeviceGraph:
 
     def cheby_filter_dev(self, coeffs, x_ptr, y_ptr, nsig, lmax, mode=_capi.ANALYSIS):
         """Device pointers in / out (ints).  Returns device milliseconds of the whole call."""
-        c = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        c = _coeff_matrix(coeffs)
         Nf, M = c.shape
         ms = ctypes.c_double(0)
         self.ctx.call(_capi.load().gspx_cheby_filter_dev,
@@ -885,14 +934,13 @@ class DeviceGraph:
         """Squared column norms of the bank `coeffs` (Nf, M) applied to the device signals at x_ptr (N x nsig):
         ((Nf, nsig) float64 host array of ||p_f(L) x_j||^2, device milliseconds of the call), without the filtered
         outputs (gspx_cheby_sqnorms_dev)."""
-        c = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        c = _coeff_matrix(coeffs)
         Nf, M = c.shape
         out = np.zeros((Nf, int(nsig)))
         ms = ctypes.c_double(0)
         self.ctx.call(_capi.load().gspx_cheby_sqnorms_dev, self._h, float(lmax), Nf, M, _capi.ptr(c), int(nsig),
                       ctypes.c_void_p(x_ptr), _capi.ptr(out), ctypes.byref(ms))
         return out, ms.value
-
 
     def tune_placement(self, coeffs, x_ptr, y_ptr, nsig, lmax, candidates=6, stride_mb=0):
         """Draw `candidates` physical backings for the context's streamed workspaces and keep the one on which THIS call
@@ -916,47 +964,26 @@ class DeviceGraph:
                       ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), int(mode))
         return self.ctx.last_timing()
 
+    # ---- polynomial programs (Newton and product forms of one filter) -----------------------------
+    def _signals(self, x):
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        if x.ndim != 2 or x.shape[0] != self.N:
+            raise ValueError("input must be (N, Nsig), got {}".format(x.shape))
+        return x
 
-def _newton_methods():
     def newton_filter(self, nodes, dcoef, x, lmax):
         """Newton-form evaluation (single filter): host arrays in/out, x (N, Nsig) -> (N, Nsig)."""
         nodes = np.ascontiguousarray(nodes, dtype=np.float64)
         dcoef = np.ascontiguousarray(dcoef, dtype=np.float64)
         if dcoef.size != nodes.size + 1:
             raise ValueError("need K nodes and K+1 coefficients")
-        x = np.ascontiguousarray(x, dtype=self.dtype)
-        if x.ndim != 2 or x.shape[0] != self.N:
-            raise ValueError("input must be (N, Nsig), got {}".format(x.shape))
+        x = self._signals(x)
         y = np.empty_like(x)
         ms = ctypes.c_double(0)
         self.ctx.call(_capi.load().gspx_newton_filter,
             self._h, float(lmax), int(nodes.size), _capi.ptr(nodes), _capi.ptr(dcoef), x.shape[1],
             _capi.ptr(x), _capi.ptr(y), ctypes.byref(ms))
         return y, ms.value
-
-    def program_filter(self, program, x, lmax, old_is_x=False):
-        """A polynomial program (gspx_poly_program; filters.cheb_to_product builds the product form's): host arrays in /
-        out, x (N, Nsig) -> (N, Nsig).  program: (S, 3) rows of (scale, beta, gamma)."""
-        prog = np.ascontiguousarray(program, dtype=np.float64).reshape(-1, 3)
-        x = np.ascontiguousarray(x, dtype=self.dtype)
-        if x.ndim != 2 or x.shape[0] != self.N:
-            raise ValueError("input must be (N, Nsig), got {}".format(x.shape))
-        y = np.empty_like(x)
-        ms = ctypes.c_double(0)
-        cols = [np.ascontiguousarray(prog[:, k]) for k in range(3)]
-        self.ctx.call(_capi.load().gspx_poly_program, self._h, float(lmax), int(prog.shape[0]), _capi.ptr(cols[0]),
-                      _capi.ptr(cols[1]), _capi.ptr(cols[2]), int(bool(old_is_x)), x.shape[1], _capi.ptr(x), _capi.ptr(y),
-                      ctypes.byref(ms))
-        return y, ms.value
-
-    def program_filter_dev(self, program, x_ptr, y_ptr, nsig, lmax, old_is_x=False):
-        prog = np.ascontiguousarray(program, dtype=np.float64).reshape(-1, 3)
-        cols = [np.ascontiguousarray(prog[:, k]) for k in range(3)]
-        ms = ctypes.c_double(0)
-        self.ctx.call(_capi.load().gspx_poly_program_dev, self._h, float(lmax), int(prog.shape[0]), _capi.ptr(cols[0]),
-                      _capi.ptr(cols[1]), _capi.ptr(cols[2]), int(bool(old_is_x)), int(nsig), ctypes.c_void_p(x_ptr),
-                      ctypes.c_void_p(y_ptr), ctypes.byref(ms))
-        return ms.value
 
     def newton_filter_dev(self, nodes, dcoef, x_ptr, y_ptr, nsig, lmax):
         nodes = np.ascontiguousarray(nodes, dtype=np.float64)
@@ -967,6 +994,26 @@ def _newton_methods():
             ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), ctypes.byref(ms))
         return ms.value
 
+    def program_filter(self, program, x, lmax, old_is_x=False):
+        """A polynomial program (gspx_poly_program; filters.cheb_to_product builds the product form's): host arrays in /
+        out, x (N, Nsig) -> (N, Nsig).  program: (S, 3) rows of (scale, beta, gamma)."""
+        S, scale, beta, gamma = _program_columns(program)
+        x = self._signals(x)
+        y = np.empty_like(x)
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_poly_program, self._h, float(lmax), S, _capi.ptr(scale), _capi.ptr(beta),
+                      _capi.ptr(gamma), int(bool(old_is_x)), x.shape[1], _capi.ptr(x), _capi.ptr(y), ctypes.byref(ms))
+        return y, ms.value
+
+    def program_filter_dev(self, program, x_ptr, y_ptr, nsig, lmax, old_is_x=False):
+        S, scale, beta, gamma = _program_columns(program)
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_poly_program_dev, self._h, float(lmax), S, _capi.ptr(scale), _capi.ptr(beta),
+                      _capi.ptr(gamma), int(bool(old_is_x)), int(nsig), ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr),
+                      ctypes.byref(ms))
+        return ms.value
+
+    # ---- gather tiles (the LDS-staged recurrence step, k_step_tile) --------------------------------
     def download_internal(self):
         """(rowptr, col) of the engine's internal padded CSR (internal vertex order)."""
         rp = np.empty(self.N + 1, dtype=np.int32)
@@ -1007,33 +1054,17 @@ def _newton_methods():
         "enabled") or None when the graph is too small to bother."""
         if self.N < min_vertices:
             return None
-        st = build_gather_tiles(self)  # on the device: cheap enough to just try
+        st = self.build_gather_tiles()  # on the device: cheap enough to just try
         st["enabled"] = st["slow_blocks"] * 50 <= st["nb"]
         if not st["enabled"]:
-            disable_gather_tiles(self)
+            self.disable_gather_tiles()
         return st
 
     def disable_gather_tiles(self):
         _capi.check(_capi.load().gspx_graph_set_gather_tiles(self._h, 0, 0, None, None, None, None))
 
-    DeviceGraph.newton_filter = newton_filter
-    DeviceGraph.newton_filter_dev = newton_filter_dev
-    DeviceGraph.program_filter = program_filter
-    DeviceGraph.program_filter_dev = program_filter_dev
-    DeviceGraph.download_internal = download_internal
-    DeviceGraph.enable_gather_tiles = enable_gather_tiles
-    DeviceGraph.disable_gather_tiles = disable_gather_tiles
-    DeviceGraph.auto_gather_tiles = auto_gather_tiles
-    DeviceGraph.build_gather_tiles = build_gather_tiles
-
-
-_newton_methods()
-
-
-def _ops_methods():
-    """Operators that reuse the device CSR next to the Chebyshev path (include/gspx_ext.h, SURVEY 8(f)
-    row 3).  Host arrays in / out; the *_dev variants take device pointers."""
-
+    # ---- operators that reuse the device CSR (include/gspx_ext.h, SURVEY 8(f) row 3) ----------------
+    # Host arrays in / out; the *_dev variants take device pointers.
     def _panel(self, x, rows, what):
         x = np.asarray(x)
         one_d = x.ndim == 1
@@ -1041,6 +1072,15 @@ def _ops_methods():
         if x2.shape[0] != rows:
             raise ValueError("{}: first dimension must be {}, got {}".format(what, rows, x.shape))
         return x2, one_d
+
+    def _panel_op(self, x, rows_in, rows_out, fn, what):
+        """fn(x_ptr, y_ptr, nsig) on the uploaded panel x, (rows_in[, Nsig]) -> (rows_out[, Nsig])."""
+        x2, one_d = self._panel(x, rows_in, what)
+        with self.ctx._temporaries() as t:
+            bx, by = t.upload(x2), t.alloc(rows_out * x2.shape[1] * self.dtype.itemsize)
+            fn(bx.ptr, by.ptr, x2.shape[1])
+            y = by.download((rows_out, x2.shape[1]), self.dtype)
+        return y[:, 0] if one_d else y
 
     def laplacian_apply_dev(self, x_ptr, y_ptr, nsig):
         ms = ctypes.c_double(0)
@@ -1050,15 +1090,7 @@ def _ops_methods():
 
     def laplacian_apply(self, x):
         """L x for x of shape (N,) or (N, Nsig)."""
-        x2, one_d = _panel(self, x, self.N, "laplacian_apply")
-        bx, by = self.ctx.upload(x2), self.ctx.alloc(max(x2.nbytes, 16))
-        try:
-            laplacian_apply_dev(self, bx.ptr, by.ptr, x2.shape[1])
-            y = by.download(x2.shape, self.dtype)
-        finally:
-            bx.free()
-            by.free()
-        return y[:, 0] if one_d else y
+        return self._panel_op(x, self.N, self.N, self.laplacian_apply_dev, "laplacian_apply")
 
     def dirichlet_energy_dev(self, x_ptr, nsig):
         gram = np.zeros((int(nsig), int(nsig)), dtype=np.float64)
@@ -1070,14 +1102,24 @@ def _ops_methods():
     def dirichlet_energy(self, x):
         """x^T L x: a float for one signal, the (Nsig, Nsig) matrix x.T @ (L @ x) for a panel
         (what Graph.dirichlet_energy returns for 2-D input, graph.py:701-702)."""
-        x2, one_d = _panel(self, x, self.N, "dirichlet_energy")
-        bx = self.ctx.upload(x2)
-        try:
-            gram, _ = dirichlet_energy_dev(self, bx.ptr, x2.shape[1])
-        finally:
-            bx.free()
+        x2, one_d = self._panel(x, self.N, "dirichlet_energy")
+        with self.ctx._temporaries() as t:
+            gram, _ = self.dirichlet_energy_dev(t.upload(x2).ptr, x2.shape[1])
         return float(gram[0, 0]) if one_d else gram
 
+    def lanczos_basis(self, x, order, breakdown=0.0):
+        """The Krylov stacks of gspx_lanczos_krylov_dev for x (N,) or (N, n), n <= 256, on this float64 graph,
+        downloaded: (V (N, order[, n]) in the caller's vertex order, alpha (order[, n]), beta (order[, n]: row 0 is
+        ||x||, row k beta_k), steps (Krylov dimension per column; an int for 1-D x)).  A column stops at step k when
+        beta_k <= `breakdown`.  For tests at small N."""
+        from . import lanczos
+        x2, one_d = self._panel(x, self.N, "lanczos_basis")
+        V, alpha, beta, steps = lanczos.device_basis(self, x2, order, breakdown)
+        if one_d:
+            return V[:, :, 0], alpha[:, 0], beta[:, 0], int(steps[0])
+        return V, alpha, beta, steps
+
+    # ---- learning (Tikhonov regression and classification) ------------------------------------------
     def tikhonov_cg_dev(self, tau, mask_ptr, y_ptr, x_ptr, nsig, rtol=1e-5, atol=0.0, maxiter=None):
         maxiter = 10 * self.N if maxiter is None else int(maxiter)
         iters = np.zeros(max(int(nsig), 1), dtype=np.int32)
@@ -1090,19 +1132,14 @@ def _ops_methods():
     def tikhonov_cg(self, tau, mask, y, rtol=1e-5, atol=0.0, maxiter=None):
         """Solve (diag(mask) + tau L) x = mask * y per column by conjugate gradients (scipy's cg
         recurrence and stopping rule).  Returns (x, iterations per column, device ms)."""
-        y2, one_d = _panel(self, y, self.N, "tikhonov_cg")
+        y2, one_d = self._panel(y, self.N, "tikhonov_cg")
         m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=self.dtype)
         if m.size != self.N:
             raise ValueError("M should be of size [G.n_vertices,]")
-        bm, by = self.ctx.upload(m), self.ctx.upload(y2)
-        bx = self.ctx.alloc(max(y2.nbytes, 16))
-        try:
-            iters, ms = tikhonov_cg_dev(self, tau, bm.ptr, by.ptr, bx.ptr, y2.shape[1], rtol, atol, maxiter)
+        with self.ctx._temporaries() as t:
+            bm, by, bx = t.upload(m), t.upload(y2), t.alloc(y2.nbytes)
+            iters, ms = self.tikhonov_cg_dev(tau, bm.ptr, by.ptr, bx.ptr, y2.shape[1], rtol, atol, maxiter)
             x = bx.download(y2.shape, self.dtype)
-        finally:
-            bm.free()
-            by.free()
-            bx.free()
         return (x[:, 0] if one_d else x), iters, ms
 
     def tikhonov_simplex(self, tau, step, labels, n_classes, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
@@ -1120,42 +1157,25 @@ def _ops_methods():
         off = lambda v: -1.0 if v is None else float(v)
         obj = np.zeros(max(maxit, 0) + 1, dtype=np.float64)
         niter, crit, ms = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0)
-        bl = self.ctx.upload(lab)
-        bx = self.ctx.alloc(max(self.N * max(n_classes, 1) * 8, 16))
-        try:
+        with self.ctx._temporaries() as t:
+            bl, bx = t.upload(lab), t.alloc(self.N * max(n_classes, 1) * 8)
             self.ctx.call(_capi.load().gspx_tikhonov_simplex_dev,
                 self._h, float(tau), float(step), ctypes.c_void_p(bl.ptr), n_classes, off(rtol), off(atol), off(dtol),
                 off(xtol), maxit, ctypes.c_void_p(bx.ptr), ctypes.byref(niter), ctypes.byref(crit), _capi.ptr(obj),
                 ctypes.byref(ms))
             X = bx.download((self.N, n_classes), np.float64)
-        finally:
-            bl.free()
-            bx.free()
         crits = {1: "ATOL", 2: "DTOL", 3: "RTOL", 4: "XTOL", 5: "MAXIT"}
         info = {"niter": int(niter.value), "crit": crits.get(crit.value), "objective": obj[:niter.value + 1].copy(),
                 "ms": ms.value}
         return X, info
 
-    def lanczos_basis(self, x, order, breakdown=0.0):
-        """The Krylov stacks of gspx_lanczos_krylov_dev for x (N,) or (N, n), n <= 256, on this float64 graph,
-        downloaded: (V (N, order[, n]) in the caller's vertex order, alpha (order[, n]), beta (order[, n]: row 0 is
-        ||x||, row k beta_k), steps (Krylov dimension per column; an int for 1-D x)).  A column stops at step k when
-        beta_k <= `breakdown`.  For tests at small N."""
-        from . import lanczos
-        x2, one_d = _panel(self, x, self.N, "lanczos_basis")
-        V, alpha, beta, steps = lanczos.device_basis(self, x2, order, breakdown)
-        if one_d:
-            return V[:, :, 0], alpha[:, 0], beta[:, 0], int(steps[0])
-        return V, alpha, beta, steps
-
+    # ---- edges: the differential operator D, grad = D^T x, div = D y ---------------------------------
     def n_edges(self):
-        v = ctypes.c_int64(0)
-        _capi.check(_capi.load().gspx_graph_n_edges(self._h, ctypes.byref(v)))
-        return v.value
+        return self._i64(_capi.load().gspx_graph_n_edges)
 
     def edge_list(self, with_d=False):
         """(sources, targets, weights) in Graph.get_edge_list order; with_d adds D's two values per edge."""
-        E = n_edges(self)
+        E = self.n_edges()
         src, dst = np.empty(E, dtype=np.int32), np.empty(E, dtype=np.int32)
         w, ds, dt = (np.empty(E, dtype=self.dtype) for _ in range(3))
         _capi.check(_capi.load().gspx_graph_download_edges(
@@ -1164,7 +1184,7 @@ def _ops_methods():
 
     def differential_operator(self):
         """D as scipy csc (N x n_edges), assembled on the host from the device edge arrays."""
-        src, dst, _, ds, dt = edge_list(self, with_d=True)
+        src, dst, _, ds, dt = self.edge_list(with_d=True)
         E = src.size
         rows = np.concatenate([src, dst])
         cols = np.concatenate([np.arange(E), np.arange(E)])
@@ -1195,33 +1215,13 @@ def _ops_methods():
                                               ctypes.c_void_p(z_ptr), ctypes.byref(ms))
         return ms.value
 
-    def _edge_op(self, x, rows_in, rows_out, fn, what):
-        x2, one_d = _panel(self, x, rows_in, what)
-        out_bytes = rows_out * x2.shape[1] * np.dtype(self.dtype).itemsize
-        bx, by = self.ctx.upload(x2), self.ctx.alloc(max(out_bytes, 16))
-        try:
-            fn(self, bx.ptr, by.ptr, x2.shape[1])
-            y = by.download((rows_out, x2.shape[1]), self.dtype)
-        finally:
-            bx.free()
-            by.free()
-        return y[:, 0] if one_d else y
-
     def grad(self, x):
         """D^T x: (N,) or (N, Nsig) -> (n_edges,) or (n_edges, Nsig)."""
-        return _edge_op(self, x, self.N, n_edges(self), grad_dev, "grad")
+        return self._panel_op(x, self.N, self.n_edges(), self.grad_dev, "grad")
 
     def div(self, y):
         """D y: (n_edges,) or (n_edges, Nsig) -> (N,) or (N, Nsig)."""
-        return _edge_op(self, y, n_edges(self), self.N, div_dev, "div")
-
-    for f in (laplacian_apply_dev, laplacian_apply, dirichlet_energy_dev, dirichlet_energy,
-              tikhonov_cg_dev, tikhonov_cg, tikhonov_simplex, lanczos_basis, n_edges, edge_list, differential_operator, set_edge_list,
-              grad_dev, div_dev, grad, div):
-        setattr(DeviceGraph, f.__name__, f)
-
-
-_ops_methods()
+        return self._panel_op(y, self.n_edges(), self.N, self.div_dev, "div")
 
 
 METRICS = {"euclidean": 0, "manhattan": 1, "max_dist": 2}
@@ -1267,6 +1267,24 @@ class DeviceAdjacency:
             pass
 
 
+def _adjacency(h, ctx, N, keep_on_device, weights=np.float64, neighbors=None):
+    """The common end of the device builders: the gspx_knn handle `h` becomes a DeviceAdjacency (destroyed instead
+    when anything fails before that), downloaded unless it is to stay on the device.  neighbors: (NN, D) arrays to
+    fill with the k-NN query's result while the handle is there.  Returns (W, sigma, build_ms)."""
+    lib = _capi.load()
+    try:
+        nnz, sg, ms = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0)
+        _capi.check(lib.gspx_knn_info(h, ctypes.byref(nnz), ctypes.byref(sg), ctypes.byref(ms)))
+        if neighbors is not None:
+            _capi.check(lib.gspx_knn_download_neighbors(h, _capi.ptr(neighbors[0]), _capi.ptr(neighbors[1])))
+        W = DeviceAdjacency(h, ctx, N, nnz.value, weights)
+        h = None
+    finally:
+        if h:
+            lib.gspx_knn_destroy(h)
+    return (W if keep_on_device else W.download()), sg.value, ms.value
+
+
 def knn_graph(coords, k, sigma=None, ctx=None, neighbors=False, metric="euclidean", symmetrize="average",
               keep_on_device=False):
     """k-nearest-neighbour weights on the device (gspx_knn_build): the KD-tree query, Gaussian weights
@@ -1279,25 +1297,15 @@ def knn_graph(coords, k, sigma=None, ctx=None, neighbors=False, metric="euclidea
     if X.ndim != 2:
         raise ValueError("coords must be (N, d)")
     N, d = X.shape
-    lib = _capi.load()
     h = ctypes.c_void_p()
-    _capi.check(lib.gspx_knn_build(ctx._h, N, d, _capi.ptr(X), int(k), float(sigma or 0.0), METRICS[metric],
-                                   SYMMETRIZE[symmetrize], ctypes.byref(h)))
-    try:
-        nnz, sg, ms = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0)
-        _capi.check(lib.gspx_knn_info(h, ctypes.byref(nnz), ctypes.byref(sg), ctypes.byref(ms)))
-        info = {"build_ms": ms.value}
-        if neighbors:
-            NN = np.empty((N, int(k)), dtype=np.int32)
-            D = np.empty((N, int(k)), dtype=np.float64)
-            _capi.check(lib.gspx_knn_download_neighbors(h, _capi.ptr(NN), _capi.ptr(D)))
-            info["NN"], info["D"] = NN, D
-        W = DeviceAdjacency(h, ctx, N, nnz.value)
-        h = None
-    finally:
-        if h:
-            lib.gspx_knn_destroy(h)
-    return (W if keep_on_device else W.download()), sg.value, info
+    _capi.check(_capi.load().gspx_knn_build(ctx._h, N, d, _capi.ptr(X), int(k), float(sigma or 0.0), METRICS[metric],
+                                            SYMMETRIZE[symmetrize], ctypes.byref(h)))
+    nn = (np.empty((N, int(k)), dtype=np.int32), np.empty((N, int(k)), dtype=np.float64)) if neighbors else None
+    W, sg, ms = _adjacency(h, ctx, N, keep_on_device, neighbors=nn)
+    info = {"build_ms": ms}
+    if neighbors:
+        info["NN"], info["D"] = nn
+    return W, sg, info
 
 
 def radius_graph(coords, epsilon, sigma=None, ctx=None, metric="euclidean", keep_on_device=False):
@@ -1309,19 +1317,11 @@ def radius_graph(coords, epsilon, sigma=None, ctx=None, metric="euclidean", keep
     if X.ndim != 2:
         raise ValueError("coords must be (N, d)")
     N, d = X.shape
-    lib = _capi.load()
     h = ctypes.c_void_p()
-    _capi.check(lib.gspx_radius_build(ctx._h, N, d, _capi.ptr(X), float(epsilon), float(sigma or 0.0),
-                                      METRICS[metric], ctypes.byref(h)))
-    try:
-        nnz, sg, ms = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0)
-        _capi.check(lib.gspx_knn_info(h, ctypes.byref(nnz), ctypes.byref(sg), ctypes.byref(ms)))
-        W = DeviceAdjacency(h, ctx, N, nnz.value)
-        h = None
-    finally:
-        if h:
-            lib.gspx_knn_destroy(h)
-    return (W if keep_on_device else W.download()), sg.value, {"build_ms": ms.value}
+    _capi.check(_capi.load().gspx_radius_build(ctx._h, N, d, _capi.ptr(X), float(epsilon), float(sigma or 0.0),
+                                               METRICS[metric], ctypes.byref(h)))
+    W, sg, ms = _adjacency(h, ctx, N, keep_on_device)
+    return W, sg, {"build_ms": ms}
 
 
 def sbm_graph(z, M, seed=None, ctx=None, keep_on_device=False, directed=False, self_loops=False):
@@ -1341,26 +1341,18 @@ def sbm_graph(z, M, seed=None, ctx=None, keep_on_device=False, directed=False, s
     bounds = np.ascontiguousarray(np.searchsorted(z[order], np.arange(k + 1)), dtype=np.int64)
     if seed is None:
         seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-    lib = _capi.load()
     h = ctypes.c_void_p()
     flags = (1 if directed else 0) | (2 if self_loops else 0)
-    _capi.check(lib.gspx_sbm_build_ex(ctx._h, N, k, _capi.ptr(order), _capi.ptr(bounds), _capi.ptr(M),
-                                      ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), flags, ctypes.byref(h)))
-    try:
-        nnz, sg, ms = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0)
-        _capi.check(lib.gspx_knn_info(h, ctypes.byref(nnz), ctypes.byref(sg), ctypes.byref(ms)))
-        # (keep_on_device: unit int64 weights in the host copy, like the reference's W)
-        W = DeviceAdjacency(h, ctx, N, nnz.value, weights=np.int64 if keep_on_device else np.float64)
-        h = None
-    finally:
-        if h:
-            lib.gspx_knn_destroy(h)
-    return (W if keep_on_device else W.download()), ms.value
+    _capi.check(_capi.load().gspx_sbm_build_ex(ctx._h, N, k, _capi.ptr(order), _capi.ptr(bounds), _capi.ptr(M),
+                                               ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), flags, ctypes.byref(h)))
+    # (keep_on_device: unit int64 weights in the host copy, like the reference's W)
+    W, _, ms = _adjacency(h, ctx, N, keep_on_device, weights=np.int64 if keep_on_device else np.float64)
+    return W, ms
 
 
 def plan_describe(coeffs, ctx=None):
     """The engine's step schedule for these coefficients (host-only; for schedule tests)."""
-    c = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+    c = _coeff_matrix(coeffs)
     Nf, M = c.shape
     if M < 2:
         _capi.check(_capi.load().gspx_plan_describe(None, Nf, M, _capi.ptr(c), None))

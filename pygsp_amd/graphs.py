@@ -126,19 +126,7 @@ class Graph:
         if rep["zeros"]:  # graph.py:126-128: W keeps no edge of weight 0 (in place, like the reference; the device
             adjacency.eliminate_zeros()  # Laplacian was built without them)
         self._adjacency = adjacency
-        self.n_vertices = self.N = adjacency.shape[0]
-        # directed (W - W.T has a nonzero, counted on the device): the Laplacian was built from (W + W.T) / 2 in the
-        # same device call (graph.py:613-616); n_edges: stored entries, or unordered pairs + self-loops (graph.py:135-140)
-        directed = self._flags["directed"] = rep["asymmetric"] > 0
-        stored, loops = adjacency.nnz, rep["self_loops"]
-        self.n_edges = self.Ne = stored if directed else (stored - loops) // 2 + loops
-        self._perm_done, self._perm_lazy = True, dev if rep["reordered"] else None
-        self.setup_report = rep
-        if self.tiles == "auto":
-            self.tile_stats = dev.auto_gather_tiles()
-        elif self.tiles:
-            self.tile_stats = dev.enable_gather_tiles()
-        self._dev[self.compute_dtype] = dev
+        self._adopt_device_graph(dev, rep, adjacency)
         return True
 
     def _setup_from_device_adjacency(self, adjacency):
@@ -164,27 +152,39 @@ class Graph:
             self.logger.warning("Adjacency: there are self-loops (non-zeros on the diagonal). "
                                 "The Laplacian will not see them.")
         self._adj_dev = adjacency
+        self._adopt_device_graph(dev, rep, adjacency)
+        return True
+
+    def _adopt_device_graph(self, dev, rep, adjacency):
+        """What both device set-up routes leave behind: the sizes of `adjacency` (a scipy matrix or a DeviceAdjacency),
+        the facts of the set-up report, the device graph `dev` (with its gather tiles) as the one of the compute dtype."""
         self.n_vertices = self.N = adjacency.shape[0]
-        directed = self._flags["directed"] = rep["asymmetric"] > 0  # (a 'tril' / 'triu' neighbour graph, a directed block model)
+        # directed (W - W.T has a nonzero, counted on the device: also a 'tril' / 'triu' neighbour graph, a directed
+        # block model): the Laplacian was built from (W + W.T) / 2 in the same device call (graph.py:613-616);
+        # n_edges: stored entries, or unordered pairs + self-loops (graph.py:135-140)
+        directed = self._flags["directed"] = rep["asymmetric"] > 0
         stored, loops = adjacency.nnz, rep["self_loops"]
         self.n_edges = self.Ne = stored if directed else (stored - loops) // 2 + loops
         self._perm_done, self._perm_lazy = True, dev if rep["reordered"] else None
         self.setup_report = rep
+        self._apply_tiles(dev)
+        self._dev[self.compute_dtype] = dev
+
+    def _apply_tiles(self, dev):
+        """Gather tiles of the LDS-staged recurrence step on `dev`, as `tiles` asks: "auto" (when the order is local)
+        or a truth value."""
         if self.tiles == "auto":
             self.tile_stats = dev.auto_gather_tiles()
         elif self.tiles:
             self.tile_stats = dev.enable_gather_tiles()
-        self._dev[self.compute_dtype] = dev
-        return True
 
     def _curve_coords(self, n_vertices):
-        """The coordinates a space-filling curve can order (the test of engine.DeviceGraph._order_args: one row per
-        vertex, at least two columns), else None - a 1-D point cloud or a layout of another size then takes the
-        same route as a graph without coordinates (random-like: no order; otherwise reverse Cuthill-McKee on the
-        host) instead of silently keeping the graph's own order."""
+        """The coordinates a space-filling curve can order (engine._curve_coords: one row per vertex, at least two
+        columns), else None - a 1-D point cloud or a layout of another size then takes the same route as a graph
+        without coordinates (random-like: no order; otherwise reverse Cuthill-McKee on the host) instead of silently
+        keeping the graph's own order."""
         coords = getattr(self, "coords", None)
-        ok = coords is not None and np.ndim(coords) == 2 and np.shape(coords)[0] == n_vertices and np.shape(coords)[1] >= 2
-        return coords if ok else None
+        return coords if engine._curve_coords(coords, n_vertices) else None
 
     @property
     def _adjacency(self):
@@ -285,10 +285,7 @@ class Graph:
                     g = None
             if g is None:
                 g = engine.DeviceGraph.from_w(self._symmetric_w(), self.lap_type, dtype=dt, perm=perm, ctx=self.context)
-            if self.tiles == "auto":  # LDS tiles for the recurrence step, when the order is local
-                self.tile_stats = g.auto_gather_tiles()
-            elif self.tiles:
-                self.tile_stats = g.enable_gather_tiles()
+            self._apply_tiles(g)
             self._dev[dt] = g
         return g
 

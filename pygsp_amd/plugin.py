@@ -16,10 +16,12 @@ from . import engine, filters as _filters
 
 import threading
 
-# The originals of everything install() replaces are kept ON the patched object itself (attribute _gspx_saved of the
-# approximations module, of the Filter class, of the Graph class), so that two pygsp-shaped modules can be patched
-# and restored independently (one global table restored the first module's functions into the second).
+# The originals of everything install() replaces are kept ON the patched object itself (attribute _gspx_saved of
+# every module and class in _targets(): name -> the package's own attribute), so that two pygsp-shaped modules can be
+# patched and restored independently (one global table restored the first module's functions into the
+# second).
 _SAVED = "_gspx_saved"
+_MISSING = object()  # saved for a name the package does not have (an alias, lanczos_op): nothing to put back
 _installed = {}  # id(module) -> module, in installation order (uninstall() without an argument: the last one)
 _config = {"laplacian": "device", "dtype": np.float64, "device": 0, "reorder": "auto", "tiles": "auto",
            "devices": None, "evaluation": None}
@@ -27,12 +29,11 @@ _cache_lock = threading.RLock()
 
 
 def _finite_coords(G):
-    coords = getattr(G, "coords", None)
     try:
-        coords = np.asarray(coords, dtype=np.float64)
+        coords = np.asarray(getattr(G, "coords", None), dtype=np.float64)
     except (TypeError, ValueError):
         return None
-    if coords.ndim != 2 or coords.shape[0] != G.N or coords.shape[1] < 2 or not np.isfinite(coords).all():
+    if not engine._curve_coords(coords, G.N) or not np.isfinite(coords).all():
         return None  # plotting layouts may hold NaN / inf, a 1-D cloud has no curve: the pattern-based order
     return coords
 
@@ -139,7 +140,11 @@ def _saved_on(cls):
 
 def _reference_coefficients(bank, m):
     # the coefficients of the bank's own package (approximations.py:9-55): its own code, its own kernels
-    return _saved_on(type(bank))["approximations"].compute_cheby_coeff(bank, m=m)
+    for mod in list(_installed.values()):  # (the patched package whose wrapped Filter class the bank derives from)
+        filter_cls = getattr(mod.filters, "Filter", None)
+        if filter_cls in type(bank).__mro__ and _SAVED in vars(filter_cls):
+            return mod.filters.approximations.compute_cheby_coeff(bank, m=m)
+    raise RuntimeError("pygsp_amd.plugin: {} is not a patched class".format(type(bank).__name__))
 
 
 def _filter_on_device(self, s, method="chebyshev", order=30):
@@ -190,43 +195,6 @@ def _compute_fourier_basis_on_device(self, n_eigenvectors=None):
     return _saved_on(type(self))["compute_fourier_basis"](self, n_eigenvectors)
 
 
-def _patch_graph_class(graph_cls, lmax_device, fourier):
-    """Replace estimate_lmax (lmax='device') and compute_fourier_basis (fourier=True) on the reference's Graph class;
-    whatever was patched before and is not asked for now is restored."""
-    _restore(graph_cls, tuple(graph_cls.__dict__.get(_SAVED, ())))
-    wanted = {}
-    if lmax_device:
-        wanted["estimate_lmax"] = _estimate_lmax_on_device
-    if fourier:
-        wanted["compute_fourier_basis"] = _compute_fourier_basis_on_device
-    if wanted:
-        setattr(graph_cls, _SAVED, {n: getattr(graph_cls, n) for n in wanted})
-        for n, fn in wanted.items():
-            setattr(graph_cls, n, fn)
-
-
-_SAVED_LANCZOS = "_gspx_saved_lanczos"  # (on the approximations module: lanczos_op and its pygsp.filters alias)
-
-
-def _patch_lanczos(pygsp_module, wanted):
-    """Replace approximations.lanczos_op and the pygsp.filters.lanczos_op alias with filters.lanczos_op (wanted), or
-    put back the originals saved by an earlier install (not wanted)."""
-    approx = pygsp_module.filters.approximations
-    saved = approx.__dict__.get(_SAVED_LANCZOS)
-    if wanted:
-        if saved is None:
-            setattr(approx, _SAVED_LANCZOS, {"lanczos_op": getattr(approx, "lanczos_op", None),
-                                             "alias": getattr(pygsp_module.filters, "lanczos_op", None)})
-        approx.lanczos_op = _filters.lanczos_op
-        pygsp_module.filters.lanczos_op = _filters.lanczos_op
-    elif saved is not None:
-        for obj, key in ((approx, "lanczos_op"), (pygsp_module.filters, "alias")):
-            if saved[key] is not None:
-                setattr(obj, "lanczos_op", saved[key])
-        delattr(approx, _SAVED_LANCZOS)
-
-
-_SAVED_FEATURES = "_gspx_saved_features"  # (on the features module: compute_norm_tig, compute_spectrogram)
 _FEATURES = ("compute_norm_tig", "compute_spectrogram")
 
 
@@ -258,28 +226,6 @@ def _feature_functions(pygsp_module, saved):
     return {"compute_norm_tig": compute_norm_tig, "compute_spectrogram": compute_spectrogram}
 
 
-def _patch_features(pygsp_module, wanted):
-    """Replace features.compute_norm_tig and compute_spectrogram (wanted), or put back the originals saved by an
-    earlier install (not wanted).  Graph.plot_spectrogram looks compute_spectrogram up at call time and follows."""
-    feats = getattr(pygsp_module, "features", None)
-    if feats is None:
-        if wanted:
-            raise ValueError("features=True: {} has no features module".format(pygsp_module.__name__))
-        return
-    saved = feats.__dict__.get(_SAVED_FEATURES)
-    if wanted:
-        if saved is None:
-            saved = {n: getattr(feats, n) for n in _FEATURES}
-            setattr(feats, _SAVED_FEATURES, saved)
-        for n, fn in _feature_functions(pygsp_module, saved).items():
-            setattr(feats, n, fn)
-    elif saved is not None:
-        for n in _FEATURES:
-            setattr(feats, n, saved[n])
-        delattr(feats, _SAVED_FEATURES)
-
-
-_SAVED_LEARNING = "_gspx_saved_learning"  # (on the learning module: the two functions below)
 _LEARNING = ("classification_tikhonov_simplex", "regression_tikhonov")
 
 
@@ -306,27 +252,6 @@ def _learning_functions(saved):
     classification_tikhonov_simplex.__doc__ = learning.classification_tikhonov_simplex.__doc__
     return {"classification_tikhonov_simplex": classification_tikhonov_simplex,
             "regression_tikhonov": regression_tikhonov}
-
-
-def _patch_learning(pygsp_module, wanted):
-    """Replace learning.classification_tikhonov_simplex and regression_tikhonov (wanted), or put back the originals
-    saved by an earlier install (not wanted)."""
-    learn = getattr(pygsp_module, "learning", None)
-    if learn is None:
-        if wanted:
-            raise ValueError("learning=True: {} has no learning module".format(pygsp_module.__name__))
-        return
-    saved = learn.__dict__.get(_SAVED_LEARNING)
-    if wanted:
-        if saved is None:
-            saved = {n: getattr(learn, n) for n in _LEARNING}
-            setattr(learn, _SAVED_LEARNING, saved)
-        for n, fn in _learning_functions(saved).items():
-            setattr(learn, n, fn)
-    elif saved is not None:
-        for n in _LEARNING:
-            setattr(learn, n, saved[n])
-        delattr(learn, _SAVED_LEARNING)
 
 
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
@@ -371,40 +296,69 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         device = devices[0]
     _config.update(laplacian=laplacian, dtype=np.dtype(dtype), device=int(device), reorder=reorder,
                    tiles=tiles, devices=devices, evaluation=evaluation)
-    approx = pygsp_module.filters.approximations
-    if _SAVED not in approx.__dict__:
-        setattr(approx, _SAVED, {"cheby_op": approx.cheby_op, "alias": getattr(pygsp_module.filters, "cheby_op", None)})
+    on = _targets(pygsp_module)
     _installed.pop(id(pygsp_module), None)
     _installed[id(pygsp_module)] = pygsp_module
-    approx.cheby_op = _filters.cheby_op
-    pygsp_module.filters.cheby_op = _filters.cheby_op
-    filter_cls = getattr(pygsp_module.filters, "Filter", None)
-    can_wrap = filter_cls is not None and hasattr(approx, "compute_cheby_coeff")
-    if wrap_filter and can_wrap:
-        if _SAVED not in filter_cls.__dict__:
-            setattr(filter_cls, _SAVED, {"filter": filter_cls.filter, "compute_frame": filter_cls.compute_frame,
-                                         "approximations": approx})
-        filter_cls.filter, filter_cls.compute_frame = _filter_on_device, _compute_frame_on_device
-    elif filter_cls is not None:
-        _restore(filter_cls, ("filter", "compute_frame"))
-    graph_cls = getattr(getattr(pygsp_module, "graphs", None), "Graph", None)
-    if graph_cls is not None:
-        _patch_graph_class(graph_cls, lmax == "device", bool(fourier))
-    _patch_lanczos(pygsp_module, bool(lanczos))
-    _patch_features(pygsp_module, bool(features))
-    _patch_learning(pygsp_module, bool(learning))
+    ops = {"cheby_op": _filters.cheby_op}
+    if lanczos:
+        ops["lanczos_op"] = _filters.lanczos_op
+    _apply(on["approximations"], ops)
+    _apply(on["filters"], ops)  # (the aliases of pygsp/filters/__init__.py)
+    if on["Filter"] is not None:
+        wrap = wrap_filter and hasattr(on["approximations"], "compute_cheby_coeff")
+        _apply(on["Filter"], {"filter": _filter_on_device, "compute_frame": _compute_frame_on_device} if wrap else {})
+    if on["Graph"] is not None:
+        methods = {}
+        if lmax == "device":
+            methods["estimate_lmax"] = _estimate_lmax_on_device
+        if fourier:
+            methods["compute_fourier_basis"] = _compute_fourier_basis_on_device
+        _apply(on["Graph"], methods)
+    for name, asked, names, replacements in (
+            ("features", features, _FEATURES, lambda saved: _feature_functions(pygsp_module, saved)),
+            ("learning", learning, _LEARNING, _learning_functions)):
+        if on[name] is not None:
+            _apply(on[name], replacements(_originals(on[name], names)) if asked else {})
+        elif asked:
+            raise ValueError("{0}=True: {1} has no {0} module".format(name, pygsp_module.__name__))
     return pygsp_module
 
 
-def _restore(obj, names):
-    """Put back the originals saved on `obj` (a class or a module) and drop the table; no-op when there is none."""
-    saved = obj.__dict__.get(_SAVED)
-    if saved is None:
-        return None
-    for n in names:
-        setattr(obj, n, saved[n])
-    delattr(obj, _SAVED)
-    return saved
+def _targets(pygsp_module):
+    """The modules and classes of `pygsp_module` that install() patches, by role; None where the package has none."""
+    filters = pygsp_module.filters
+    return {"approximations": filters.approximations, "filters": filters, "Filter": getattr(filters, "Filter", None),
+            "Graph": getattr(getattr(pygsp_module, "graphs", None), "Graph", None),
+            "features": getattr(pygsp_module, "features", None), "learning": getattr(pygsp_module, "learning", None)}
+
+
+def _apply(obj, wanted):
+    """Make `obj` (a module or a class) carry exactly the replacements `wanted` (name -> replacement): names patched
+    before and not wanted now get their saved original back, the originals of newly patched names are saved in the
+    table on `obj`, and an empty table is dropped."""
+    saved = obj.__dict__.get(_SAVED, {})
+    for n in [n for n in saved if n not in wanted]:
+        original = saved.pop(n)
+        if original is not _MISSING:
+            setattr(obj, n, original)
+    for n, replacement in wanted.items():
+        saved.setdefault(n, getattr(obj, n, _MISSING))
+        setattr(obj, n, replacement)
+    if saved:
+        setattr(obj, _SAVED, saved)
+    elif _SAVED in obj.__dict__:
+        delattr(obj, _SAVED)
+
+
+def _restore(obj):
+    """Put back every original saved on `obj` and drop the table; no-op when there is none."""
+    _apply(obj, {})
+
+
+def _originals(obj, names):
+    """The package's own obj.name for each of `names`, whether or not it is patched at the moment."""
+    saved = obj.__dict__.get(_SAVED, {})
+    return {n: saved[n] if n in saved else getattr(obj, n) for n in names}
 
 
 def uninstall(pygsp_module=None):
@@ -421,21 +375,9 @@ def uninstall(pygsp_module=None):
     _installed.pop(id(pygsp_module), None)
     if not _installed:
         _config["evaluation"] = None
-    approx = pygsp_module.filters.approximations
-    _patch_lanczos(pygsp_module, False)
-    _patch_features(pygsp_module, False)
-    _patch_learning(pygsp_module, False)
-    saved = _restore(approx, ("cheby_op",))
-    if saved is None:
-        return
-    if saved["alias"] is not None:
-        pygsp_module.filters.cheby_op = saved["alias"]
-    filter_cls = getattr(pygsp_module.filters, "Filter", None)
-    if filter_cls is not None:
-        _restore(filter_cls, ("filter", "compute_frame"))
-    graph_cls = getattr(getattr(pygsp_module, "graphs", None), "Graph", None)
-    if graph_cls is not None:
-        _restore(graph_cls, tuple(graph_cls.__dict__.get(_SAVED, ())))
+    for obj in _targets(pygsp_module).values():
+        if obj is not None:
+            _restore(obj)
 
 
 def use_backend(name, pygsp_module=None, **install_options):

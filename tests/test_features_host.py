@@ -178,7 +178,7 @@ def test_plugin_features_seam_is_opt_in():
     finally:
         plugin.uninstall(mod)
     assert (feats.compute_tig, feats.compute_norm_tig, feats.compute_spectrogram) == own
-    assert not hasattr(feats, plugin._SAVED_FEATURES)
+    assert not hasattr(feats, plugin._SAVED)
     bare = _standin(with_features=False)
     with pytest.raises(ValueError):
         plugin.install(bare, features=True)

@@ -471,6 +471,123 @@ def test_install_wraps_and_restores_the_filter_methods():
         plugin._config.update(dtype=np.dtype(np.float64))
 
 
+def test_install_flags_patch_and_restore_every_seam_through_one_table():
+    """plugin.install() on a pygsp-shaped module with every seam (no device needed: nothing is called): each optional
+    seam - lanczos_op, features, learning, compute_fourier_basis, estimate_lmax - follows its flag from one install to
+    the next while cheby_op and Filter.filter stay patched, and uninstall() after any sequence of installs leaves every
+    touched object with the package's own attributes and without a save table."""
+    import itertools
+    import types
+
+    from pygsp_amd import plugin
+
+    def make(with_lanczos=True):
+        mod = types.ModuleType("pygsp")
+        mod.filters = types.ModuleType("pygsp.filters")
+        approx = mod.filters.approximations = types.ModuleType("pygsp.filters.approximations")
+        approx.cheby_op = mod.filters.cheby_op = lambda G, c, s, **kw: "reference"
+        approx.compute_cheby_coeff = lambda f, m=30: np.ones(m + 1)
+        if with_lanczos:
+            approx.lanczos_op = mod.filters.lanczos_op = lambda f, s, order=30: "reference lanczos"
+
+        class Filter:
+            def filter(self, s, method="chebyshev", order=30):
+                return "own filter"
+
+            def compute_frame(self, **kwargs):
+                return "own frame"
+
+        class Graph:
+            def estimate_lmax(self, method="lanczos"):
+                return "own lmax"
+
+            def compute_fourier_basis(self, n_eigenvectors=None):
+                return "own basis"
+
+        mod.filters.Filter = Filter
+        mod.graphs = types.ModuleType("pygsp.graphs")
+        mod.graphs.Graph = Graph
+        mod.features = types.ModuleType("pygsp.features")
+        mod.features.compute_tig = lambda g, **k: "own tig"
+        mod.features.compute_norm_tig = lambda g, **k: "own norm tig"
+        mod.features.compute_spectrogram = lambda G, atom=None, M=100, **k: "own spectrogram"
+        mod.learning = types.ModuleType("pygsp.learning")
+        mod.learning.regression_tikhonov = lambda G, y, M, tau=0: "own regression"
+        mod.learning.classification_tikhonov_simplex = lambda G, y, M, tau=0.1, **k: "own simplex"
+        mod.learning.classification_tikhonov = lambda G, y, M, tau=0: "own classification"
+        return mod
+
+    def touched(mod):
+        return (mod.filters.approximations, mod.filters, mod.filters.Filter, mod.graphs.Graph, mod.features,
+                mod.learning)
+
+    def attributes(mod):
+        return {(i, n): v for i, obj in enumerate(touched(mod)) for n, v in vars(obj).items() if callable(v)}
+
+    def assert_untouched(mod, own):
+        now = attributes(mod)
+        assert now.keys() == own.keys()
+        for key in own:
+            assert now[key] is own[key], key
+        for obj in touched(mod):
+            assert plugin._SAVED not in vars(obj), obj
+
+    mod = make()
+    own = attributes(mod)
+    approx, Graph, feats, learn = mod.filters.approximations, mod.graphs.Graph, mod.features, mod.learning
+    optional = ((approx, "lanczos_op"), (mod.filters, "lanczos_op"), (feats, "compute_norm_tig"),
+                (feats, "compute_spectrogram"), (learn, "regression_tikhonov"),
+                (learn, "classification_tikhonov_simplex"), (Graph, "compute_fourier_basis"), (Graph, "estimate_lmax"))
+    try:
+        plugin.install(mod, lanczos=True, features=True, learning=True, fourier=True, lmax="device")
+        assert approx.lanczos_op is filters.lanczos_op and mod.filters.lanczos_op is filters.lanczos_op
+        assert Graph.compute_fourier_basis is plugin._compute_fourier_basis_on_device
+        assert Graph.estimate_lmax is plugin._estimate_lmax_on_device
+        for obj, name in optional:
+            assert getattr(obj, name) is not own[touched(mod).index(obj), name], name
+        plugin.install(mod)  # the defaults: each of the five goes back to the package's own object ...
+        for obj, name in optional:
+            assert getattr(obj, name) is own[touched(mod).index(obj), name], name
+        for obj in (Graph, feats, learn):
+            assert plugin._SAVED not in vars(obj)
+        # ... while the primary and the secondary seam stay
+        assert approx.cheby_op is filters.cheby_op and mod.filters.cheby_op is filters.cheby_op
+        assert mod.filters.Filter.filter is plugin._filter_on_device
+        assert mod.filters.Filter.compute_frame is plugin._compute_frame_on_device
+        assert mod.filters.Filter().filter(None, method="exact") == "own filter"
+        plugin.uninstall(mod)
+        assert_untouched(mod, own)
+        # any sequence of installs, then one uninstall
+        flag_sets = [dict(lanczos=a, features=b, learning=c, fourier=d, lmax=e, wrap_filter=f)
+                     for a, b, c, d, e, f in itertools.product((False, True), (False, True), (False, True),
+                                                               (False, True), ("reference", "device"), (True, False))]
+        for first, second in ((0, 63), (63, 0), (21, 42), (42, 21), (63, 63), (5, 58), (36, 27)):
+            plugin.install(mod, **flag_sets[first])
+            plugin.install(mod, **flag_sets[second])
+            plugin.uninstall(mod)
+            assert_untouched(mod, own)
+        for flags in flag_sets:
+            plugin.install(mod, **flags)
+        plugin.uninstall(mod)
+        assert_untouched(mod, own)
+        plugin.uninstall(mod)  # nothing left to restore: a no-op
+        assert_untouched(mod, own)
+        # a package without lanczos_op: there is no original to put back, and no table stays behind either
+        bare = make(with_lanczos=False)
+        own_bare = attributes(bare)
+        plugin.install(bare, lanczos=True)
+        assert bare.filters.approximations.lanczos_op is filters.lanczos_op
+        plugin.install(bare)
+        plugin.uninstall(bare)
+        for obj in touched(bare):
+            assert plugin._SAVED not in vars(obj)
+        now = attributes(bare)
+        for key in own_bare:
+            assert now[key] is own_bare[key], key
+    finally:
+        plugin.uninstall(mod)
+
+
 def test_device_array_pool_is_locked_and_gives_way_to_allocations():
     """the recycled-buffer pool of a Context (take / give) is mutated from DeviceArray.__del__ and from
     user threads - one lock - and must never be the reason an allocation fails: Context.call() empties it and runs a
@@ -526,7 +643,7 @@ def test_device_array_pool_is_locked_and_gives_way_to_allocations():
     ctx.clear_pool()
     # many threads giving and taking: the byte count stays exact
     def take_or_new(n):  # Context.take without the device allocation behind it
-        with ctx._pool_state():
+        with ctx._pool_lock:
             stack = ctx._pool.get(n)
             if stack:
                 ctx._pooled -= n
@@ -547,7 +664,7 @@ def test_device_array_pool_is_locked_and_gives_way_to_allocations():
         t.start()
     for t in ts:
         t.join()
-    with ctx._pool_state():
+    with ctx._pool_lock:
         assert ctx._pooled == 16 * sum(len(v) for v in ctx._pool.values())
     ctx.clear_pool()
     assert ctx.pooled_bytes() == 0

@@ -237,7 +237,7 @@ def test_plugin_seam_on_a_standin(golden, monkeypatch):
     finally:
         plugin.uninstall(mod)
     assert (mod.learning.regression_tikhonov, mod.learning.classification_tikhonov_simplex) == originals
-    assert "_gspx_saved_learning" not in mod.learning.__dict__
+    assert plugin._SAVED not in mod.learning.__dict__
 
 
 def test_entry_point_refuses_bad_arguments_without_a_device():

@@ -55,6 +55,7 @@ typedef struct gspx_buf gspx_buf;
 #define GSPX_ERR_HIP 3     /* HIP runtime failure                   -> RuntimeError*/
 #define GSPX_ERR_NODEVICE 4
 #define GSPX_ERR_OOM 5     /* device allocation failed, nothing written yet -> RuntimeError (safe to retry) */
+#define GSPX_ERR_INTERNAL 6 /* an invariant of the library itself did not hold    -> RuntimeError */
 
 const char* gspx_last_error(void);
 const char* gspx_version(void);

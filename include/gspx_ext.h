@@ -244,6 +244,22 @@ int gspx_graph_lmax_bounds(gspx_graph* g, double out[4]);
 /* the internal vertex order of a graph (perm[new] = old); GSPX_ERR_INVALID when it has none */
 int gspx_graph_download_perm(gspx_graph* g, int32_t* perm);
 
+/* Connected components of the graph's undirected pattern - the off-diagonal stored entries of its Laplacian, read in
+ * both directions - labelled on the device (Graph.is_connected / extract_components, graph.py:294-366, 444-508;
+ * scipy.sparse.csgraph.connected_components(W, directed=False)).  labels_dev: N int32 (DEVICE, caller's vertex order)
+ * or NULL when only the count is wanted; vertex v gets the number 0 .. *n_components - 1 of its component,
+ * components numbered by their smallest vertex (scipy's numbering).  Isolated vertices are components of their own,
+ * self-loops never matter, N = 0 gives 0 components; fp32 and fp64 graphs, every vertex order.  The pattern is the
+ * Laplacian's: a normalized Laplacian of a graph with negative weights has lost the rows of vertices whose weights
+ * cancel (graph.py:621-628), the caller labels such a W itself.  Hook-to-the-smaller-label rounds with pointer
+ * shortening; *rounds (nullable): how many ran, at most the cap gspx_components_round_cap(N) = 2 ceil(log2 N) + 1
+ * (derived in gspx_components.hip.h) - labels that still change then are GSPX_ERR_INTERNAL, never a longer loop.
+ * kernel_ms (nullable): device time of the whole call.  gspx_graph_components: the same with a HOST labels array. */
+int gspx_graph_components_dev(gspx_graph* g, int32_t* labels_dev, int64_t* n_components, int* rounds,
+                              double* kernel_ms);
+int gspx_graph_components(gspx_graph* g, int32_t* labels_host, int64_t* n_components, int* rounds, double* kernel_ms);
+int gspx_components_round_cap(int64_t N, int* cap);
+
 /* Columns [j0, j0 + w) of the N x N identity as a row-major N x w panel in device memory (dtype GSPX_F32 /
  * GSPX_F64), queued on the context's stream: the input of Filter.compute_frame (filter.py:593-600 filters
  * np.identity(N)) produced where it is consumed. */

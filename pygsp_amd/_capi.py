@@ -17,7 +17,7 @@ F32, F64 = 0, 1
 LAP_COMBINATORIAL, LAP_NORMALIZED = 0, 1
 ANALYSIS, SYNTHESIS = 0, 1
 
-OK, ERR_INVALID, ERR_COEFF, ERR_HIP, ERR_NODEVICE, ERR_OOM = 0, 1, 2, 3, 4, 5
+OK, ERR_INVALID, ERR_COEFF, ERR_HIP, ERR_NODEVICE, ERR_OOM, ERR_INTERNAL = 0, 1, 2, 3, 4, 5, 6
 
 _lib = None
 
@@ -114,6 +114,12 @@ SIGNATURES = {
     "gspx_graph_setup_from_knn": (_c.c_int, [_P, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _P, _P, _c.POINTER(_P)]),
     "gspx_graph_download_perm": (_c.c_int, [_P, _P]),
     "gspx_graph_lmax_bounds": (_c.c_int, [_P, _P]),
+    # connected components (Graph.connected_components / is_connected / extract_components)
+    "gspx_graph_components_dev": (_c.c_int, [_P, _P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int),
+                                             _c.POINTER(_c.c_double)]),
+    "gspx_graph_components": (_c.c_int, [_P, _P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int),
+                                         _c.POINTER(_c.c_double)]),
+    "gspx_components_round_cap": (_c.c_int, [_c.c_int64, _c.POINTER(_c.c_int)]),
     "gspx_sbm_build": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_uint64, _P]),
     "gspx_sbm_build_ex": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_uint64, _c.c_int, _P]),
     "gspx_radius_build": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_double, _c.c_double, _c.c_int, _P]),

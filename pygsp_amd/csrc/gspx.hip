@@ -3271,6 +3271,7 @@ extern "C" int gspx_ctx_tune_placement(gspx_graph* g, double lmax, int M, const 
 #include "gspx_ops.hip.h"
 #include "gspx_knn.hip.h"
 #include "gspx_setup.hip.h"
+#include "gspx_components.hip.h"
 #include "gspx_spectral.hip.h"
 #include "gspx_lanczos.hip.h"
 #include "gspx_learning.hip.h"

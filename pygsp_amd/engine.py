@@ -809,6 +809,20 @@ class DeviceGraph:
             return None
         return out
 
+    def components(self, labels=True):
+        """Connected components of the graph's undirected pattern, labelled on the device (gspx_graph_components):
+        (n, labels or None, report).  labels: int32, one per vertex in the caller's order, components numbered
+        0 .. n - 1 by their smallest vertex - the numbering of scipy's connected_components(W, directed=False);
+        labels=False asks for the count alone and moves nothing but it.  report: {'rounds' (hook rounds run),
+        'round_cap' (the library's own bound for this N, never exceeded), 'kernel_ms' (device time)}."""
+        lib = _capi.load()
+        n, rounds, cap, ms = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
+        out = np.empty(self.N, dtype=np.int32) if labels else None
+        self.ctx.call(lib.gspx_graph_components, self._h, _capi.ptr(out), ctypes.byref(n), ctypes.byref(rounds),
+                      ctypes.byref(ms))
+        _capi.check(lib.gspx_components_round_cap(self.N, ctypes.byref(cap)))
+        return int(n.value), out, {"rounds": rounds.value, "round_cap": cap.value, "kernel_ms": ms.value}
+
     def download_perm(self):
         """The internal vertex order (perm[new] = old), or None when the graph keeps its own order."""
         perm = np.empty(self.N, dtype=np.int32)

@@ -9,8 +9,11 @@ Mirrors (same names, argument meaning and exceptions) the parts of
 * ``Graph.lmax / estimate_lmax``  graph.py:840-960  (host, scipy: a read-only input of the path)
 * ``Graph._check_signal``         graph.py:632-640
 * ``Graph.is_directed``           graph.py:357-405
+* ``Graph.is_connected``          graph.py:294-366  -> component labels ON DEVICE (gspx_graph_components)
+* ``Graph.extract_components``    graph.py:444-508  -> the same labels, one ``subgraph`` per component
+* ``Graph.subgraph / is_weighted / has_loops``      graph.py:218-292, 407-442
 
-Everything else of the reference's Graph (plotting, I/O, subgraphs, ...) is out of scope; use
+Everything else of the reference's Graph (plotting, I/O, ...) is out of scope; use
 the real pygsp together with ``pygsp_amd.plugin.install()`` for those.
 
 The synthetic generators at the bottom (Sensor, ErdosRenyi, StochasticBlockModel) are vectorised
@@ -218,19 +221,100 @@ class Graph:
     def _directed(self):
         return self._flags.get("directed")
 
+    def is_weighted(self):
+        """graph.py:257-292: some stored weight differs from one."""
+        return not np.all(self.W.data == 1)
+
+    def has_loops(self):
+        """graph.py:407-442: some diagonal entry of W is not zero."""
+        return bool(np.any(self.W.diagonal() != 0))
+
+    def _labels_need_w(self):
+        """True when the device Laplacian's pattern is not W's: with the normalized Laplacian and negative weights, a
+        vertex whose weights cancel (dw == 0) has lost its row of L (graph.py:621-628) while W still connects it."""
+        if self.lap_type != "normalized":
+            return False
+        report = getattr(self, "setup_report", None)
+        if report is not None:
+            return report["negative"] > 0
+        return bool(self.W.nnz and self.W.data.min() < 0)
+
+    def connected_components(self):
+        """(n_components, labels): labels is an int32 array with the component 0 .. n - 1 of every vertex, components
+        numbered by their smallest vertex; computed once.  An undirected graph is labelled on the device, on the
+        pattern of its device Laplacian (engine.DeviceGraph.components): W is not read, a W that lies on the device
+        stays there.  Two cases take the host route, scipy's csgraph on W: a normalized Laplacian with negative
+        weights (its pattern may have lost edges of W), and a directed graph, whose labels are its STRONGLY
+        connected components in scipy's numbering - the device Laplacian of a directed graph is built from
+        (W + W.T) / 2, the direction is gone; labelling directed graphs on the device is out of scope."""
+        if "components" not in self._flags:
+            if self.n_vertices == 0:
+                n, labels = 0, np.empty(0, dtype=np.int32)
+            elif self.is_directed() or self._labels_need_w():
+                from scipy.sparse import csgraph
+                n, labels = csgraph.connected_components(self.W, directed=self.is_directed(), connection="strong",
+                                                         return_labels=True)
+            else:
+                n, labels, self.components_report = self.device_graph().components()
+            self._flags["components"] = (int(n), np.asarray(labels, dtype=np.int32))
+            self._flags["connected"] = n <= 1
+        return self._flags["components"]
+
     def is_connected(self):
         """graph.py:303-355: every vertex reachable from every other one - for a directed graph along the
-        edges AND against them (strongly connected).  Connected components of W on the host (scipy's csgraph),
-        computed once."""
+        edges AND against them (strongly connected).  An undirected graph is answered by the device's component
+        count (nothing but the count comes back, W is not read); a directed one by scipy's csgraph on W.  Computed
+        once."""
         if "connected" not in self._flags:
-            from scipy.sparse import csgraph
             if self.n_vertices == 0:
                 self._flags["connected"] = True
-            else:
+            elif self.is_directed() or self._labels_need_w():
+                from scipy.sparse import csgraph
                 n, _ = csgraph.connected_components(self.W, directed=self.is_directed(), connection="strong",
                                                     return_labels=True)
                 self._flags["connected"] = bool(n == 1)
+            else:
+                n, _, self.components_report = self.device_graph().components(labels=False)
+                self._flags["connected"] = n == 1
         return self._flags["connected"]
+
+    def subgraph(self, vertices):
+        """graph.py:218-255: the graph induced by `vertices` (a list of indices, in the order given, or a boolean
+        indicator): adjacency W[vertices, :][:, vertices] (sliced on the host, O(nnz)), coords[vertices] if there are
+        coordinates, the same lap_type and plotting, the signals sliced.  The child is set up on the device like any
+        graph, with this graph's engine settings (compute dtype, device / context, reorder mode, tiles)."""
+        vertices = np.asarray(vertices)
+        if vertices.size == 0:
+            vertices = vertices.astype(np.int64)
+        adjacency = sparse.csr_matrix(self.W[vertices, :][:, vertices])
+        adjacency.sort_indices()
+        coords = getattr(self, "coords", None)
+        # (an explicit permutation is one of this graph's vertices: the child chooses its own order)
+        reorder = self.reorder if isinstance(self.reorder, str) or self.reorder in (None, False) else "auto"
+        child = Graph(adjacency, self.lap_type, None if coords is None else coords[vertices], self.plotting,
+                      compute_dtype=self.compute_dtype, device=self.device, reorder=reorder, tiles=self.tiles,
+                      ctx=self._ctx)
+        for name, signal in self.signals.items():
+            child.signals[name] = child._check_signal(np.asanyarray(signal)[vertices])
+        return child
+
+    def extract_components(self):
+        """graph.py:444-508: one ``subgraph`` per connected component, in order of smallest vertex, each with
+        ``info = {'orig_idx': <its vertices, sorted>}``.  The vertex lists come from the device labels by one
+        stable sort.  Directed graphs raise NotImplementedError, as in the reference."""
+        if self.is_directed():
+            raise NotImplementedError("Directed graphs not supported yet.")
+        n, labels = self.connected_components()
+        by_label = np.argsort(labels, kind="stable")
+        starts = np.searchsorted(labels[by_label], np.arange(n + 1))
+        parts = []
+        for c in range(n):
+            members = by_label[starts[c]:starts[c + 1]]
+            self.logger.info("Constructing subgraph for component of size {}.".format(members.size))
+            part = self.subgraph(members)
+            part.info = {"orig_idx": members.tolist()}
+            parts.append(part)
+        return parts
 
     def _symmetric_w(self):
         """W itself if undirected, else (W + W.T)/2 (utils.symmetrize 'average', graph.py:613-616)."""
@@ -796,7 +880,7 @@ class StochasticBlockModel(Graph):
                 break
             trial = Graph(W, reorder="none", tiles=False, ctx=ctx)
             if trial.is_connected():
-                W = trial.W  # (the host copy the connectivity test made: the device handle went with it)
+                W = trial.W  # (downloaded now, for the one trial that is kept: the device handle goes with it)
                 break
             if tries is not None:
                 tries -= 1

@@ -254,9 +254,50 @@ def _learning_functions(saved):
             "regression_tikhonov": regression_tikhonov}
 
 
+_TOPOLOGY = ("is_connected", "extract_components")
+
+
+def _labels_on_device(G):
+    """Whether the device labels G: an undirected graph with vertices whose device Laplacian has W's pattern (a
+    normalized Laplacian with negative weights may have lost edges of W, graph.py:621-628)."""
+    if G.N == 0 or G.is_directed():
+        return False
+    return not (G.lap_type == "normalized" and G.W.nnz and G.W.data.min() < 0)
+
+
+def _is_connected_on_device(self):
+    """``Graph.is_connected`` of the reference (graph.py:294-366: a Python depth-first search that slices one sparse
+    row per vertex) answered by the device's component count (gspx_graph_components) for undirected graphs; cached
+    in the reference's own ``_connected``.  Directed graphs run the reference's code."""
+    if not _labels_on_device(self):
+        return _saved_on(type(self))["is_connected"](self)
+    if self._connected is None:
+        self._connected = device_graph_for(self).components(labels=False)[0] == 1
+    return self._connected
+
+
+def _extract_components_on_device(self):
+    """``Graph.extract_components`` of the reference (graph.py:444-508) with the vertex lists taken from the device
+    labels (one stable sort); the children are built by the reference's own ``subgraph``, so they are graphs of
+    the patched package, in order of smallest vertex, with ``info = {'orig_idx': ...}``.  Directed graphs run the
+    reference's code (NotImplementedError there)."""
+    if not _labels_on_device(self):
+        return _saved_on(type(self))["extract_components"](self)
+    n, labels, _ = device_graph_for(self).components()
+    by_label = np.argsort(labels, kind="stable")
+    starts = np.searchsorted(labels[by_label], np.arange(n + 1))
+    parts = []
+    for c in range(n):
+        members = by_label[starts[c]:starts[c + 1]].tolist()
+        part = self.subgraph(members)
+        part.info = {"orig_idx": members}
+        parts.append(part)
+    return parts
+
+
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
-            lanczos=False, features=False, learning=False):
+            lanczos=False, features=False, learning=False, topology=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -280,7 +321,9 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     ``compute_tig`` already reaches the device through the wrapped ``Filter.compute_frame``.
     `learning` (default False): also replace ``pygsp.learning.classification_tikhonov_simplex`` (on the device, without
     pyunlocbox) and ``regression_tikhonov`` (tau > 0 with a sparse L: the device conjugate gradients; otherwise the
-    original); ``classification_tikhonov`` looks ``regression_tikhonov`` up at call time and follows."""
+    original); ``classification_tikhonov`` looks ``regression_tikhonov`` up at call time and follows.
+    `topology` (default False): also replace ``Graph.is_connected`` and ``Graph.extract_components`` so that undirected
+    graphs are labelled on the device (gspx_graph_components); directed graphs keep the reference's code."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -307,12 +350,16 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     if on["Filter"] is not None:
         wrap = wrap_filter and hasattr(on["approximations"], "compute_cheby_coeff")
         _apply(on["Filter"], {"filter": _filter_on_device, "compute_frame": _compute_frame_on_device} if wrap else {})
+    if topology and on["Graph"] is None:
+        raise ValueError("topology=True: {} has no graphs.Graph".format(pygsp_module.__name__))
     if on["Graph"] is not None:
         methods = {}
         if lmax == "device":
             methods["estimate_lmax"] = _estimate_lmax_on_device
         if fourier:
             methods["compute_fourier_basis"] = _compute_fourier_basis_on_device
+        if topology:
+            methods.update(zip(_TOPOLOGY, (_is_connected_on_device, _extract_components_on_device)))
         _apply(on["Graph"], methods)
     for name, asked, names, replacements in (
             ("features", features, _FEATURES, lambda saved: _feature_functions(pygsp_module, saved)),

@@ -413,7 +413,7 @@ struct gspx_ctx {
   DevMem ws_r;      // accumulators
   DevMem ws_w;      // per-step flush weights / combine coefficients
   DevMem io_x, io_y;  // staging for the host-pointer entry point
-  DevMem ws_spec;     // small matrices and reduction partials of the panel primitives (gspx_spectral.hip.h)
+  DevMem ws_spec;     // small matrices and Gram partials of the panel primitives (gspx_spectral.hip.h, gspx_reduce.hip.h)
   DevMem ws_sq, ws_sqp;  // column norms: coefficients and norms | workgroup partials (gspx_cheby_sqnorms_dev)
   HostPipe* pipe = nullptr;  // its pipelined form (created on first use)
   CopyStage* copy = nullptr; // staged transfers of large buffers (created on first use)
@@ -445,6 +445,17 @@ static void replay_reset(gspx_ctx* ctx) {
     (void)hipGraphExecDestroy(ctx->graph_exec);
     ctx->graph_exec = nullptr;
   }
+}
+
+// end of a timed entry point: kernel_ms = the time between ctx->ev[0] and ctx->ev[1], which the caller has recorded
+// on ctx->stream - where it records them (around its small host copies or inside them) is what its kernel_ms means
+static int finish_timed(gspx_ctx* ctx, double* kernel_ms) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float f = 0;
+  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
+  if (kernel_ms) *kernel_ms = f;
+  return GSPX_OK;
 }
 
 struct gspx_buf {

@@ -144,13 +144,9 @@ extern "C" int gspx_graph_components_dev(gspx_graph* g, int32_t* labels_dev, int
   int count = 0;
   HIPCHK(hipMemcpyAsync(&count, par.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  CHK(finish_timed(ctx, kernel_ms));
   *n_components = count;
   if (rounds) *rounds = done;
-  if (kernel_ms) *kernel_ms = ms;
   return GSPX_OK;
 }
 

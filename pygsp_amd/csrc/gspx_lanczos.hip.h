@@ -15,15 +15,14 @@
 // that is the reference's three-term step followed by ONE classical Gram-Schmidt pass against q_0..q_k (DESIGN.md,
 // "Lanczos filtering": why one pass is enough after the three-term subtraction).  alpha, beta, the dots and the
 // per-column active flags stay on the device: the loop does not synchronise with the host until it ends.
-// Every reduction is per workgroup into partials, then a fixed-order second pass (k_colsum / k_panel_sum_parts):
-// no atomics, the same bits on every call.  Included at the end of gspx.hip (after gspx_spectral.hip.h).
+// Every reduction is per workgroup into partials (block_colsum), then a fixed-order second pass (sum_parts), both
+// from gspx_reduce.hip.h: no atomics, the same bits on every call.  Included at the end of gspx.hip (after
+// gspx_ops.hip.h, which brings gspx_reduce.hip.h).
 #pragma once
 
 namespace gspx {
 
-// Column kernels share one thread map (k_coldot_partial's): thread t of a 256-thread workgroup takes column
-// t % ldp (ldp = ld rounded up to a power of two) and rows blockIdx.x * rstep + t / ldp + s * gridDim.x * rstep,
-// rstep = 256 / ldp.  Lanes of one row read neighbouring doubles; for ld = 1 neighbouring rows.
+// Column kernels use the shared thread map of gspx_reduce.hip.h (column t % ldp, row lanes t / ldp).
 constexpr int LZ_JB = 16;  // stack panels per workgroup of the dot kernel
 constexpr int LZ_MAX_WIDTH = 256;
 
@@ -35,18 +34,6 @@ struct LzScalars {  // device resident
   int* active;      // [ld]
   int* steps;       // [ld]: Krylov vectors written so far (m)
 };
-
-// (the LDS reduction of one value per thread over the rstep row lanes of each column, fixed order)
-__device__ inline void lz_block_sum(double* ws, double v, int ld, int ldp, int rstep, double* out) {
-  ws[threadIdx.x] = v;
-  __syncthreads();
-  if ((int)threadIdx.x < ld) {
-    double s = 0;
-    for (int k = 0; k < rstep; ++k) s += ws[k * ldp + threadIdx.x];
-    out[threadIdx.x] = s;
-  }
-  __syncthreads();
-}
 
 // beta_0 = ||x||; a zero column never starts (its outputs stay zero)
 __global__ void k_lz_start(LzScalars s, int ld) {
@@ -98,7 +85,7 @@ __global__ __launch_bounds__(256) void k_lz_three(double* __restrict__ V, size_t
       acc += q * w;
     }
   }
-  lz_block_sum(ws, acc, ld, ldp, rstep, partial + (size_t)blockIdx.x * ld);
+  block_colsum(ws, acc, ld, ldp, rstep, partial + (size_t)blockIdx.x * ld);
 }
 
 // partial h_j = q_j . (w - alpha_k q_k) for the LZ_JB stack panels j0 = blockIdx.y * LZ_JB .. of j = 0..nj-1
@@ -131,7 +118,7 @@ __global__ __launch_bounds__(256) void k_lz_dots(const double* __restrict__ V, s
   double* out = partial + (size_t)blockIdx.x * nj * ld + (size_t)j0 * ld;
 #pragma unroll
   for (int jj = 0; jj < LZ_JB; ++jj)
-    if (jj < nb) lz_block_sum(ws, acc[jj], ld, ldp, rstep, out + (size_t)jj * ld);
+    if (jj < nb) block_colsum(ws, acc[jj], ld, ldp, rstep, out + (size_t)jj * ld);
 }
 
 // r = w - alpha_k q_k - sum_j h_j q_j (active columns; a stopped column keeps its r) and partial ||r||^2.
@@ -176,7 +163,7 @@ __global__ __launch_bounds__(256) void k_lz_update(const double* __restrict__ V,
     }
     acc = (a[0] + a[1]) + (a[2] + a[3]);
   }
-  lz_block_sum(ws, acc, ld, ldp, rstep, partial + (size_t)blockIdx.x * ld);
+  block_colsum(ws, acc, ld, ldp, rstep, partial + (size_t)blockIdx.x * ld);
 }
 
 // y[(f0 + f) N + perm[i]][c] = sum_j Wt[f0 + f][j][c] V_j[i][c] for FB filters; two rows per thread, so that
@@ -224,12 +211,6 @@ __global__ __launch_bounds__(256) void k_lz_combine(const double* __restrict__ V
 }  // namespace gspx
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static int lz_pow2(int ld) {
-  int p = 1;
-  while (p < ld) p <<= 1;
-  return p;
-}
-
 // workgroups along the rows: about 2048 in all (eight per CU) over `groups` workgroup columns, and no more than
 // the rows need
 static int lz_rows_grid(int64_t N, int ldp, int groups) {
@@ -237,15 +218,6 @@ static int lz_rows_grid(int64_t N, int ldp, int groups) {
   const int64_t need = (N + rstep - 1) / rstep;
   const int64_t want = std::max<int64_t>(64, 2048 / std::max(groups, 1));
   return (int)std::max<int64_t>(1, std::min(need, want));
-}
-
-// sum of `nparts` partial slabs of `count` entries, in a fixed order
-static void lz_colsum(const double* partial, int nparts, int64_t count, double* out, hipStream_t st) {
-  if (count >= 4096)
-    hipLaunchKernelGGL(gspx::k_panel_sum_parts, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, partial,
-                       nparts, count, out);
-  else
-    hipLaunchKernelGGL(gspx::k_colsum, dim3((unsigned)count), dim3(64), 0, st, partial, nparts, (int)count, out);
 }
 
 // per-phase event timing (only when the caller asks for phase times): one event pair per launch group
@@ -319,7 +291,7 @@ extern "C" int gspx_lanczos_krylov_dev(gspx_graph* g, int order, int64_t Nsig, c
   gspx_ctx* ctx = g->ctx;
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const int ldp = lz_pow2(ld);
+  const int ldp = col_pow2(ld);
   const size_t U = (size_t)N * ld;
   const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
   // work panels: x (internal order), r, W; scalars; reduction partials (sized for the widest launch: the projection)
@@ -359,7 +331,7 @@ extern "C" int gspx_lanczos_krylov_dev(gspx_graph* g, int order, int64_t Nsig, c
   CHK(tm.mark(st, LZ_PH_PERMUTE));
   hipLaunchKernelGGL((gspx::k_coldot_partial<double>), dim3(nred1), dim3(256), 0, st, X, X, (int)N, ld, ldp,
                      partial.as<double>());
-  lz_colsum(partial.as<double>(), nred1, ld, s.rr, st);
+  sum_parts(partial.as<double>(), nred1, ld, s.rr, st);
   hipLaunchKernelGGL(gspx::k_lz_start, dim3(nsm), dim3(64), 0, st, s, ld);
   CHK(tm.mark(st, LZ_PH_UPDATE));
   for (int k = 0; k < order; ++k) {
@@ -367,18 +339,18 @@ extern "C" int gspx_lanczos_krylov_dev(gspx_graph* g, int order, int64_t Nsig, c
     CHK(tm.mark(st, LZ_PH_SPMM));
     hipLaunchKernelGGL(gspx::k_lz_three, dim3(nred1), dim3(256), 0, st, V, ps, k, R, W, s, N, ld, ldp,
                        partial.as<double>());
-    lz_colsum(partial.as<double>(), nred1, ld, s.alpha + (size_t)k * ld, st);
+    sum_parts(partial.as<double>(), nred1, ld, s.alpha + (size_t)k * ld, st);
     CHK(tm.mark(st, LZ_PH_THREE));
     if (k + 1 == order) break;  // (beta_order is not needed)
     const int nj = k + 1, gy = (nj + gspx::LZ_JB - 1) / gspx::LZ_JB;
     const int nr = lz_rows_grid(N, ldp, gy);
     hipLaunchKernelGGL(gspx::k_lz_dots, dim3(nr, gy), dim3(256), 0, st, V, ps, nj, V + (size_t)k * ps, W,
                        s.alpha + (size_t)k * ld, N, ld, ldp, partial.as<double>());
-    lz_colsum(partial.as<double>(), nr, (int64_t)nj * ld, s.h, st);
+    sum_parts(partial.as<double>(), nr, (int64_t)nj * ld, s.h, st);
     CHK(tm.mark(st, LZ_PH_DOTS));
     hipLaunchKernelGGL(gspx::k_lz_update, dim3(nred1), dim3(256), 0, st, V, ps, k, W, R, s, N, ld, ldp,
                        partial.as<double>());
-    lz_colsum(partial.as<double>(), nred1, ld, s.rr, st);
+    sum_parts(partial.as<double>(), nred1, ld, s.rr, st);
     hipLaunchKernelGGL(gspx::k_lz_next, dim3(nsm), dim3(64), 0, st, s, ld, k, breakdown);
     CHK(tm.mark(st, LZ_PH_UPDATE));
   }
@@ -387,20 +359,16 @@ extern "C" int gspx_lanczos_krylov_dev(gspx_graph* g, int order, int64_t Nsig, c
     const int nr = lz_rows_grid(N, ldp, gy);
     hipLaunchKernelGGL(gspx::k_lz_dots, dim3(nr, gy), dim3(256), 0, st, V, ps, order, (const double*)nullptr, X,
                        (const double*)nullptr, N, ld, ldp, partial.as<double>());
-    lz_colsum(partial.as<double>(), nr, (int64_t)order * ld, proj, st);
+    sum_parts(partial.as<double>(), nr, (int64_t)order * ld, proj, st);
     CHK(tm.mark(st, LZ_PH_PROJ));
   }
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  HIPCHK(hipGetLastError());
   const size_t ob = (size_t)order * ld * sizeof(double);
   HIPCHK(hipMemcpyAsync(alpha_host, s.alpha, ob, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(beta_host, s.beta, ob, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(proj_host, proj, ob, hipMemcpyDeviceToHost, st));
   HIPCHK(hipMemcpyAsync(steps_host, s.steps, (size_t)ld * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-  if (kernel_ms) *kernel_ms = f;
+  CHK(finish_timed(ctx, kernel_ms));
   if (phase_ms) CHK(tm.sum(phase_ms, LZ_NPHASE));
   return GSPX_OK;
 }
@@ -429,7 +397,7 @@ extern "C" int gspx_lanczos_combine_dev(gspx_graph* g, int order, int64_t Nsig, 
   const size_t wbytes = (size_t)Nf * order * ld * sizeof(double);
   CHK(ctx->ws_spec.ensure(wbytes));
   HIPCHK(hipMemcpyAsync(ctx->ws_spec.p, weights_host, wbytes, hipMemcpyHostToDevice, st));
-  const int ldp = lz_pow2(ld);
+  const int ldp = col_pow2(ld);
   const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
   const double* V = (const double*)V_dev;
   const size_t ps = (size_t)N * ld;
@@ -450,10 +418,5 @@ extern "C" int gspx_lanczos_combine_dev(gspx_graph* g, int order, int64_t Nsig, 
   }
 #undef LZ_COMBINE
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-  if (kernel_ms) *kernel_ms = f;
-  return GSPX_OK;
+  return finish_timed(ctx, kernel_ms);
 }

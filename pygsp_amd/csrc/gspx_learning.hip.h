@@ -378,11 +378,7 @@ static int tikhonov_simplex_t(gspx_graph* g, double tau, double step, const int3
   CHK(permute_panel<double>(g, X[n_it % 3], (unsigned)C, x, (unsigned)C, iperm));
   HIPCHK(hipMemcpyAsync(objective, obj.p, (size_t)(n_it + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-  if (ms) *ms = f;
+  CHK(finish_timed(ctx, ms));
   *niter = n_it;
   *crit = hs.crit;
   return GSPX_OK;

@@ -3,6 +3,7 @@
 // row-major N x Nsig panels of the graph's compute dtype, in the caller's vertex order.
 #pragma once
 
+#include "gspx_reduce.hip.h"
 #include "gspx_ops_kernels.hip.h"
 
 // byte offsets col*ld*sizeof(T) for this panel width (LDS / wave-row kernels), cached on the graph
@@ -94,29 +95,18 @@ static int lap_apply_t(gspx_graph* g, int64_t Nsig, const T* x, T* y, double* ms
     CHK(ensure_s1nat(g, st));
     CHK(spmm_internal<T>(g, g->rval.as<T>(), T(1), T(0), x, nullptr, (unsigned)Nsig, y, (unsigned)Nsig,
                          g->has_perm ? g->gt_s1nat.as<int>() : nullptr));
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(st));
-    float f1 = 0;
-    HIPCHK(hipEventElapsedTime(&f1, ctx->ev[0], ctx->ev[1]));
-    if (ms) *ms = f1;
-    return GSPX_OK;
-  }
-  for (int64_t c0 = 0; c0 < Nsig; c0 += max_ld) {
-    const unsigned ld = (unsigned)std::min<int64_t>(max_ld, Nsig - c0);
-    CHK(ctx->ws_t.ensure((size_t)N * ld * sizeof(T) + 256));
-    T* P0 = ctx->ws_t.as<T>();
-    CHK(permute_panel<T>(g, x + c0, (unsigned)Nsig, P0, ld, perm));
-    // the internal values array rval IS L (k_factor derives F from it)
-    CHK(spmm_internal<T>(g, g->rval.as<T>(), T(1), T(0), P0, nullptr, ld, y + c0, (unsigned)Nsig));
+  } else {
+    for (int64_t c0 = 0; c0 < Nsig; c0 += max_ld) {
+      const unsigned ld = (unsigned)std::min<int64_t>(max_ld, Nsig - c0);
+      CHK(ctx->ws_t.ensure((size_t)N * ld * sizeof(T) + 256));
+      T* P0 = ctx->ws_t.as<T>();
+      CHK(permute_panel<T>(g, x + c0, (unsigned)Nsig, P0, ld, perm));
+      // the internal values array rval IS L (k_factor derives F from it)
+      CHK(spmm_internal<T>(g, g->rval.as<T>(), T(1), T(0), P0, nullptr, ld, y + c0, (unsigned)Nsig));
+    }
   }
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-  if (ms) *ms = f;
-  return GSPX_OK;
+  return finish_timed(ctx, ms);
 }
 
 extern "C" int gspx_laplacian_apply_dev(gspx_graph* g, int64_t Nsig, const void* x_dev, void* y_dev,
@@ -148,33 +138,16 @@ static int dirichlet_t(gspx_graph* g, int64_t Nsig, const T* x, double* gram, do
   CHK(ctx->ws_t.ensure((size_t)2 * N * ld * sizeof(T) + 256));
   T* P0 = ctx->ws_t.as<T>();
   T* P1 = P0 + (size_t)N * ld;
-  // per-wave partial Gram matrices, reduced on the device (at most 512 MB of them)
-  const int64_t nw_cap = std::max<int64_t>(4, ((int64_t)512 << 20) / ((int64_t)ld * ld * 8));
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(512, nw_cap / 4), (N + 255) / 256));
-  const int nwaves = nb * 4;
-  DevMem partial, gsum;
-  CHK(partial.alloc((size_t)nwaves * ld * ld * sizeof(double)));
-  CHK(gsum.alloc((size_t)ld * ld * sizeof(double)));
   HIPCHK(hipEventRecord(ctx->ev[0], st));
   CHK(permute_panel<T>(g, x, ld, P0, ld, g->has_perm ? g->perm.as<int>() : nullptr));
   CHK(spmm_internal<T>(g, g->rval.as<T>(), T(1), T(0), P0, P1, ld, nullptr, 0));
-  // the sums do not depend on the vertex order: both panels stay in the internal order
-  for (int a0 = 0; a0 < (int)ld; a0 += 64)
-    for (int c0 = 0; c0 < (int)ld; c0 += 64) {
-      const int na = std::min(64, (int)ld - a0), nc = std::min(64, (int)ld - c0);
-      hipLaunchKernelGGL((k_gram_mfma<T>), dim3(nb), dim3(256), 0, st, P0, P1, (int)N, (int)ld, a0, na, c0,
-                         nc, partial.as<double>());
-    }
-  hipLaunchKernelGGL(k_colsum, dim3(ld * ld), dim3(64), 0, st, partial.as<double>(), nwaves, (int)(ld * ld),
-                     gsum.as<double>());
-  HIPCHK(hipMemcpyAsync(gram, gsum.p, (size_t)ld * ld * sizeof(double), hipMemcpyDeviceToHost, st));
+  // the sums do not depend on the vertex order: both panels stay in the internal order.  (The Gram grows
+  // ctx->ws_spec after the launches above; they wrote workspace only, so a call that fails there can be repeated.)
+  double* gsum = nullptr;
+  CHK(launch_panel_gram<T>(ctx, P0, ld, (int)ld, P1, ld, (int)ld, N, &gsum));
+  HIPCHK(hipMemcpyAsync(gram, gsum, (size_t)ld * ld * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-  if (ms) *ms = f;
-  return GSPX_OK;
+  return finish_timed(ctx, ms);
 }
 
 extern "C" int gspx_dirichlet_energy_dev(gspx_graph* g, int64_t Nsig, const void* x_dev,
@@ -218,8 +191,7 @@ static int tikhonov_t(gspx_graph* g, double tau, const T* mask, int64_t Nsig, co
   const int nred = (int)std::min<int64_t>(4096, std::max<int64_t>(1, N / 64));
   for (int64_t c0 = 0; c0 < Nsig; c0 += max_ld) {
     const unsigned ld = (unsigned)std::min<int64_t>(max_ld, Nsig - c0);
-    int ldp = 1;
-    while (ldp < (int)ld) ldp <<= 1;
+    const int ldp = col_pow2((int)ld);
     const size_t U = (size_t)N * ld;
     CHK(ctx->ws_t.ensure(5 * U * sizeof(T) + 256));
     T* X = ctx->ws_t.as<T>();
@@ -242,7 +214,7 @@ static int tikhonov_t(gspx_graph* g, double tau, const T* mask, int64_t Nsig, co
     auto coldot = [&](const T* a_, const T* b_, double* out) {
       hipLaunchKernelGGL((k_coldot_partial<T>), dim3(nred), dim3(256), 0, st, a_, b_, (int)N, (int)ld,
                          ldp, partial.as<double>());
-      hipLaunchKernelGGL(k_colsum, dim3(ld), dim3(64), 0, st, partial.as<double>(), nred, (int)ld, out);
+      sum_parts(partial.as<double>(), nred, ld, out, st);
     };
     // b = M y (learning.py:325-326 zeroes the unmeasured entries), r = b, x = 0
     CHK(permute_panel<T>(g, y + c0, (unsigned)Nsig, B, ld, perm));
@@ -271,7 +243,7 @@ static int tikhonov_t(gspx_graph* g, double tau, const T* mask, int64_t Nsig, co
       hipLaunchKernelGGL(k_cg_post, dim3(nbl), dim3(64), 0, st, s, s.pq, (int)ld);
       hipLaunchKernelGGL((k_cg_xr_dot<T>), dim3(nred), dim3(256), 0, st, X, R, P, Q, (int)N, (int)ld, ldp, s,
                          partial.as<double>());
-      hipLaunchKernelGGL(k_colsum, dim3(ld), dim3(64), 0, st, partial.as<double>(), nred, (int)ld, rr);
+      sum_parts(partial.as<double>(), nred, ld, rr, st);
     }
     CHK(permute_panel<T>(g, X, ld, x + c0, (unsigned)Nsig, iperm));
     if (iters) {
@@ -282,12 +254,7 @@ static int tikhonov_t(gspx_graph* g, double tau, const T* mask, int64_t Nsig, co
     }
   }
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-  if (ms) *ms = f;
-  return GSPX_OK;
+  return finish_timed(ctx, ms);
 }
 
 extern "C" int gspx_tikhonov_cg_dev(gspx_graph* g, double tau, const void* mask_dev, int64_t Nsig,
@@ -494,12 +461,7 @@ static int grad_div_t(gspx_graph* g, bool is_div, int64_t Nsig, const T* in, T* 
     hipLaunchKernelGGL((k_grad<T>), dim3(nb), dim3(256), 0, st, g->e_src.as<int>(), g->e_dst.as<int>(),
                        g->e_cs.as<T>(), g->e_ct.as<T>(), in, out, (size_t)g->n_edges, (int)Nsig, cw);
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
-  float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-  if (ms) *ms = f;
-  return GSPX_OK;
+  return finish_timed(ctx, ms);
 }
 
 static int grad_div(gspx_graph* g, bool is_div, int64_t Nsig, const void* in, void* out, double* ms) {

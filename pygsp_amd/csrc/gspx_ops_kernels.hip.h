@@ -1,6 +1,7 @@
 // gspx_ops_kernels.hip.h - device kernels of the operators that reuse the engine's CSR next to the
 // Chebyshev path: L x, Dirichlet energy, the conjugate-gradient
-// loop of Tikhonov regression, gradient / divergence.  gfx950 only.
+// loop of Tikhonov regression, gradient / divergence.  gfx950 only.  The column reductions end in
+// gspx_reduce.hip.h's block_colsum (included before this file by gspx_ops.hip.h).
 //
 // Reference call sites:
 //   Graph.dirichlet_energy          pygsp/graphs/graph.py:642-702      x.T.dot(L.dot(x))
@@ -32,7 +33,7 @@ __global__ void k_affine_values(const int* __restrict__ rptr, const int* __restr
 
 // ---- column-wise reductions over N x ld row-major panels ------------------------------------------
 // partial[b][c] = sum over the block's rows of A[i][c] * B[i][c]  (double accumulation, fixed order).
-// ldp = power of two >= ld (<= 256): thread t works on column t % ldp, rows t / ldp + k * (256 / ldp).
+// The shared thread map of gspx_reduce.hip.h, four rows in flight per thread.
 template <typename T>
 __global__ __launch_bounds__(256) void k_coldot_partial(const T* __restrict__ A, const T* __restrict__ B,
                                                         int N, int ld, int ldp,
@@ -55,73 +56,7 @@ __global__ __launch_bounds__(256) void k_coldot_partial(const T* __restrict__ A,
     for (; i < (size_t)N; i += stride) a0 += (double)A[i * ld + c] * (double)B[i * ld + c];
     acc = (a0 + a1) + (a2 + a3);
   }
-  ws[threadIdx.x] = acc;
-  __syncthreads();
-  if ((int)threadIdx.x < ldp) {
-    double s = 0;
-    for (int k = 0; k < rstep; ++k) s += ws[k * ldp + threadIdx.x];
-    if ((int)threadIdx.x < ld) partial[(size_t)blockIdx.x * ld + threadIdx.x] = s;
-  }
-}
-// out[c] = sum_b partial[b][c]: one 64-lane wave per column, fixed summation tree (deterministic)
-__global__ __launch_bounds__(64) void k_colsum(const double* __restrict__ partial, int nb, int ld,
-                                               double* __restrict__ out) {
-  const int c = blockIdx.x;
-  if (c >= ld) return;
-  double s = 0;
-  for (int b = threadIdx.x; b < nb; b += 64) s += partial[(size_t)b * ld + c];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-  if (threadIdx.x == 0) out[c] = s;
-}
-
-// Gram block on the matrix cores: G[a0 + a][c0 + c] += sum_i X[i][a0 + a] * Y[i][c0 + c] for a 64 x 64 block
-// of the Gram matrix (na, nc <= 64 valid columns).  This IS a dense panel contraction (8 flop/byte at 64
-// signals), so it runs on MFMA: v_mfma_f64_16x16x4f64 takes A = X^T (16 signals x 4 rows) and B = Y
-// (4 rows x 16 signals) straight from coalesced row loads - lane l holds row l / 16, column l % 16 of
-// both - and accumulates a 16 x 16 tile; a wave keeps the 4 x 4 tiles of its block in registers and
-// walks the rows four at a time.  fp32 panels are converted on load: the sums are double either way.
-// partial[w][a][c] (ld x ld per wave, only this block's entries written).
-template <typename T>
-__global__ __launch_bounds__(256) void k_gram_mfma(const T* __restrict__ X, const T* __restrict__ Y, int N,
-                                                   int ld, int a0, int na, int c0, int nc,
-                                                   double* __restrict__ partial) {
-  typedef double d4 __attribute__((ext_vector_type(4)));
-  const int lane = threadIdx.x & 63;
-  const int kq = lane >> 4, cq = lane & 15;
-  const int gw = blockIdx.x * 4 + (threadIdx.x >> 6), nw = gridDim.x * 4;
-  d4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0;
-  for (long r4 = gw; r4 * 4 < (long)N; r4 += nw) {
-    const long row = r4 * 4 + kq;
-    const bool rok = row < (long)N;
-    double xa[4], yb[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int ca = t * 16 + cq;
-      xa[t] = (rok && ca < na) ? (double)X[(size_t)row * ld + a0 + ca] : 0.0;
-      yb[t] = (rok && ca < nc) ? (double)Y[(size_t)row * ld + c0 + ca] : 0.0;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[i], yb[j], acc[i][j], 0, 0, 0);
-  }
-  // D layout of the f64 16x16x4 instruction: lane l holds rows (l / 16) + 4 e (e = 0..3), column l % 16
-  double* out = partial + (size_t)gw * ld * ld;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int aa = i * 16 + kq + 4 * e, cc = j * 16 + cq;
-        if (aa < na && cc < nc) out[(size_t)(a0 + aa) * ld + (c0 + cc)] = acc[i][j][e];
-      }
+  block_colsum(ws, acc, ld, ldp, rstep, partial + (size_t)blockIdx.x * ld);
 }
 
 // ---- conjugate gradient, one independent system per column (scipy.sparse.linalg.cg's recurrence) ---
@@ -221,13 +156,7 @@ __global__ __launch_bounds__(256) void k_cg_xr_dot(T* __restrict__ x, T* __restr
     for (; i < (size_t)N; i += stride) a0 += upd(i);
     acc = (a0 + a1) + (a2 + a3);
   }
-  ws[threadIdx.x] = acc;
-  __syncthreads();
-  if ((int)threadIdx.x < ldp) {
-    double t = 0;
-    for (int k = 0; k < rstep; ++k) t += ws[k * ldp + threadIdx.x];
-    if ((int)threadIdx.x < ld) partial[(size_t)blockIdx.x * ld + threadIdx.x] = t;
-  }
+  block_colsum(ws, acc, ld, ldp, rstep, partial + (size_t)blockIdx.x * ld);
 }
 __global__ void k_cg_init(CgScalars s, const double* __restrict__ bb, int ld, double rtol, double atol) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;

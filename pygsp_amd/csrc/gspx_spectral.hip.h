@@ -6,107 +6,14 @@
 //   r_i = ||LX_i - th_i X_i|| gspx_panel_residual_norms_dev  (one read of both panels)
 //   Y = X (strided)           gspx_panel_copy_dev            (a column block out of / into a wider panel)
 // Panels are row-major device arrays with an explicit leading dimension (elements), any N >= 0, widths 1..512.
-// Gram and combine run on the matrix cores (v_mfma_f64_16x16x4f64).  Every reduction is per workgroup (or per
-// wave) into partials, then a fixed-order second pass (gspx::k_colsum): no atomics, the same bits on every call.
-// Included at the end of gspx.hip (uses its helpers and gspx_ops_kernels.hip.h).
+// Gram and combine run on the matrix cores (v_mfma_f64_16x16x4f64).  The Gram kernel and the second pass of every
+// reduction are gspx_reduce.hip.h's (launch_panel_gram, sum_parts): no atomics, the same bits on every call.
+// Included at the end of gspx.hip (uses its helpers and gspx_reduce.hip.h).
 #pragma once
 
 namespace gspx {
 
 typedef double spec_d4 __attribute__((ext_vector_type(4)));
-
-// ---- C = A^T B: per wave a 64 x 64 tile of C over a slice of rows ------------------------------------------
-// grid.x = tile (ta * ntb + tb), grid.y = row chunk of `rpc` rows (a multiple of 16).  Wave w of the workgroup takes
-// the 4-row groups w, w + 4, ... of its chunk.  v_mfma_f64_16x16x4f64 with A-operand = A^T (lane l: column l % 16 of
-// the tile, row l / 16 of the group) and B-operand = B (the same lane map): coalesced 128-byte row segments, no LDS.
-// D layout of the f64 instruction: lane l holds rows (l / 16) + 4 e, column l % 16.
-// The four waves' tiles are summed in LDS in a fixed order (((w0 + w1) + w2) + w3) and wave 0 writes the workgroup's
-// partial[chunk * na * nb + a * nb + c]: every entry of every chunk's slot is written (zeros where the slice has no
-// rows), so the second pass needs no initialisation.
-__global__ __launch_bounds__(256) void k_panel_gram(const double* __restrict__ A, int64_t lda, int na,
-                                                    const double* __restrict__ B, int64_t ldb, int nb, int64_t N,
-                                                    int64_t rpc, double* __restrict__ partial) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int kq = lane >> 4, cq = lane & 15;
-  const int ntb = (nb + 63) / 64;
-  const int a0 = (int)(blockIdx.x / ntb) * 64, b0 = (int)(blockIdx.x % ntb) * 64;
-  const int nta = min(4, (na - a0 + 15) / 16), ntc = min(4, (nb - b0 + 15) / 16);  // 16-wide sub-tiles in use
-  const int64_t r_begin = (int64_t)blockIdx.y * rpc;
-  const int64_t r_end = min(N, r_begin + rpc);
-  spec_d4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0;
-  for (int64_t r = r_begin + 4 * w; r < r_end; r += 16) {
-    const int64_t row = r + kq;
-    const bool rok = row < r_end;
-    double xa[4], yb[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int ca = a0 + t * 16 + cq, cb = b0 + t * 16 + cq;
-      xa[t] = (rok && ca < na) ? A[row * lda + ca] : 0.0;
-      yb[t] = (rok && cb < nb) ? B[row * ldb + cb] : 0.0;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < nta)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (j < ntc) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[i], yb[j], acc[i][j], 0, 0, 0);
-  }
-  __shared__ double red[16 * 4 * 64];  // one wave's 4 x 4 tiles, lane-major (no bank conflicts)
-  for (int src = 1; src < 4; ++src) {
-    if (w == src)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) red[((i * 4 + j) * 4 + e) * 64 + lane] = acc[i][j][e];
-    __syncthreads();
-    if (w == 0)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[i][j][e] += red[((i * 4 + j) * 4 + e) * 64 + lane];
-    __syncthreads();
-  }
-  if (w != 0) return;
-  double* out = partial + (size_t)blockIdx.y * (size_t)na * nb;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int aa = a0 + i * 16 + kq + 4 * e, cc = b0 + j * 16 + cq;
-        if (aa < na && cc < nb) out[(size_t)aa * nb + cc] = acc[i][j][e];
-      }
-}
-
-// out[c] = sum over b of partial[b * count + c], b in order: one thread per entry, so neighbouring threads read
-// neighbouring entries (the second pass of the Gram when it has many entries; gspx::k_colsum, one wave per entry with
-// a fixed tree, takes the narrow ones)
-__global__ __launch_bounds__(256) void k_panel_sum_parts(const double* __restrict__ partial, int nparts, int64_t count,
-                                                         double* __restrict__ out) {
-  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (c >= count) return;
-  double s = 0;
-  int b = 0;
-  for (; b + 4 <= nparts; b += 4) {
-    const double v0 = partial[(size_t)b * count + c], v1 = partial[(size_t)(b + 1) * count + c];
-    const double v2 = partial[(size_t)(b + 2) * count + c], v3 = partial[(size_t)(b + 3) * count + c];
-    s += v0;
-    s += v1;
-    s += v2;
-    s += v3;
-  }
-  for (; b < nparts; ++b) s += partial[(size_t)b * count + c];
-  out[c] = s;
-}
 
 // ---- Y = X Q: a workgroup owns 64 rows x 64 columns of Y ---------------------------------------------------
 // The contraction runs in chunks of SPEC_KC columns of X: the X chunk (64 rows) and the matching SPEC_KC x 64 tile of
@@ -215,15 +122,6 @@ static size_t spec_span(int64_t N, int64_t ld, int width) {
 
 // kernel_ms covers the kernels only: ev[0] is recorded after the small host-to-device copies (Q, theta) and ev[1]
 // before the device-to-host copy of the result
-static int spec_finish(gspx_ctx* ctx, double* kernel_ms) {
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  float f = 0;
-  HIPCHK(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-  if (kernel_ms) *kernel_ms = f;
-  return GSPX_OK;
-}
-
 extern "C" int gspx_panel_gram_dev(gspx_ctx* ctx, int64_t N, const double* A, int64_t lda, int na, const double* B,
                                    int64_t ldb, int nb, double* C_host, double* kernel_ms) {
   if (N < 0) return set_err(GSPX_ERR_INVALID, "panel_gram: negative number of rows");
@@ -241,30 +139,13 @@ extern "C" int gspx_panel_gram_dev(gspx_ctx* ctx, int64_t N, const double* A, in
     return GSPX_OK;
   }
   HIPCHK(hipSetDevice(ctx->device));
-  const int ntiles = ((na + 63) / 64) * ((nb + 63) / 64);
-  // about eight workgroups per CU in all; at least 16 rows per wave; at most 256 MiB of partials
-  int64_t nchunk = std::max<int64_t>(1, ((int64_t)8 * ctx->cu_count + ntiles - 1) / ntiles);
-  nchunk = std::min<int64_t>(nchunk, (N + 63) / 64);
-  nchunk = std::min<int64_t>(nchunk, std::max<int64_t>(1, ((int64_t)256 << 20) / (int64_t)(count * sizeof(double))));
-  nchunk = std::min<int64_t>(nchunk, 65535);
-  const int64_t rpc = ((N + nchunk - 1) / nchunk + 15) / 16 * 16;
-  nchunk = (N + rpc - 1) / rpc;
-  const size_t nparts = (size_t)nchunk;
-  CHK(ctx->ws_spec.ensure((nparts + 1) * count * sizeof(double)));
-  double* partial = ctx->ws_spec.as<double>();
-  double* csum = partial + nparts * count;
   hipStream_t st = ctx->stream;
+  double* csum = nullptr;
   HIPCHK(hipEventRecord(ctx->ev[0], st));
-  hipLaunchKernelGGL(gspx::k_panel_gram, dim3(ntiles, (unsigned)nchunk), dim3(256), 0, st, A, lda, na, B, ldb, nb, N, rpc,
-                     partial);
-  if (count >= 4096)
-    hipLaunchKernelGGL(gspx::k_panel_sum_parts, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, partial,
-                       (int)nparts, (int64_t)count, csum);
-  else
-    hipLaunchKernelGGL(gspx::k_colsum, dim3((unsigned)count), dim3(64), 0, st, partial, (int)nparts, (int)count, csum);
+  CHK(launch_panel_gram<double>(ctx, A, lda, na, B, ldb, nb, N, &csum));
   HIPCHK(hipEventRecord(ctx->ev[1], st));
   HIPCHK(hipMemcpyAsync(C_host, csum, count * sizeof(double), hipMemcpyDeviceToHost, st));
-  return spec_finish(ctx, kernel_ms);
+  return finish_timed(ctx, kernel_ms);
 }
 
 extern "C" int gspx_panel_combine_dev(gspx_ctx* ctx, int64_t N, const double* X, int64_t ldx, int p,
@@ -292,7 +173,7 @@ extern "C" int gspx_panel_combine_dev(gspx_ctx* ctx, int64_t N, const double* X,
   hipLaunchKernelGGL(gspx::k_panel_combine, dim3(grid), dim3(256), 0, st, X, ldx, p, ctx->ws_spec.as<double>(), q, Y,
                      ldy, N);
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  return spec_finish(ctx, kernel_ms);
+  return finish_timed(ctx, kernel_ms);
 }
 
 extern "C" int gspx_panel_residual_norms_dev(gspx_ctx* ctx, int64_t N, const double* X, const double* LX, int64_t ld,
@@ -321,10 +202,10 @@ extern "C" int gspx_panel_residual_norms_dev(gspx_ctx* ctx, int64_t N, const dou
   HIPCHK(hipMemcpyAsync(th, theta_host, (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipEventRecord(ctx->ev[0], st));
   hipLaunchKernelGGL(gspx::k_panel_residual, dim3(nbk, (p + 63) / 64), dim3(256), 0, st, X, LX, ld, p, th, N, partial);
-  hipLaunchKernelGGL(gspx::k_colsum, dim3(p), dim3(64), 0, st, partial, nbk, p, sums);
+  sum_parts(partial, nbk, p, sums, st);
   HIPCHK(hipEventRecord(ctx->ev[1], st));
   HIPCHK(hipMemcpyAsync(out_host, sums, (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
-  CHK(spec_finish(ctx, kernel_ms));
+  CHK(finish_timed(ctx, kernel_ms));
   for (int i = 0; i < p; ++i) out_host[i] = std::sqrt(out_host[i]);
   return GSPX_OK;
 }
@@ -348,5 +229,5 @@ extern "C" int gspx_panel_copy_dev(gspx_ctx* ctx, int64_t N, const double* X, in
   HIPCHK(hipMemcpy2DAsync(Y, (size_t)ldy * sizeof(double), X, (size_t)ldx * sizeof(double), (size_t)w * sizeof(double),
                           (size_t)N, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipEventRecord(ctx->ev[1], st));
-  return spec_finish(ctx, kernel_ms);
+  return finish_timed(ctx, kernel_ms);
 }

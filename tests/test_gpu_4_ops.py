@@ -128,6 +128,38 @@ def test_oracle_sensor20k(ctx, dtype, lap_type):
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_dirichlet_shared_gram(ctx, dtype):
+    """dirichlet_energy on the Gram kernel it shares with the panel primitives: graphs below one 4-row group, with a
+    ragged last group (70) and with several row chunks and a short last one (257); widths at the 16-column sub-tile
+    and 64-column tile edges and one above the panel primitives' own limit of 512; with and without a vertex
+    permutation.  Against the oracle on the float64 copy, the same bits on a second call, symmetric within the same
+    tolerance; 2048 signals still pass and 2049 are still refused."""
+    tol = TOL[np.dtype(dtype)] * 10
+    rng = np.random.default_rng(23)
+    for N in (2, 5, 70, 257):
+        W = random_graph(N, 4, seed=60 + N)
+        L = ops.laplacian(W)
+        widths = (1, 15, 16, 17, 64, 65, 130, 513) + ((2048,) if N == 70 and dtype == np.float64 else ())
+        refs = {}
+        for perm in (rng.permutation(N).astype(np.int32), None):
+            dev = engine.DeviceGraph.from_w(W, dtype=dtype, perm=perm, ctx=ctx)
+            for nsig in widths:
+                if perm is not None:
+                    X = rng.standard_normal((N, nsig)).astype(dtype)
+                    refs[nsig] = (X, ops.dirichlet_energy(L, X.astype(np.float64)))
+                X, ref = refs[nsig]
+                gram = dev.dirichlet_energy(X)
+                assert gram.shape == (nsig, nsig)
+                assert rel_err(gram, ref) < tol, (N, nsig, perm is not None)
+                assert np.array_equal(gram, dev.dirichlet_energy(X)), (N, nsig)
+                assert rel_err(gram.T, gram) <= tol, (N, nsig, "symmetry")
+            if N == 70:
+                with pytest.raises(ValueError, match="0 <= Nsig <= 2048"):
+                    dev.dirichlet_energy(np.zeros((N, 2049), dtype=dtype))
+            dev.destroy()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_oracle_tikhonov(ctx, dtype):
     tol = CGTOL[np.dtype(dtype)]
     rng = np.random.default_rng(11)

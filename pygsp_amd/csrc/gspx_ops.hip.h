@@ -245,7 +245,16 @@ static int tikhonov_t(gspx_graph* g, double tau, const T* mask, int64_t Nsig, co
                          partial.as<double>());
       sum_parts(partial.as<double>(), nred, ld, rr, st);
     }
-    CHK(permute_panel<T>(g, X, ld, x + c0, (unsigned)Nsig, iperm));
+    if ((int64_t)ld == Nsig) {
+      CHK(permute_panel<T>(g, X, ld, x, ld, iperm));
+    } else {
+      // a column batch of a wider result: ld columns into rows of pitch Nsig (permute_panel copies whole rows of
+      // the output's pitch: it would carry Nsig columns of every row of X, over the other batches' columns and,
+      // from the second batch on, c0 elements past the end of x)
+      const unsigned nbo = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
+      hipLaunchKernelGGL((k_permute_out_pad<T>), dim3(nbo), dim3(256), 0, st, X, ld, x + c0, (unsigned)Nsig, ld, (int)N,
+                         perm);
+    }
     if (iters) {
       std::vector<int> hi(ld);
       HIPCHK(hipMemcpyAsync(hi.data(), s.iters, ld * sizeof(int), hipMemcpyDeviceToHost, st));

@@ -94,6 +94,44 @@ def test_breakdown_steps_and_exactness(W, x, expected):
     assert rel_err(y, exact_filter(laplacian(W, "combinatorial"), f, x)) <= 1e-12
 
 
+SMALL_GRAPHS = {}
+
+
+@pytest.mark.parametrize("order", [8, 20])
+@pytest.mark.parametrize("width", [1, 3, 17, 64, 65, 255, 256])
+@pytest.mark.parametrize("N", [70, 257])
+def test_shared_thread_map_at_small_n(N, width, order):
+    """The column kernels' thread map (gspx_reduce.hip.h) under Lanczos where it changes behaviour: fewer rows than one
+    workgroup takes and a ragged last row group, ldp = 1 .. 256 (rstep = 1 at 255 and 256: k_lz_update's four-row tail
+    is ragged at both sizes), and at width 256 the dot pass of step 16 (16 x 256 = 4096 entries) switches sum_parts
+    from k_colsum to k_panel_sum_parts inside one order-20 run.  Against the numpy backend's basis."""
+    from lanczos_helpers import NumpyBackend
+    if N not in SMALL_GRAPHS:
+        W = random_graph(N, 4, seed=N)
+        SMALL_GRAPHS[N] = (W, laplacian(W, "combinatorial"))
+    W, L = SMALL_GRAPHS[N]
+    rng = np.random.default_rng(1000 * N + 10 * width + order)
+    x = rng.standard_normal((N, width))
+    if width > 2:
+        x[:, 1] = 0  # a zero column
+    Vr, ar, br, _, sr = NumpyBackend(L).krylov(x, 0, width, order, 0.0)
+    live = x.any(axis=0)
+    assert np.array_equal(sr, np.where(live, order, 0))
+    for perm in (rng.permutation(N).astype(np.int32), None):
+        dev = engine.DeviceGraph.from_w(W, dtype=np.float64, perm=perm)
+        V, alpha, beta, steps = dev.lanczos_basis(x, order)
+        again = dev.lanczos_basis(x, order)
+        dev.destroy()
+        assert V.shape == (N, order, width) and np.array_equal(steps, sr)
+        for c in np.flatnonzero(live):
+            assert rel_err(alpha[:, c], ar[:, c]) <= 1e-10 and rel_err(beta[:, c], br[:, c]) <= 1e-10, (c, perm is None)
+            Q = V[:, :, c]
+            assert np.max(np.abs(Q.T @ Q - np.eye(order))) <= 1e-12, (c, perm is None)
+        assert rel_err(V, np.moveaxis(Vr, 0, 1)) <= 1e-10
+        assert not V[:, :, ~live].any() and not alpha[:, ~live].any() and not beta[:, ~live].any()
+        assert all(np.asarray(a).tobytes() == np.asarray(b).tobytes() for a, b in zip((V, alpha, beta, steps), again))
+
+
 def test_repeated_calls_give_identical_bits():
     W = random_graph(50_000, 8, seed=9, hub=True)
     G = graphs.Graph(W, compute_dtype=np.float64)

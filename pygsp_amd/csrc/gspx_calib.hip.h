@@ -1,5 +1,7 @@
 // gspx_calib.hip.h - calibration kernel for graphs WITHOUT vertex locality (BASELINE configs 2 and 3):
-// the rate at which this chip serves random row gathers.  Included by gspx.hip.
+// the rate at which this chip serves random row gathers.  After it, the calibrations that run the engine's own code:
+// the copy and read ceilings, the access-mix ceiling (gspx_bench_step_mix) and the placement tuner.
+// After gspx_poly.hip.h (launch_permute_in, tile_geometry, check_filter_args, gspx_cheby_filter_dev).
 //
 // On an Erdos-Renyi or block-model graph every stored entry of L fetches one panel row through an L2 miss
 // (a 4 MB L2 against a 128-256 MB panel), so a recurrence step on such a graph is bound by
@@ -145,6 +147,20 @@ __global__ __launch_bounds__(256) void k_bench_streams(const u32x4* __restrict__
   if (NW == 0 && (acc.x ^ acc.y) == 0x9e3779b9u) sink[0] = acc.x;  // keeps the loads alive
 }
 
+// calibration: every workgroup streams the same `n4` float4s `passes` times (read-only), so the
+// data is served by whichever cache level holds `16*n4` bytes
+__global__ __launch_bounds__(256) void k_read_loop(const float4* __restrict__ p, size_t n4, int passes,
+                                                   float* __restrict__ sink) {
+  float acc = 0;
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (int r = 0; r < passes; ++r)
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+      const float4 v = p[i];
+      acc += v.x + v.y + v.z + v.w;
+    }
+  if (acc == 123456.789f) sink[0] = acc;  // keep the loads alive
+}
+
 }  // namespace gspx
 
 template <int NR>
@@ -262,4 +278,208 @@ extern "C" int gspx_bench_gather(gspx_ctx* ctx, int64_t panel_rows, int row_byte
   if (ms) *ms = per_launch;
   if (gbps) *gbps = (double)n * row_bytes / (per_launch * 1e-3) / 1e9;
   return GSPX_OK;
+}
+
+// calibration: streaming copy with the engine's own 16-byte-per-lane copy kernel (k_permute_in
+// without a permutation) - the measured HBM ceiling quoted beside every roofline fraction.
+extern "C" int gspx_bench_copy(gspx_ctx* ctx, int64_t bytes, int iters, double* gbps) {
+  if (!ctx || !gbps || bytes < 4096 || iters < 1)
+    return set_err(GSPX_ERR_INVALID, "gspx_bench_copy: bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  DevMem a, b;
+  CHK(a.alloc((size_t)bytes));
+  CHK(b.alloc((size_t)bytes));
+  const unsigned ld = 1024;  // floats per row
+  const int rows = (int)(bytes / (ld * sizeof(float)));
+  hipLaunchKernelGGL((k_fill<float>), dim3(4096), dim3(256), 0, ctx->stream, a.as<float>(),
+                     (size_t)rows * ld, 1.0f);
+  launch_permute_in<float>(a.as<float>(), ld, b.as<float>(), ld, rows, nullptr, 4, ctx->stream);
+  HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+  for (int i = 0; i < iters; ++i)
+    launch_permute_in<float>(a.as<float>(), ld, b.as<float>(), ld, rows, nullptr, 4, ctx->stream);
+  HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipGetLastError());
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+  *gbps = 2.0 * (double)rows * ld * sizeof(float) * iters / (ms * 1e-3) / 1e9;
+  return GSPX_OK;
+}
+
+// calibration: read-only bandwidth of a `bytes`-sized buffer streamed `passes` times inside one
+// launch (cache-level bandwidth as seen by the CUs)
+extern "C" int gspx_bench_read(gspx_ctx* ctx, int64_t bytes, int passes, double* gbps) {
+  if (!ctx || !gbps || bytes < 4096 || passes < 1)
+    return set_err(GSPX_ERR_INVALID, "gspx_bench_read: bad argument");
+  HIPCHK(hipSetDevice(ctx->device));
+  DevMem a, sink;
+  CHK(a.alloc((size_t)bytes));
+  CHK(sink.alloc(64));
+  const size_t n4 = (size_t)bytes / 16;
+  hipLaunchKernelGGL((k_fill<float>), dim3(4096), dim3(256), 0, ctx->stream, a.as<float>(), n4 * 4,
+                     1.0f);
+  const unsigned nb = (unsigned)std::min<size_t>((n4 + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_read_loop, dim3(nb), dim3(256), 0, ctx->stream, (const float4*)a.p, n4, 1,
+                     sink.as<float>());
+  HIPCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+  hipLaunchKernelGGL(k_read_loop, dim3(nb), dim3(256), 0, ctx->stream, (const float4*)a.p, n4,
+                     passes, sink.as<float>());
+  HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipGetLastError());
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+  *gbps = (double)n4 * 16.0 * passes / (ms * 1e-3) / 1e9;
+  return GSPX_OK;
+}
+
+// Calibration: the call gspx_cheby_filter_dev(g, lmax, 1, M, coeffs, Nsig, x, y, analysis) would make - the same
+// plan, the same K launches over the same buffers with the same flushes, sweeps and cache bits - with the row products
+// removed from every wide k_step_tile launch (mode 1; mode 2: the two barriers of a pass too).  y receives numbers
+// without meaning.  Times through gspx_last_timing like any filter call.  The mix ceiling of bench.py's roofline.
+extern "C" int gspx_bench_step_mix(gspx_graph* g, double lmax, int M, const double* coeffs, int64_t Nsig,
+                                   const void* x_dev, void* y_dev, int mode) {
+  if (!g || !g->ctx) return set_err(GSPX_ERR_INVALID, "gspx_bench_step_mix: null graph");
+  if (mode != 1 && mode != 2) return set_err(GSPX_ERR_INVALID, "gspx_bench_step_mix: mode must be 1 or 2");
+  gspx_ctx* ctx = g->ctx;
+  const bool wide = Nsig > 0 && Nsig < (1 << 20) && (size_t)Nsig * elt_size(g->dtype) > 128 &&
+                    (g->dtype == GSPX_F32 ? tile_geometry<float>(g, ctx->opt, (unsigned)Nsig)
+                                          : tile_geometry<double>(g, ctx->opt, (unsigned)Nsig));
+  if (!wide)
+    return set_err(GSPX_ERR_INVALID, "gspx_bench_step_mix: this call would not run the wide LDS-staged step "
+                                     "(gather tiles, rows of more than 128 bytes made of 16-byte pieces)");
+  replay_reset(ctx);
+  ctx->opt.calib_mix = mode;
+  const int rc = gspx_cheby_filter_dev(g, lmax, 1, M, coeffs, Nsig, x_dev, y_dev, GSPX_ANALYSIS, nullptr);
+  ctx->opt.calib_mix = 0;
+  replay_reset(ctx);
+  return rc;
+}
+
+// Placement tuning (round 6, profiles/r06_placement.md).  On MI355X the speed of the recurrence on panels beyond the
+// Infinity Cache depends on WHICH physical pages back the streamed workspaces: the same call, in one process on one GPU,
+// runs anywhere between 0.54 and 0.60 of 8 TB/s as the allocator hands out different pages - the "slow boxes" of rounds
+// 2 to 5 were partly boxes whose first allocation drew badly (and partly cards that are slow whatever they draw).
+// Relative shifts of the panels inside one allocation change nothing (256 B ... 16 MB, measured), so this is not
+// stream-against-stream channel aliasing that a layout rule could avoid; the remedy is to draw several times and keep
+// the best.  For `candidates` fresh backings of the two workspaces (the previous ones held meanwhile, so every draw
+// gets other pages) the caller's OWN call runs three times (a 7-launch stand-in on scratch panels ranked the candidates
+// wrongly: its spread was 2 %, the full call's 8 %); the fastest backing stays in the context, the others are
+// released.  out[i]: milliseconds per recurrence launch with candidate i (candidate 0 = the backing the context had,
+// or its first own draw; 0 for candidates never drawn because memory ran out), out[candidates] = index kept.
+// stride_mb > 0: a pad of that size is allocated and held before every further draw, so that the candidates sample the
+// card's memory at that stride - the speed classes come in zones of tens of GB in allocation order (tools/zone_map.py:
+// 0 - 60 GB mixed, 60 - 130 GB slow, 130 - 200 GB medium, 200 - 270 GB fast on one card), and a card whose first 12 GB
+// are slow may have its fast zone 200 GB in.  The pads are released with the losing candidates.
+extern "C" int gspx_ctx_tune_placement(gspx_graph* g, double lmax, int M, const double* coeffs, int64_t Nsig,
+                                       const void* x_dev, void* y_dev, int candidates, int64_t stride_mb, double* out) {
+  if (!g || !g->ctx || !out) return set_err(GSPX_ERR_INVALID, "gspx_ctx_tune_placement: null argument");
+  if (candidates < 1 || candidates > 32) return set_err(GSPX_ERR_INVALID, "gspx_ctx_tune_placement: 1 to 32 candidates");
+  if (stride_mb < 0 || stride_mb > ((int64_t)1 << 20))
+    return set_err(GSPX_ERR_INVALID, "gspx_ctx_tune_placement: stride_mb out of range");
+  CHK(check_filter_args(g, lmax, 1, M, coeffs, Nsig, x_dev, y_dev, GSPX_ANALYSIS));
+  for (int i = 0; i <= candidates; ++i) out[i] = 0.0;
+  gspx_ctx* ctx = g->ctx;
+  HIPCHK(hipSetDevice(ctx->device));
+  replay_reset(ctx);
+  std::vector<std::unique_ptr<DevMem>> held;  // losing candidates stay allocated until the end: no page is drawn twice
+  struct Pads {  // physical memory held without a mapping (hipMemCreate): occupies pages, costs no page-table work
+    std::vector<hipMemGenericAllocationHandle_t> h;
+    bool hold(size_t bytes, int device) {
+      hipMemAllocationProp prop = {};
+      prop.type = hipMemAllocationTypePinned;
+      prop.location.type = hipMemLocationTypeDevice;
+      prop.location.id = device;
+      size_t gran = 0;
+      if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || !gran) {
+        (void)hipGetLastError();
+        return false;
+      }
+      hipMemGenericAllocationHandle_t one;
+      if (hipMemCreate(&one, (bytes + gran - 1) / gran * gran, &prop, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+      }
+      h.push_back(one);
+      return true;
+    }
+    ~Pads() {
+      for (auto& one : h) (void)hipMemRelease(one);
+    }
+  } pads;
+  DevMem best_t, best_r;
+  double best_ms = 0;
+  int best = -1;
+  for (int i = 0; i < candidates; ++i) {
+    if (i > 0) {  // candidate 0 is what the context has (or draws now); later ones start from empty workspaces
+      DevMem t, r;
+      t.streamed = ctx->ws_t.streamed;
+      r.streamed = ctx->ws_r.streamed;
+      ctx->ws_t.swap(t);
+      ctx->ws_r.swap(r);
+      if (best == i - 1) {  // the previous candidate is the best so far: keep it aside
+        best_t.swap(t);
+        best_r.swap(r);
+      }
+      held.emplace_back(new DevMem());
+      held.back()->swap(t);  // (what best_t held before, or the loser itself)
+      held.emplace_back(new DevMem());
+      held.back()->swap(r);
+      if (stride_mb > 0) {  // a held pad moves the next draw `stride_mb` further along the allocator's order: the speed
+        bool ok = pads.hold((size_t)stride_mb << 20, ctx->device);  // classes come in zones of tens of GB
+        if (!ok) {  // (physical memory without a mapping is all a pad needs; a plain allocation if that API refuses)
+          held.emplace_back(new DevMem());
+          ok = held.back()->alloc((size_t)stride_mb << 20) == GSPX_OK;
+          if (!ok) held.pop_back();
+        }
+        if (!ok) {  // memory exhausted: the search ends here
+          ctx->ws_t.swap(best_t);  // (the live workspaces are empty at this point: the best so far goes back in)
+          ctx->ws_r.swap(best_r);
+          out[candidates] = (double)best;
+          replay_reset(ctx);
+          return GSPX_OK;
+        }
+      }
+    }
+    {  // room for a third panel in the candidate's T workspace, drawn from the same place: the Newton evaluation of the
+       // same call (evaluation='auto') keeps three panels there and would otherwise grow the winner by one panel from
+       // wherever the allocator stands after the search
+      const size_t panel = (size_t)g->N * (size_t)Nsig * elt_size(g->dtype);
+      if (panel < ((size_t)1 << 31) && ctx->ws_t.ensure(3 * panel + 256) != GSPX_OK && best >= 0) {
+        ctx->ws_t.swap(best_t);  // memory exhausted: the search ends here with the best so far
+        ctx->ws_r.swap(best_r);
+        out[candidates] = (double)best;
+        replay_reset(ctx);
+        return gspx_cheby_filter_dev(g, lmax, 1, M, coeffs, Nsig, x_dev, y_dev, GSPX_ANALYSIS, nullptr);
+      }
+    }
+    double ms = 0;
+    for (int rep = 0; rep < 3; ++rep) {  // the caller's own call: the first run allocates, the best of the next two counts
+      const int rc = gspx_cheby_filter_dev(g, lmax, 1, M, coeffs, Nsig, x_dev, y_dev, GSPX_ANALYSIS, nullptr);
+      if (rc != GSPX_OK) {
+        if (best >= 0 && best != i) {  // put the best backing found so far in place
+          ctx->ws_t.swap(best_t);
+          ctx->ws_r.swap(best_r);
+        }
+        if (rc == GSPX_ERR_OOM && best >= 0) {  // a deep candidate that did not fit: the search ends, not the call
+          out[candidates] = (double)best;
+          replay_reset(ctx);
+          return gspx_cheby_filter_dev(g, lmax, 1, M, coeffs, Nsig, x_dev, y_dev, GSPX_ANALYSIS, nullptr);
+        }
+        return rc;
+      }
+      const double t = ctx->timing[1] / std::max(ctx->timing[2], 1.0);
+      if (rep == 1 || (rep == 2 && t < ms)) ms = t;
+      replay_reset(ctx);
+    }
+    out[i] = ms;
+    if (best < 0 || ms < best_ms) best_ms = ms, best = i;
+  }
+  if (best != candidates - 1) {  // the live workspaces hold the last candidate: exchange it for the best
+    ctx->ws_t.swap(best_t);
+    ctx->ws_r.swap(best_r);
+  }
+  out[candidates] = (double)best;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return GSPX_OK;  // (held and best_t / best_r - now the losers - are released here; y holds the call's result)
 }

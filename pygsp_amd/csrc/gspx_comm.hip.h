@@ -1,5 +1,5 @@
 // gspx_comm.hip.h - the path's one collective inside the library: the gather of the ranks' outputs to a
-// root over RCCL (xGMI), SURVEY.md 8(b)/(e).  Included by gspx.hip.
+// root over RCCL (xGMI), SURVEY.md 8(b)/(e).  After gspx_ctx.hip.h (gspx_ctx, gspx_buf).
 //
 // The recurrence itself never communicates (independent graphs / signal columns per GPU); only the final
 // outputs travel.  Two forms:
@@ -347,5 +347,66 @@ extern "C" int gspx_comm_info(gspx_comm* h, int64_t out[3]) {
   if (R->CommUserRank) RCCLCHK(R->CommUserRank(h->comm, &rk));
   out[1] = cnt;
   out[2] = rk;
+  return GSPX_OK;
+}
+
+// The path's one collective in single-process form: every part (a buffer on its own context /
+// device) lands in root_out, one after the other in argument order.  Between devices the blocks travel
+// as grouped RCCL send / recv pairs (gather_rccl above), each over its own xGMI link.  If RCCL
+// cannot be loaded or refuses the device set, the same gather is done with peer copies: each queued on
+// the SOURCE context's stream (hipMemcpyPeerAsync, DMA engines); same-device parts are device copies.
+extern "C" int gspx_gather(gspx_ctx** ctxs, int n, gspx_buf** parts, gspx_buf* root_out) {
+  if (n < 0 || (n > 0 && !parts) || !root_out)
+    return set_err(GSPX_ERR_INVALID, "gspx_gather: bad argument");
+  int64_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!parts[i]) return set_err(GSPX_ERR_INVALID, "gspx_gather: null part");
+    if (ctxs && ctxs[i] && ctxs[i] != parts[i]->ctx)
+      return set_err(GSPX_ERR_INVALID, "gspx_gather: part %d does not belong to context %d", i, i);
+    if (parts[i] == root_out) return set_err(GSPX_ERR_INVALID, "gspx_gather: a part aliases the output");
+    total += parts[i]->bytes;
+  }
+  if (total > root_out->bytes)
+    return set_err(GSPX_ERR_INVALID, "gspx_gather: output holds %lld bytes, parts add up to %lld",
+                   (long long)root_out->bytes, (long long)total);
+  gspx_ctx* root = root_out->ctx;
+  if (root->opt.gather_rccl > 0) {
+    bool multi = false;
+    for (int i = 0; i < n; ++i) multi |= parts[i]->ctx->device != root->device;
+    if (multi || root->opt.gather_rccl == 2) {
+      if (gather_rccl(n, parts, root_out, root->opt.gather_rccl == 2) == GSPX_OK) return GSPX_OK;
+      if (root->opt.gather_rccl == 2) return GSPX_ERR_HIP;  // asked for RCCL explicitly: report why not
+      (void)hipGetLastError();  // otherwise: peer copies below
+    }
+  }
+  HIPCHK(hipSetDevice(root->device));
+  HIPCHK(hipStreamSynchronize(root->stream));  // earlier work on the output buffer
+  int64_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    gspx_ctx* src = parts[i]->ctx;
+    const size_t nb = (size_t)parts[i]->bytes;
+    if (nb) {
+      HIPCHK(hipSetDevice(src->device));
+      unsigned char* dst = (unsigned char*)root_out->mem.p + off;
+      if (src->device == root->device) {
+        HIPCHK(hipMemcpyAsync(dst, parts[i]->mem.p, nb, hipMemcpyDeviceToDevice, src->stream));
+      } else {
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, src->device, root->device) == hipSuccess && can) {
+          const hipError_t e = hipDeviceEnablePeerAccess(root->device, 0);
+          if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
+            return set_err(GSPX_ERR_HIP, "hipDeviceEnablePeerAccess: %s", hipGetErrorString(e));
+          (void)hipGetLastError();
+        }
+        HIPCHK(hipMemcpyPeerAsync(dst, root->device, parts[i]->mem.p, src->device, nb, src->stream));
+      }
+    }
+    off += parts[i]->bytes;
+  }
+  for (int i = 0; i < n; ++i) {
+    HIPCHK(hipSetDevice(parts[i]->ctx->device));
+    HIPCHK(hipStreamSynchronize(parts[i]->ctx->stream));
+  }
+  HIPCHK(hipSetDevice(root->device));
   return GSPX_OK;
 }

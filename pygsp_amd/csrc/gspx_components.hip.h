@@ -1,4 +1,4 @@
-// gspx_components.hip.h - connected components of a gspx_graph, labelled on the device.  Included by gspx.hip.
+// gspx_components.hip.h - connected components of a gspx_graph, labelled on the device.  After gspx_graph.hip.h.
 //
 // What Graph.is_connected / Graph.extract_components of the reference (pygsp/graphs/graph.py:294-366, 444-508: a
 // Python depth-first search that slices one sparse row per vertex) and scipy.sparse.csgraph.connected_components

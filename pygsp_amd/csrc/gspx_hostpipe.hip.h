@@ -1,5 +1,6 @@
 // gspx_hostpipe.hip.h - the host-pointer entry points (gspx_cheby_filter, gspx_poly_program, gspx_newton_filter) as a
-// five-stage pipeline over signal-column batches.  Included by gspx.hip; its host_call decides which calls take it.
+// five-stage pipeline over signal-column batches.  After gspx_ctx.hip.h, before gspx_poly.hip.h, whose host_call decides
+// which calls take it.
 //
 // What a plugin-mode caller of pygsp/filters/filter.py:146-328 hands over is pageable numpy memory: round 2
 // copied the whole input (pageable hipMemcpyAsync: the runtime stages it on one thread), ran the kernels,
@@ -28,7 +29,7 @@
 #include <thread>
 
 // (PinMem and HostPipe - the pinned staging buffers, streams and events a context keeps for this - are defined
-// in gspx.hip next to the context itself)
+// in gspx_mem.hip.h)
 
 // rows [r0, r1) of a strided column block <-> a compact panel; `rb` bytes per row piece
 static inline void copy_rows(unsigned char* dst, size_t dpitch, const unsigned char* src, size_t spitch, size_t rb,
@@ -315,4 +316,26 @@ static void host_pipeline_shape(const Options& opt, size_t elt, int64_t N, int64
     t = (int)std::min<unsigned>(16, std::max<unsigned>(1, hc / 4));
   }
   *threads_out = std::min(t, 64);
+}
+
+// host-only: the column batches and thread count the pipelined host-pointer call would use (for schedule tests)
+extern "C" int gspx_host_pipeline_describe(int mode, int64_t host_batch, int64_t host_edge, int64_t host_threads,
+                                           int dtype, int64_t N, int64_t Nsig, int planes_total, int64_t* widths,
+                                           int capacity, int* n_batches, int* threads) {
+  if (!n_batches || N < 0 || Nsig < 0 || planes_total < 1 || (dtype != GSPX_F32 && dtype != GSPX_F64))
+    return set_err(GSPX_ERR_INVALID, "bad argument");
+  Options opt;
+  opt.host_pipeline = mode;
+  opt.host_batch = host_batch;
+  opt.host_edge = host_edge;
+  opt.host_threads = host_threads;
+  std::vector<int64_t> w;
+  int t = 1;
+  host_pipeline_shape(opt, elt_size(dtype), N, Nsig, planes_total, &w, &t);
+  if (w.size() < 2) w.clear();  // (a single batch is the one-shot form)
+  *n_batches = (int)w.size();
+  if (threads) *threads = t;
+  if (widths)
+    for (int i = 0; i < capacity && i < (int)w.size(); ++i) widths[i] = w[(size_t)i];
+  return GSPX_OK;
 }

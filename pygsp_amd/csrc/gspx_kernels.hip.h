@@ -722,7 +722,7 @@ __global__ __launch_bounds__(256) void k_step_lds(const int* __restrict__ rowptr
 }
 
 // ---------------------------------------------------------------------------------------------
-// Row products from LDS (k_step_tile; the two-level experimental kernels under experimental/ use it too)
+// Row products from LDS (k_step_tile)
 // ---------------------------------------------------------------------------------------------
 typedef unsigned short u16;
 typedef unsigned char u8;
@@ -1005,389 +1005,10 @@ __global__ __launch_bounds__(256) void k_permute_out_pad(const T* __restrict__ r
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// graph build kernels (replace graph.py:618-628, 830-838)
-// ---------------------------------------------------------------------------------------------
-// dw[i] = sum_j W_ij, sequential in ascending column order: for an exactly symmetric W this is
-// the same addition order as scipy's column sums W.sum(axis=0) (graph.py:833).
-template <typename T>
-__global__ void k_degree(const int* __restrict__ ptr, const T* __restrict__ val, int N,
-                         T* __restrict__ dw) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  T s = 0;
-  for (int j = ptr[i]; j < ptr[i + 1]; ++j) s += val[j];
-  dw[i] = s;
-}
-
-// The ingredients of Graph._get_upper_bound (graph.py:933-960) in one pass over W, per 256-row block:
-// part[4 b + 0..3] = max W_ij, max (dw_i + dw_j) over stored entries, max (dw_i + (W dw)_i / dw_i), number of
-// zero-degree rows (their 0 / 0 makes numpy's maximum NaN: the host layer then drops that candidate, as
-// Python's min() does).  The row sums run in column order without fused multiply-add, like scipy's W.dot(dw).
-__global__ __launch_bounds__(256) void k_lmax_bounds(const int* __restrict__ ptr, const int* __restrict__ col,
-                                                     const double* __restrict__ val, const double* __restrict__ dw,
-                                                     int N, double* __restrict__ part) {
-#pragma clang fp contract(off)
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  double wmax = -1e300, emax = -1e300, mmax = -1e300, zero = 0;
-  if (i < N) {
-    const double di = dw[i];
-    double s = 0;
-    for (int j = ptr[i]; j < ptr[i + 1]; ++j) {
-      const double w = val[j], dj = dw[col[j]];
-      const double p = w * dj;
-      s = s + p;
-      wmax = fmax(wmax, w);
-      emax = fmax(emax, di + dj);
-    }
-    if (di == 0.0) zero = 1;
-    else mmax = di + s / di;
-  }
-  __shared__ double sh[4][4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    wmax = fmax(wmax, __shfl_down(wmax, off));
-    emax = fmax(emax, __shfl_down(emax, off));
-    mmax = fmax(mmax, __shfl_down(mmax, off));
-    zero += __shfl_down(zero, off);
-  }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sh[wv][0] = wmax;
-    sh[wv][1] = emax;
-    sh[wv][2] = mmax;
-    sh[wv][3] = zero;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double* o = part + (size_t)blockIdx.x * 4;
-    o[0] = fmax(fmax(sh[0][0], sh[1][0]), fmax(sh[2][0], sh[3][0]));
-    o[1] = fmax(fmax(sh[0][1], sh[1][1]), fmax(sh[2][1], sh[3][1]));
-    o[2] = fmax(fmax(sh[0][2], sh[1][2]), fmax(sh[2][2], sh[3][2]));
-    o[3] = sh[0][3] + sh[1][3] + sh[2][3] + sh[3][3];
-  }
-}
-
-// d^{-1/2} with the reference's isolated-vertex rule (graph.py:622-624)
-template <typename T> __device__ __forceinline__ T inv_sqrt_deg(T dw) {
-  return dw == T(0) ? T(0) : T(1) / sqrt(dw);
-}
-
-// value of L_ij for an off-diagonal stored W_ij
-template <typename T>
-__device__ __forceinline__ T lap_offdiag(int lap_type, T w, T di, T dj) {
-  if (lap_type == 0) return -w;
-  return -((di * w) * dj);  // (D*W)*D, graph.py:626
-}
-// value of L_ii given dw_i and the (possibly absent) self-loop weight
-template <typename T> __device__ __forceinline__ T lap_diag(int lap_type, T dw, T wii, T di) {
-  if (lap_type == 0) return dw - wii;
-  if (dw == T(0)) return T(0);   // L[disconnected, disconnected] = 0, graph.py:627
-  return T(1) - (di * wii) * di;
-}
-
-// pass 1 (count) / pass 2 (fill) of canonical L = D - W  or  I - D^-1/2 W D^-1/2, zeros dropped
-template <typename T, bool FILL>
-__global__ void k_lap_build(const int* __restrict__ wptr, const int* __restrict__ wcol,
-                            const T* __restrict__ wval, const T* __restrict__ dw, int N,
-                            int lap_type, int* __restrict__ cnt, const int* __restrict__ lptr,
-                            int* __restrict__ lcol, T* __restrict__ lval) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const T dwi = dw[i];
-  const T di = lap_type == 1 ? inv_sqrt_deg(dwi) : T(0);
-  // self loop weight
-  T wii = 0;
-  for (int j = wptr[i]; j < wptr[i + 1]; ++j)
-    if (wcol[j] == i) wii = wval[j];
-  const T dval = lap_diag(lap_type, dwi, wii, di);
-  int n = 0;
-  int o = FILL ? lptr[i] : 0;
-  bool diag_done = false;
-  for (int j = wptr[i]; j < wptr[i + 1]; ++j) {
-    const int c = wcol[j];
-    if (c == i) continue;
-    if (!diag_done && c > i) {
-      diag_done = true;
-      if (dval != T(0)) {
-        if (FILL) { lcol[o] = i; lval[o] = dval; ++o; }
-        ++n;
-      }
-    }
-    const T dj = lap_type == 1 ? inv_sqrt_deg(dw[c]) : T(0);
-    const T v = lap_offdiag(lap_type, wval[j], di, dj);
-    if (v != T(0)) {
-      if (FILL) { lcol[o] = c; lval[o] = v; ++o; }
-      ++n;
-    }
-  }
-  if (!diag_done && dval != T(0)) {
-    if (FILL) { lcol[o] = i; lval[o] = dval; ++o; }
-    ++n;
-  }
-  if (!FILL) cnt[i] = n;
-}
-
-__global__ void k_inverse_perm(const int* __restrict__ perm, int N, int* __restrict__ iperm) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) iperm[perm[i]] = i;
-}
-
-// canonical L -> internal padded CSR.  pass 1: padded row lengths; pass 2: fill.
-template <typename T, bool FILL>
-__global__ void k_internal_build(const int* __restrict__ lptr, const int* __restrict__ lcol,
-                                 const T* __restrict__ lval, int N,
-                                 const int* __restrict__ perm, const int* __restrict__ iperm,
-                                 int* __restrict__ cnt, int* __restrict__ rptr,
-                                 int* __restrict__ rcol, T* __restrict__ rval) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;  // internal row
-  if (i >= N) return;
-  const int old = perm ? perm[i] : i;
-  const int s = lptr[old], e = lptr[old + 1];
-  bool has_diag = false;
-  for (int j = s; j < e; ++j)
-    if (lcol[j] == old) { has_diag = true; break; }
-  const int n = (e - s) + (has_diag ? 0 : 1);
-  const int npad = (n + 3) & ~3;
-  if (!FILL) {
-    cnt[i] = npad;
-    return;
-  }
-  const int o = rptr[i];  // multiple of 4 (every row length is)
-  rptr[i] = o | (npad - n);  // low 2 bits: number of pad entries closing this row
-  // Rows of at most CAP entries (all but hubs): read once into registers, every entry's final position - the
-  // diagonal first, the others by ascending internal column - is its rank among the row's entries (CAP^2 predicated
-  // compares on registers), written once.  (The insertion sort in global memory below cost 5.2 GB of traffic for
-  // 130 MB of matrix at N = 1M: profiles/r04_setup_hostpipe_rocprofv3_summary.txt.)
-  constexpr int CAP = sizeof(T) == 8 ? 24 : 32;  // (32 doubles + 32 columns would spill at the default register bound)
-  if (n <= CAP) {
-    int cc[CAP];
-    T vv[CAP];
-    const int len = e - s;
-#pragma unroll
-    for (int p = 0; p < CAP; ++p) {
-      const bool in = p < len;
-      const int c = in ? lcol[s + p] : 0;
-      cc[p] = in ? (iperm ? iperm[c] : c) : (p == len && !has_diag ? i : 0x7FFFFFFF);
-      vv[p] = in ? lval[s + p] : T(0);
-    }
-#pragma unroll
-    for (int p = 0; p < CAP; ++p) {
-      if (p < n) {
-        int pos = 0;
-        if (cc[p] != i) {
-          pos = 1;
-#pragma unroll
-          for (int q = 0; q < CAP; ++q) pos += (q < n && cc[q] != i && cc[q] < cc[p]) ? 1 : 0;
-        }
-        rcol[o + pos] = cc[p];
-        rval[o + pos] = vv[p];
-      }
-    }
-    for (int m2 = n; m2 < npad; ++m2) {
-      rcol[o + m2] = N;  // out-of-range sentinel: the gather's bounds check returns 0
-      rval[o + m2] = T(0);
-    }
-    return;
-  }
-  int m = 0;
-  for (int j = s; j < e; ++j) {
-    rcol[o + m] = iperm ? iperm[lcol[j]] : lcol[j];
-    rval[o + m] = lval[j];
-    ++m;
-  }
-  if (!has_diag) {
-    rcol[o + m] = i;
-    rval[o + m] = T(0);
-    ++m;
-  }
-  // keep short rows sorted by (internal) column: neighbouring gathers stay adjacent
-  if ((perm || !has_diag) && m <= 128) {
-    for (int p = 1; p < m; ++p) {
-      const int c = rcol[o + p];
-      const T v = rval[o + p];
-      int q = p - 1;
-      while (q >= 0 && rcol[o + q] > c) {
-        rcol[o + q + 1] = rcol[o + q];
-        rval[o + q + 1] = rval[o + q];
-        --q;
-      }
-      rcol[o + q + 1] = c;
-      rval[o + q + 1] = v;
-    }
-  }
-  // the diagonal slot becomes entry 0 of the row: the step kernels take T_{k-1}[row] from that
-  // gather instead of loading it again (flush and Newton-form steps)
-  {
-    int p = 0;
-    while (p < m && rcol[o + p] != i) ++p;
-    const T dv = rval[o + p];
-    if (m <= 128) {
-      for (int q = p; q > 0; --q) {  // keep the rest sorted
-        rcol[o + q] = rcol[o + q - 1];
-        rval[o + q] = rval[o + q - 1];
-      }
-    } else {
-      rcol[o + p] = rcol[o];
-      rval[o + p] = rval[o];
-    }
-    rcol[o] = i;
-    rval[o] = dv;
-  }
-  for (; m < npad; ++m) {
-    rcol[o + m] = N;  // out-of-range sentinel: the gather's bounds check returns 0
-    rval[o + m] = T(0);
-  }
-}
-
-// F = (2/a1) * (L - a2 I) on the internal layout (approximations.py:105)
-template <typename T>
-__global__ void k_factor(const int* __restrict__ rptr, const int* __restrict__ rcol,
-                         const T* __restrict__ rval, int N, T two_over_a1, T a2,
-                         T* __restrict__ fval) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  for (int j = rptr[i] & ~3; j < (rptr[i + 1] & ~3); ++j) {
-    const int c = rcol[j];
-    T v = rval[j];
-    if (c == i) v -= a2;
-    fval[j] = (c == N) ? T(0) : two_over_a1 * v;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// small vector kernels for the device Lanczos estimate of lambda_max (graph.py:907-920)
-// ---------------------------------------------------------------------------------------------
-// partial[b] = sum over the block's grid-stride elements of x*y (double accumulation)
-template <typename T>
-__global__ __launch_bounds__(256) void k_dot_partial(const T* __restrict__ x, const T* __restrict__ y,
-                                                     size_t n, double* __restrict__ partial) {
-  __shared__ double ws[4];
-  double acc = 0;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-    acc += (double)x[i] * (double)y[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-// out[0] = sum(partial[0..n)) in a fixed order (deterministic)
-__global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__ partial, int n,
-                                                      double* __restrict__ out) {
-  __shared__ double ws[4];
-  double acc = 0;
-  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-// y = a*x + b*y
-template <typename T>
-__global__ void k_axpby(T a, const T* __restrict__ x, T b, T* __restrict__ y, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x)
-    y[i] = a * x[i] + b * y[i];
-}
-// deterministic start vector: a fixed hash of the index mapped to [-1, 1)
-template <typename T> __global__ void k_start_vector(T* v, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (size_t)gridDim.x * blockDim.x) {
-    unsigned h = (unsigned)i * 2654435761u;
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    v[i] = (T)((double)h / 2147483648.0 - 1.0);
-  }
-}
-
-// calibration: every workgroup streams the same `n4` float4s `passes` times (read-only), so the
-// data is served by whichever cache level holds `16*n4` bytes
-__global__ __launch_bounds__(256) void k_read_loop(const float4* __restrict__ p, size_t n4, int passes,
-                                                   float* __restrict__ sink) {
-  float acc = 0;
-  const size_t stride = (size_t)gridDim.x * 256;
-  for (int r = 0; r < passes; ++r)
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-      const float4 v = p[i];
-      acc += v.x + v.y + v.z + v.w;
-    }
-  if (acc == 123456.789f) sink[0] = acc;  // keep the loads alive
-}
-
 template <typename T> __global__ void k_fill(T* p, size_t n, T v) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (size_t)gridDim.x * blockDim.x)
     p[i] = v;
-}
-
-// ---------------------------------------------------------------------------------------------
-// exclusive scan of int32 (three small kernels; tile = 1024 elements)
-// ---------------------------------------------------------------------------------------------
-#define GSPX_SCAN_TILE 1024
-// (in and out may be the same array - radix_argsort scans its histogram in place: every thread reads its four
-// inputs before it writes its four outputs, and no thread touches another's - so neither is __restrict__)
-__global__ __launch_bounds__(256) void k_scan_tiles(const int* in, int n, int* out, int* __restrict__ tile_sums) {
-  __shared__ int wsum[4];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int base = blockIdx.x * GSPX_SCAN_TILE + t * 4;
-  int v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = (base + k < n) ? in[base + k] : 0;
-  const int mine = v[0] + v[1] + v[2] + v[3];
-  int incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(incl, off);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) wsum[wv] = incl;
-  __syncthreads();
-  int wbase = 0;
-  for (int k = 0; k < wv; ++k) wbase += wsum[k];
-  int run = wbase + incl - mine;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (base + k < n) out[base + k] = run;
-    run += v[k];
-  }
-  if (t == 255) tile_sums[blockIdx.x] = wbase + incl;
-}
-
-__global__ __launch_bounds__(256) void k_scan_sums(int* tile_sums, int ntiles) {
-  // single workgroup: serial over 256-element strips with a carry
-  __shared__ int wsum[4];
-  __shared__ int carry_s;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  if (t == 0) carry_s = 0;
-  __syncthreads();
-  for (int base = 0; base < ntiles; base += 256) {
-    const int i = base + t;
-    const int mine = i < ntiles ? tile_sums[i] : 0;
-    int incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    int wbase = carry_s;
-    for (int k = 0; k < wv; ++k) wbase += wsum[k];
-    if (i < ntiles) tile_sums[i] = wbase + incl - mine;
-    __syncthreads();
-    if (t == 255) carry_s = wbase + incl;
-    __syncthreads();
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scan_add(int* __restrict__ out, int n,
-                                                  const int* __restrict__ tile_sums) {
-  const int add = tile_sums[blockIdx.x];
-  const int base = blockIdx.x * GSPX_SCAN_TILE + threadIdx.x * 4;
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (base + k < n) out[base + k] += add;
 }
 
 }  // namespace gspx

@@ -1,5 +1,5 @@
 // gspx_knn.hip.h - k-nearest-neighbour graph construction on the device.
-// Included at the end of gspx.hip.  gfx950 only.
+// After gspx_graph.hip.h (scan_exclusive).  gfx950 only.
 //
 // Replaces, for NNtype='knn' (1 <= d <= 3 by the grid search below; 4 <= d <= 64 by the tiled brute force on the
 // matrix cores of gspx_knn_bf.hip.h; the weights / symmetrisation / CSR stages are shared):
@@ -433,7 +433,6 @@ struct gspx_knn {
 
 #include "gspx_knn_bf.hip.h"
 
-
 template <int KMAX>
 static void launch_knn_query(const double* sorted, const int* order, const int* start, int N,
                              const KnnGrid& g, int k, int* nn, double* dist, hipStream_t st) {
@@ -768,8 +767,6 @@ __global__ void k_sbm_fill(const int* __restrict__ er, const int* __restrict__ e
 
 }  // namespace gspx
 
-extern "C" int gspx_sbm_build_ex(gspx_ctx* ctx, int64_t N, int k, const int32_t* order, const int64_t* bounds,
-                                 const double* M, uint64_t seed, int flags, gspx_knn** out);
 extern "C" int gspx_sbm_build(gspx_ctx* ctx, int64_t N, int k, const int32_t* order, const int64_t* bounds,
                               const double* M, uint64_t seed, gspx_knn** out) {
   return gspx_sbm_build_ex(ctx, N, k, order, bounds, M, seed, 0, out);

@@ -16,7 +16,7 @@
 // "Lanczos filtering": why one pass is enough after the three-term subtraction).  alpha, beta, the dots and the
 // per-column active flags stay on the device: the loop does not synchronise with the host until it ends.
 // Every reduction is per workgroup into partials (block_colsum), then a fixed-order second pass (sum_parts), both
-// from gspx_reduce.hip.h: no atomics, the same bits on every call.  Included at the end of gspx.hip (after
+// from gspx_reduce.hip.h: no atomics, the same bits on every call.  After gspx_poly.hip.h (and
 // gspx_ops.hip.h, which brings gspx_reduce.hip.h).
 #pragma once
 

@@ -21,7 +21,7 @@
 //   spmm_internal  L X_k, the engine's product
 // After the done flag is set every step and rule launch returns at once: the host polls the flag every few
 // launches, and what it launches past the stop changes nothing.  Partial sums have one order for a given N and C:
-// the same inputs give the same bits on every call.  Included at the end of gspx.hip.
+// the same inputs give the same bits on every call.  After gspx_ops.hip.h.
 #pragma once
 
 namespace gspx {

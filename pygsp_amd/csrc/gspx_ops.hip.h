@@ -1,12 +1,10 @@
 // gspx_ops.hip.h - host side of the operators that reuse the engine's CSR.
-// Included at the end of gspx.hip (uses its helpers).  All entry points take DEVICE pointers to
+// After gspx_poly.hip.h (tile_usable, launch_step_tile, choose_shape, launch_step).  All entry points take DEVICE pointers to
 // row-major N x Nsig panels of the graph's compute dtype, in the caller's vertex order.
 #pragma once
 
 #include "gspx_reduce.hip.h"
 #include "gspx_ops_kernels.hip.h"
-
-// byte offsets col*ld*sizeof(T) for this panel width (LDS / wave-row kernels), cached on the graph
 
 // out = scale * (vals . cur) + beta * cur on internal-order panels (one launch of the step kernel);
 // with y != null the result goes to y in the caller's order instead (rows y[perm[i]])
@@ -489,4 +487,76 @@ extern "C" int gspx_grad_dev(gspx_graph* g, int64_t Nsig, const void* x_dev, voi
 extern "C" int gspx_div_dev(gspx_graph* g, int64_t Nsig, const void* y_dev, void* z_dev,
                             double* kernel_ms) {
   return grad_div(g, true, Nsig, y_dev, z_dev, kernel_ms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// panel primitives of the host layer
+// ------------------------------------------------------------------------------------------------
+// Columns [j0, j0 + w) of the N x N identity as a row-major N x w panel, written on the device: the
+// input of Filter.compute_frame (filter.py:593-600 filters np.identity(N)) without an N x N host array or
+// its trip over PCIe.
+template <typename T> __global__ void k_identity_panel(T* __restrict__ out, int N, int j0, int w) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)N * w) return;
+  const int row = (int)(i / w), col = (int)(i % w);
+  out[i] = row == j0 + col ? T(1) : T(0);
+}
+
+extern "C" int gspx_identity_panel_dev(gspx_ctx* ctx, int dtype, int64_t N, int64_t j0, int64_t w, void* out_dev) {
+  if (!ctx || N < 0 || j0 < 0 || w < 0 || j0 + w > N || (dtype != GSPX_F32 && dtype != GSPX_F64))
+    return set_err(GSPX_ERR_INVALID, "gspx_identity_panel_dev: bad argument");
+  if (N * w == 0) return GSPX_OK;
+  if (!out_dev) return set_err(GSPX_ERR_INVALID, "gspx_identity_panel_dev: null output");
+  if (N >= ((int64_t)1 << 31) || w >= ((int64_t)1 << 31))
+    return set_err(GSPX_ERR_INVALID, "gspx_identity_panel_dev: panel too large");
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t total = (size_t)N * (size_t)w;
+  const unsigned nb = (unsigned)((total + 255) / 256);
+  if (dtype == GSPX_F32)
+    hipLaunchKernelGGL((k_identity_panel<float>), dim3(nb), dim3(256), 0, ctx->stream, (float*)out_dev, (int)N,
+                       (int)j0, (int)w);
+  else
+    hipLaunchKernelGGL((k_identity_panel<double>), dim3(nb), dim3(256), 0, ctx->stream, (double*)out_dev, (int)N,
+                       (int)j0, (int)w);
+  HIPCHK(hipGetLastError());
+  return GSPX_OK;
+}
+
+// (vertex, signal, feature) tensor <-> feature planes [feature][vertex][signal]: the two layouts a signal cube
+// has on either side of Filter.filter (filter.py:310-311, 315-316) - for device-resident arrays that arrive in
+// the "wrong" one (an (N, Nf) panel of Nf signals read as one signal with Nf features, filter.py:270-278).
+// One thread per element of the planes side, whose accesses are the coalesced ones; the cube side of a vertex
+// is S * F contiguous elements, so its lines are shared by neighbouring lanes.
+template <typename T>
+__global__ void k_planes_pack(const T* __restrict__ src, T* __restrict__ dst, int64_t N, int S, int F, int to_planes) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // index in [f][n][s]
+  if (i >= N * S * F) return;
+  const int s = (int)(i % S);
+  const int64_t n = (i / S) % N;
+  const int f = (int)(i / ((int64_t)S * N));
+  const int64_t cube = (n * S + s) * F + f;
+  if (to_planes) dst[i] = src[cube];
+  else dst[cube] = src[i];
+}
+
+extern "C" int gspx_planes_pack_dev(gspx_ctx* ctx, int dtype, int64_t N, int64_t S, int64_t F, const void* src_dev,
+                                    void* dst_dev, int to_planes) {
+  if (!ctx || N < 0 || S < 0 || F < 0 || (dtype != GSPX_F32 && dtype != GSPX_F64))
+    return set_err(GSPX_ERR_INVALID, "gspx_planes_pack_dev: bad argument");
+  if (N * S * F == 0) return GSPX_OK;
+  if (!src_dev || !dst_dev || src_dev == dst_dev)
+    return set_err(GSPX_ERR_INVALID, "gspx_planes_pack_dev: null or aliased buffers");
+  if (S >= ((int64_t)1 << 31) || F >= ((int64_t)1 << 31) || N * S * F >= ((int64_t)1 << 40))
+    return set_err(GSPX_ERR_INVALID, "gspx_planes_pack_dev: tensor too large");
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t total = N * S * F;
+  const unsigned nb = (unsigned)((total + 255) / 256);
+  if (dtype == GSPX_F32)
+    hipLaunchKernelGGL((k_planes_pack<float>), dim3(nb), dim3(256), 0, ctx->stream, (const float*)src_dev,
+                       (float*)dst_dev, N, (int)S, (int)F, to_planes);
+  else
+    hipLaunchKernelGGL((k_planes_pack<double>), dim3(nb), dim3(256), 0, ctx->stream, (const double*)src_dev,
+                       (double*)dst_dev, N, (int)S, (int)F, to_planes);
+  HIPCHK(hipGetLastError());
+  return GSPX_OK;
 }

@@ -2,7 +2,7 @@
 // column sum, one second pass over workgroup partials, one Gram kernel on the matrix cores.  Every reduction is per
 // workgroup (or per wave) into partials, then a fixed-order second pass: no atomics, the same bits on every call -
 // for all callers, because there is one definition of each piece.  gfx950 only.
-// Included by gspx_ops.hip.h at the end of gspx.hip (the host helpers use gspx.hip's: gspx_ctx, DevMem, HIPCHK, CHK).
+// Included by gspx_ops.hip.h (the host helpers use gspx_ctx, DevMem, HIPCHK, CHK).
 //
 // The shared thread map of the column kernels (k_coldot_partial, k_cg_xr_dot, k_lz_three, k_lz_dots, k_lz_update):
 // a 256-thread workgroup over a row-major N x ld panel, ldp = ld rounded up to a power of two (col_pow2, <= 256),

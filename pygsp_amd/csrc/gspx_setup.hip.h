@@ -1,4 +1,4 @@
-// gspx_setup.hip.h - graph set-up in ONE call, on the device.  Included by gspx.hip.
+// gspx_setup.hip.h - graph set-up in ONE call, on the device.  After gspx_knn.hip.h.
 //
 // What pygsp/graphs/graph.py:98-176 + 510-630 do to a weight matrix before the first filter call - the checks
 // of Graph.__init__ (NaN / inf, self-loops, negative weights, graph.py:108-134), the directedness test

@@ -8,7 +8,7 @@
 // Panels are row-major device arrays with an explicit leading dimension (elements), any N >= 0, widths 1..512.
 // Gram and combine run on the matrix cores (v_mfma_f64_16x16x4f64).  The Gram kernel and the second pass of every
 // reduction are gspx_reduce.hip.h's (launch_panel_gram, sum_parts): no atomics, the same bits on every call.
-// Included at the end of gspx.hip (uses its helpers and gspx_reduce.hip.h).
+// After gspx_ops.hip.h (which brings gspx_reduce.hip.h).
 #pragma once
 
 namespace gspx {

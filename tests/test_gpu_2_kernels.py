@@ -1,6 +1,9 @@
 """Row a6 in depth: every kernel variant, panel width, schedule (fused flush / deferred combine),
 batching, hipGraph replay, in-place input, hubs and tiny graphs of cheby_op (approximations.py:58-114)
 against the oracle; the plugin seam on a pygsp-like module.  Real MI355X (`-m gpu`)."""
+import os
+import re
+
 import numpy as np
 import pytest
 from scipy import sparse
@@ -238,6 +241,32 @@ def test_options_api(ctx):
         ctx.get_option("no_such_option")
     assert ctx.bench_copy(64 << 20, 3) > 100.0  # GB/s: sanity of the calibration kernels
     assert ctx.bench_read(8 << 20, 20) > 100.0
+
+
+def test_documented_options_are_library_keys():
+    """Every key named in the options comment of include/gspx.h is a key of the library: get_option accepts it and
+    set_option takes its current value back; the one the comment calls read-only refuses a set.  A fresh context, no
+    graph, no launch."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "gspx.h")).read()
+    start = header.index("Integer options of a context")
+    comment = header[start:header.index("*/", start)]
+    keys = re.findall(r'"([a-z0-9_]+)"', comment)
+    read_only = re.findall(r'read-only "([a-z0-9_]+)"', comment)
+    assert len(keys) >= 20 and len(set(keys)) == len(keys) and {"kernel", "tile_lg", "streamed_alloc"} <= set(keys)
+    assert read_only == ["retired_va_mb"]
+    c = engine.Context(0)
+    try:
+        for key in keys:
+            value = c.get_option(key)
+            if key in read_only:
+                with pytest.raises(ValueError):
+                    c.set_option(key, value)
+            else:
+                c.set_option(key, value)
+                assert c.get_option(key) == value, key
+    finally:
+        c.close()
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

@@ -1,4 +1,4 @@
-"""Allocator regression tests for the context workspaces (libgspx DevMem, pygsp_amd/csrc/gspx.hip).
+"""Allocator regression tests for the context workspaces (libgspx DevMem, pygsp_amd/csrc/gspx_mem.hip.h).
 
 Round 1 ended red on hardware because a workspace of 32 MB and more - assembled from 2 MB physical
 chunks through the HIP virtual-memory API - was re-grown by unmap / address-free / re-reserve / re-map

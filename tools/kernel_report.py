@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Compile pygsp_amd/csrc/gspx.hip with -save-temps and print per-kernel register / occupancy
-figures from the gfx950 assembly; optionally dump one kernel's ISA.  CPU-only (cross compile).
+"""Compile pygsp_amd/csrc/gspx.hip (the one translation unit: it includes every gspx_*.hip.h) with -save-temps
+and print per-kernel register / occupancy figures from the gfx950 assembly; optionally dump one kernel's ISA.  CPU-only (cross compile).
 
 usage: tools/kernel_report.py [substring-of-kernel-name-to-dump]
 """

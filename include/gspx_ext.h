@@ -122,6 +122,16 @@ int gspx_tikhonov_cg_dev(gspx_graph* g, double tau, const void* mask_dev, int64_
 int gspx_tikhonov_simplex_dev(gspx_graph* g, double tau, double step, const int32_t* labels_dev, int n_classes,
                               double rtol, double atol, double dtol, double xtol, int64_t maxit, void* x_dev,
                               int64_t* niter, int32_t* crit, double* objective_host, double* kernel_ms);
+/* Proximal operator of the graph total variation: argmin over z (N x Nsig) of 1/2 ||x - z||^2 + gamma ||D^T z||_1, D
+ * the differential operator below (the edge list the graph holds when called: the default upper triangle or the one of
+ * gspx_graph_set_edge_list).  FISTA on the dual min_{|u| <= gamma} 1/2 ||x - D u||^2 with the fixed `step` (<= 1 /
+ * lambda_max(D D^T)), u_0 = 0, primal iterate z_k = x - D u_k; one objective, obj_k = 1/2 ||x - z_k||^2 + gamma
+ * ||D^T z_k||_1, for the whole panel.  float64 graphs only; Nsig 1..256; gamma >= 0; x_dev / z_dev: N x Nsig fp64
+ * (DEVICE, caller's vertex order; they may be the same buffer).  Stopping rule, outputs and reproducibility as for
+ * gspx_tikhonov_simplex_dev, with ||z_k - z_{k-1}||_F / sqrt(N Nsig) for xtol; objective_host: room for maxit + 1. */
+int gspx_prox_tv_dev(gspx_graph* g, double gamma, double step, int64_t Nsig, const void* x_dev, void* z_dev,
+                     double rtol, double atol, double dtol, double xtol, int64_t maxit, int64_t* niter, int32_t* crit,
+                     double* objective_host, double* kernel_ms);
 /* Differential operator D (L = D D^T) of an UNDIRECTED graph without self loops created from W
  * (pygsp/graphs/difference.py:26-166).  Edges = stored entries (i, j > i) in row-major order, the
  * order of Graph.get_edge_list (graph.py:1019-1029).  Built on the device at first use.

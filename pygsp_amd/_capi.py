@@ -94,6 +94,9 @@ SIGNATURES = {
     "gspx_tikhonov_simplex_dev": (_c.c_int, [_P, _c.c_double, _c.c_double, _P, _c.c_int, _c.c_double, _c.c_double,
                                               _c.c_double, _c.c_double, _c.c_int64, _P, _c.POINTER(_c.c_int64),
                                               _c.POINTER(_c.c_int32), _P, _c.POINTER(_c.c_double)]),
+    "gspx_prox_tv_dev": (_c.c_int, [_P, _c.c_double, _c.c_double, _c.c_int64, _P, _P, _c.c_double, _c.c_double,
+                                     _c.c_double, _c.c_double, _c.c_int64, _c.POINTER(_c.c_int64),
+                                     _c.POINTER(_c.c_int32), _P, _c.POINTER(_c.c_double)]),
     "gspx_graph_n_edges": (_c.c_int, [_P, _P]),
     "gspx_graph_download_edges": (_c.c_int, [_P, _P, _P, _P, _P, _P]),
     "gspx_graph_set_edge_list": (_c.c_int, [_P, _c.c_int64, _P, _P, _P, _c.c_int]),

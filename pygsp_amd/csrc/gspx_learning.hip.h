@@ -70,26 +70,10 @@ __global__ void k_spx_init(const int* __restrict__ labels, const int* __restrict
   for (int c = 0; c < C; ++c) X0[(size_t)i * C + c] = c == l ? 1.0 : 0.0;
 }
 
-// the three per-thread sums -> partial[q * gridDim.x + blockIdx.x], wave shuffles then the four waves in order
+// the three per-thread sums -> partial[q * gridDim.x + blockIdx.x] (gspx_reduce.hip.h's block_sums)
 __device__ inline void spx_block_sums(double s0, double s1, double s2, double* partial) {
-  __shared__ double ws[3][4];
-  double v[3] = {s0, s1, s2};
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    ws[0][w] = v[0];
-    ws[1][w] = v[1];
-    ws[2][w] = v[2];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int q = threadIdx.x;
-    partial[(size_t)q * gridDim.x + blockIdx.x] = (ws[q][0] + ws[q][1]) + (ws[q][2] + ws[q][3]);
-  }
+  const double v[3] = {s0, s1, s2};
+  block_sums<3>(v, partial + blockIdx.x, gridDim.x);
 }
 
 // z = V - step grad f(V) for one entry (y = [c == label], m = [label >= 0])
@@ -227,50 +211,45 @@ __global__ __launch_bounds__(256) void k_spx_step_wave(SpxStep a) {
   spx_block_sums(sd, sx, ss, a.partial);
 }
 
+// The stopping rule of the FISTA loops (this file and gspx_optim.hip.h) for iteration it >= 1: the first criterion that
+// holds, in this order, or 0.  dx2 = ||X_it - X_{it-1}||_F^2, nc = the number of entries of X.
+__device__ inline int fista_rule(double cur, double prev, double dx2, double nc, long long it, double rtol, double atol,
+                                 double dtol, double xtol, long long maxit) {
+  const double diff = fabs(cur - prev);
+  double den = cur;
+  if (den == 0) den = prev;
+  if (den == 0) den = 1.0;
+  if (atol >= 0 && cur < atol) return SPX_ATOL;
+  if (dtol >= 0 && diff < dtol) return SPX_DTOL;
+  if (rtol >= 0 && diff / den < rtol) return SPX_RTOL;
+  if (xtol >= 0 && sqrt(dx2) / sqrt(nc) < xtol) return SPX_XTOL;
+  if (it >= maxit) return SPX_MAXIT;
+  return 0;
+}
+
 // After launch k: obj_{k-1} = tau sum(X_{k-1} L X_{k-1}) + data_{k-1}; the rule on iteration k - 1 >= 1; then the
 // sums of X_k wait in the state for the next launch.  One workgroup of 256 threads, thread t sums partials
-// t, t + 256, ... in order, the threads are combined as in spx_block_sums; thread 0 applies the rule.
+// t, t + 256, ... in order, the threads are combined by block_sums; thread 0 applies the rule.
 __global__ __launch_bounds__(256) void k_spx_rule(SpxState* state, const double* __restrict__ partial, int nb,
                                                   long long k, double tau, double rtol, double atol, double dtol,
                                                   double xtol, long long maxit, double nc, double* __restrict__ obj) {
   if (state->done) return;
-  __shared__ double ws[3][4];
+  __shared__ double tot[3];
   double v[3] = {0, 0, 0};
   for (int b = threadIdx.x; b < nb; b += 256) {
     v[0] += partial[b];
     v[1] += partial[(size_t)nb + b];
     v[2] += partial[(size_t)2 * nb + b];
   }
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    ws[0][threadIdx.x >> 6] = v[0];
-    ws[1][threadIdx.x >> 6] = v[1];
-    ws[2][threadIdx.x >> 6] = v[2];
-  }
+  block_sums<3>(v, tot, 1);
   __syncthreads();
   if (threadIdx.x != 0) return;
-  const double data = (ws[0][0] + ws[0][1]) + (ws[0][2] + ws[0][3]);
-  const double dx = (ws[1][0] + ws[1][1]) + (ws[1][2] + ws[1][3]);
-  const double smooth = (ws[2][0] + ws[2][1]) + (ws[2][2] + ws[2][3]);
+  const double data = tot[0], dx = tot[1], smooth = tot[2];
   const long long it = k - 1;
   const double cur = tau * smooth + state->data_prev;
   obj[it] = cur;
   if (it >= 1) {
-    const double prev = obj[it - 1];
-    const double diff = fabs(cur - prev);
-    double den = cur;
-    if (den == 0) den = prev;
-    if (den == 0) den = 1.0;
-    int crit = 0;
-    if (atol >= 0 && cur < atol) crit = SPX_ATOL;
-    else if (dtol >= 0 && diff < dtol) crit = SPX_DTOL;
-    else if (rtol >= 0 && diff / den < rtol) crit = SPX_RTOL;
-    else if (xtol >= 0 && sqrt(state->dx_prev) / sqrt(nc) < xtol) crit = SPX_XTOL;
-    else if (it >= maxit) crit = SPX_MAXIT;
+    const int crit = fista_rule(cur, obj[it - 1], state->dx_prev, nc, it, rtol, atol, dtol, xtol, maxit);
     if (crit) {
       state->crit = crit;
       state->niter = it;

@@ -1,5 +1,5 @@
-// gspx_reduce.hip.h - the column reductions every operator next to the Chebyshev path shares: one in-workgroup
-// column sum, one second pass over workgroup partials, one Gram kernel on the matrix cores.  Every reduction is per
+// gspx_reduce.hip.h - the reductions every operator next to the Chebyshev path shares: one in-workgroup column sum,
+// one in-workgroup total, one second pass over workgroup partials, one Gram kernel on the matrix cores.  Every reduction is per
 // workgroup (or per wave) into partials, then a fixed-order second pass: no atomics, the same bits on every call -
 // for all callers, because there is one definition of each piece.  gfx950 only.
 // Included by gspx_ops.hip.h (the host helpers use gspx_ctx, DevMem, HIPCHK, CHK).
@@ -25,6 +25,30 @@ __device__ inline void block_colsum(double* ws, double v, int ld, int ldp, int r
     out[threadIdx.x] = s;
   }
   __syncthreads();
+}
+
+// ---- in-workgroup totals of Q per-thread sums --------------------------------------------------------------------
+// A 256-thread workgroup: wave shuffles, then the four waves in the order (w0 + w1) + (w2 + w3); thread q < Q writes
+// out[q * stride].  All 256 threads call it, once per kernel (ws is not guarded for a second call).
+template <int Q>
+__device__ inline void block_sums(const double (&s)[Q], double* out, size_t stride) {
+  __shared__ double ws[Q][4];
+  double v[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    v[q] = s[q];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) ws[q][threadIdx.x >> 6] = v[q];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < Q) {
+    const int q = threadIdx.x;
+    out[(size_t)q * stride] = (ws[q][0] + ws[q][1]) + (ws[q][2] + ws[q][3]);
+  }
 }
 
 // ---- second pass: out[c] = sum over b of partial[b * count + c] (sum_parts below picks the kernel) ---------------

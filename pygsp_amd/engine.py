@@ -1183,6 +1183,43 @@ class DeviceGraph:
                 "ms": ms.value}
         return X, info
 
+    # ---- optimization (proximal operators) ----------------------------------------------------------
+    def prox_tv_dev(self, x_ptr, z_ptr, nsig, gamma, step, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
+        """gspx_prox_tv_dev on device pointers (N x nsig float64 panels, caller's vertex order); returns info."""
+        maxit = int(maxit)
+        off = lambda v: -1.0 if v is None else float(v)
+        obj = np.zeros(max(maxit, 0) + 1, dtype=np.float64)
+        niter, crit, ms = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_prox_tv_dev,
+            self._h, float(gamma), float(step), int(nsig), ctypes.c_void_p(x_ptr), ctypes.c_void_p(z_ptr), off(rtol),
+            off(atol), off(dtol), off(xtol), maxit, ctypes.byref(niter), ctypes.byref(crit), _capi.ptr(obj),
+            ctypes.byref(ms))
+        crits = {1: "ATOL", 2: "DTOL", 3: "RTOL", 4: "XTOL", 5: "MAXIT"}
+        return {"niter": int(niter.value), "crit": crits.get(crit.value), "objective": obj[:niter.value + 1].copy(),
+                "ms": ms.value}
+
+    def prox_tv(self, x, gamma, step, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
+        """argmin_z 1/2 ||x - z||^2 + gamma ||D^T z||_1 for x (N,) or (N, Nsig), Nsig <= 256, by FISTA on the dual
+        (gspx_prox_tv_dev), on this float64 graph and the edge list it holds; a tolerance of None is off, one
+        objective for the whole panel.  x: a numpy array or a float64 DeviceArray of this context; z comes back as
+        the same kind.  Returns (z, info) with info = {'niter', 'crit' ('ATOL', 'DTOL', 'RTOL', 'XTOL' or 'MAXIT'),
+        'objective' (obj_0 .. obj_niter), 'ms' (device time)}."""
+        if self.dtype != np.float64:
+            raise ValueError("prox_tv runs on the float64 device graph")
+        opts = dict(rtol=rtol, atol=atol, dtol=dtol, xtol=xtol, maxit=maxit)
+        if isinstance(x, DeviceArray):
+            if x.dtype != np.float64 or x.ctx is not self.ctx or x.cube[0] != self.N or x.cube[2] != 1:
+                raise ValueError("prox_tv: a device signal must be (N[, Nsig]) float64 on the graph's context")
+            z = DeviceArray.empty(self.ctx, x.cube, np.float64)
+            z.shape = x.shape
+            return z, self.prox_tv_dev(x.ptr, z.ptr, x.cube[1], gamma, step, **opts)
+        x2, one_d = self._panel(x, self.N, "prox_tv")
+        with self.ctx._temporaries() as t:
+            bx, bz = t.upload(x2), t.alloc(max(x2.nbytes, 16))
+            info = self.prox_tv_dev(bx.ptr, bz.ptr, x2.shape[1], gamma, step, **opts)
+            z = bz.download(x2.shape, np.float64)
+        return (z[:, 0] if one_d else z), info
+
     # ---- edges: the differential operator D, grad = D^T x, div = D y ---------------------------------
     def n_edges(self):
         return self._i64(_capi.load().gspx_graph_n_edges)

@@ -254,6 +254,20 @@ def _learning_functions(saved):
             "regression_tikhonov": regression_tikhonov}
 
 
+_OPTIMIZATION = ("prox_tv",)
+
+
+def _optimization_functions(saved):
+    """prox_tv on the device (pygsp_amd.optimization): the package's own function cannot run as shipped."""
+    from . import optimization
+
+    def prox_tv(x, gamma, G, A=None, At=None, nu=1, tol=10e-4, maxit=200, use_matrix=True, **kwargs):
+        return optimization.prox_tv(x, gamma, G, A, At, nu, tol, maxit, use_matrix, **kwargs)
+
+    prox_tv.__doc__ = optimization.prox_tv.__doc__
+    return {"prox_tv": prox_tv}
+
+
 _TOPOLOGY = ("is_connected", "extract_components")
 
 
@@ -297,7 +311,7 @@ def _extract_components_on_device(self):
 
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
-            lanczos=False, features=False, learning=False, topology=False):
+            lanczos=False, features=False, learning=False, topology=False, optimization=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -323,7 +337,9 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     pyunlocbox) and ``regression_tikhonov`` (tau > 0 with a sparse L: the device conjugate gradients; otherwise the
     original); ``classification_tikhonov`` looks ``regression_tikhonov`` up at call time and follows.
     `topology` (default False): also replace ``Graph.is_connected`` and ``Graph.extract_components`` so that undirected
-    graphs are labelled on the device (gspx_graph_components); directed graphs keep the reference's code."""
+    graphs are labelled on the device (gspx_graph_components); directed graphs keep the reference's code.
+    `optimization` (default False): also replace ``pygsp.optimization.prox_tv`` with pygsp_amd.optimization.prox_tv (the
+    graph total-variation proximal operator on the device, without pyunlocbox)."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -363,7 +379,8 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         _apply(on["Graph"], methods)
     for name, asked, names, replacements in (
             ("features", features, _FEATURES, lambda saved: _feature_functions(pygsp_module, saved)),
-            ("learning", learning, _LEARNING, _learning_functions)):
+            ("learning", learning, _LEARNING, _learning_functions),
+            ("optimization", optimization, _OPTIMIZATION, _optimization_functions)):
         if on[name] is not None:
             _apply(on[name], replacements(_originals(on[name], names)) if asked else {})
         elif asked:
@@ -376,7 +393,8 @@ def _targets(pygsp_module):
     filters = pygsp_module.filters
     return {"approximations": filters.approximations, "filters": filters, "Filter": getattr(filters, "Filter", None),
             "Graph": getattr(getattr(pygsp_module, "graphs", None), "Graph", None),
-            "features": getattr(pygsp_module, "features", None), "learning": getattr(pygsp_module, "learning", None)}
+            "features": getattr(pygsp_module, "features", None), "learning": getattr(pygsp_module, "learning", None),
+            "optimization": getattr(pygsp_module, "optimization", None)}
 
 
 def _apply(obj, wanted):

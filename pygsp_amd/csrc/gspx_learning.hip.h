@@ -16,29 +16,22 @@
 //                  sum m ||X_k - Y||^2 and ||X_k - X_{k-1}||^2, and of sum X_{k-1} * L X_{k-1} (both read anyway):
 //                  obj_{k-1} is complete only after launch k, so three X buffers rotate and the rule fires on
 //                  X_{k-1} while X_k sits in the third
-//   k_spx_rule     one workgroup: sums the partials in a fixed order, then one thread records obj_{k-1} and applies
-//                  the stopping rule to iteration k - 1 (done flag, niter, criterion)
+//   k_spx_rule     one workgroup: forms obj_{k-1} from the summed partials and hands iteration k - 1 to the shared
+//                  rule (fista_totals, fista_judge)
 //   spmm_internal  L X_k, the engine's product
-// After the done flag is set every step and rule launch returns at once: the host polls the flag every few
-// launches, and what it launches past the stop changes nothing.  Partial sums have one order for a given N and C:
-// the same inputs give the same bits on every call.  After gspx_ops.hip.h.
+// The loop around them - momentum, stopping rule, done flag, poll, finish - is gspx_fista.hip.h's.  Partial sums have
+// one order for a given N and C: the same inputs give the same bits on every call.  After gspx_fista.hip.h.
 #pragma once
 
 namespace gspx {
 
 constexpr int SPX_MAX_CLASSES = 256;
 constexpr int SPX_BLOCKS = 2048;  // fixed grid of the step kernels (grid-stride over rows): one summation order
-constexpr int SPX_POLL = 4;       // the host looks at the done flag every SPX_POLL launches
-constexpr long long SPX_MAXIT_LIMIT = 10000000;  // (the objective sequence is a device array of maxit + 1 doubles)
-
-enum { SPX_ATOL = 1, SPX_DTOL = 2, SPX_RTOL = 3, SPX_XTOL = 4, SPX_MAXIT = 5 };
 
 struct SpxState {     // device resident
   double data_prev;   // sum m ||X_{k-1} - Y||^2 of the last iterate the rule has not judged yet
   double dx_prev;     // ||X_{k-1} - X_{k-2}||^2
-  int done;
-  int crit;
-  long long niter;
+  FistaState f;
   int bad_label;      // a label outside -1..C-1 was seen by k_spx_init
 };
 
@@ -89,7 +82,7 @@ __device__ inline double spx_point(const SpxStep& a, double av, double bv, doubl
 // exact and sort-free, at most C passes and usually two or three.
 template <int CMAX>
 __global__ __launch_bounds__(256) void k_spx_step_row(SpxStep a) {
-  if (a.state->done) return;
+  if (a.state->f.done) return;
   const int C = a.C;
   double sd = 0, sx = 0, ss = 0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < a.N; i += gridDim.x * 256) {
@@ -150,7 +143,7 @@ __device__ inline double spx_wave_sum(double v) {  // butterfly: every lane ends
 // wave sums.
 template <int VPL>
 __global__ __launch_bounds__(256) void k_spx_step_wave(SpxStep a) {
-  if (a.state->done) return;
+  if (a.state->f.done) return;
   const int C = a.C;
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -211,54 +204,19 @@ __global__ __launch_bounds__(256) void k_spx_step_wave(SpxStep a) {
   spx_block_sums(sd, sx, ss, a.partial);
 }
 
-// The stopping rule of the FISTA loops (this file and gspx_optim.hip.h) for iteration it >= 1: the first criterion that
-// holds, in this order, or 0.  dx2 = ||X_it - X_{it-1}||_F^2, nc = the number of entries of X.
-__device__ inline int fista_rule(double cur, double prev, double dx2, double nc, long long it, double rtol, double atol,
-                                 double dtol, double xtol, long long maxit) {
-  const double diff = fabs(cur - prev);
-  double den = cur;
-  if (den == 0) den = prev;
-  if (den == 0) den = 1.0;
-  if (atol >= 0 && cur < atol) return SPX_ATOL;
-  if (dtol >= 0 && diff < dtol) return SPX_DTOL;
-  if (rtol >= 0 && diff / den < rtol) return SPX_RTOL;
-  if (xtol >= 0 && sqrt(dx2) / sqrt(nc) < xtol) return SPX_XTOL;
-  if (it >= maxit) return SPX_MAXIT;
-  return 0;
-}
-
-// After launch k: obj_{k-1} = tau sum(X_{k-1} L X_{k-1}) + data_{k-1}; the rule on iteration k - 1 >= 1; then the
-// sums of X_k wait in the state for the next launch.  One workgroup of 256 threads, thread t sums partials
-// t, t + 256, ... in order, the threads are combined by block_sums; thread 0 applies the rule.
+// After launch k: obj_{k-1} = tau sum(X_{k-1} L X_{k-1}) + data_{k-1}, judged as iteration k - 1 with the distance that
+// waited in the state beside data_{k-1}; unless the rule fires, the sums of X_k wait there for the next launch.
 __global__ __launch_bounds__(256) void k_spx_rule(SpxState* state, const double* __restrict__ partial, int nb,
-                                                  long long k, double tau, double rtol, double atol, double dtol,
-                                                  double xtol, long long maxit, double nc, double* __restrict__ obj) {
-  if (state->done) return;
+                                                  long long k, double tau, FistaTol tol, double nc,
+                                                  double* __restrict__ obj) {
+  if (state->f.done) return;
   __shared__ double tot[3];
-  double v[3] = {0, 0, 0};
-  for (int b = threadIdx.x; b < nb; b += 256) {
-    v[0] += partial[b];
-    v[1] += partial[(size_t)nb + b];
-    v[2] += partial[(size_t)2 * nb + b];
-  }
-  block_sums<3>(v, tot, 1);
-  __syncthreads();
+  fista_totals<3>(partial, nb, tot);
   if (threadIdx.x != 0) return;
-  const double data = tot[0], dx = tot[1], smooth = tot[2];
-  const long long it = k - 1;
-  const double cur = tau * smooth + state->data_prev;
-  obj[it] = cur;
-  if (it >= 1) {
-    const int crit = fista_rule(cur, obj[it - 1], state->dx_prev, nc, it, rtol, atol, dtol, xtol, maxit);
-    if (crit) {
-      state->crit = crit;
-      state->niter = it;
-      state->done = 1;
-      return;
-    }
-  }
-  state->data_prev = data;
-  state->dx_prev = dx;
+  const double cur = tau * tot[2] + state->data_prev;
+  if (fista_judge(&state->f, obj, k - 1, cur, state->dx_prev, nc, tol)) return;
+  state->data_prev = tot[0];
+  state->dx_prev = tot[1];
 }
 
 }  // namespace gspx
@@ -282,25 +240,24 @@ static int spx_blocks(int64_t N, int C) {  // a function of N and C alone: the p
   return (int)std::max<int64_t>(1, std::min<int64_t>(gspx::SPX_BLOCKS, (N + rows_per_block - 1) / rows_per_block));
 }
 
-static int tikhonov_simplex_t(gspx_graph* g, double tau, double step, const int32_t* labels, int C, double rtol,
-                              double atol, double dtol, double xtol, int64_t maxit, double* x, int64_t* niter,
-                              int32_t* crit, double* objective, double* ms) {
+static int tikhonov_simplex_t(gspx_graph* g, double tau, double step, const int32_t* labels, int C, const FistaTol& tol,
+                              double* x, int64_t* niter, int32_t* crit, double* objective, double* ms) {
   gspx_ctx* ctx = g->ctx;
   hipStream_t st = ctx->stream;
-  const int64_t N = g->N;
+  const int64_t N = g->N, maxit = tol.maxit;
   const size_t U = (size_t)N * C;
   const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
   const int* iperm = g->has_perm ? g->iperm.as<int>() : nullptr;
   const int nb = spx_blocks(N, C);
-  DevMem panels, lab, part, obj, state;
+  FistaLoop loop;
+  CHK(loop.init(g, "tikhonov_simplex", tol, sizeof(SpxState), offsetof(SpxState, f)));
+  DevMem panels, lab, part;
   // panels 256-byte aligned, with room for the product kernels' vector reads past a panel's end
   const size_t pitch = (U * sizeof(double) + 511) & ~(size_t)255;
   const size_t pad = 256;
   CHK(panels.alloc(5 * pitch));
   CHK(lab.alloc((size_t)N * sizeof(int) + pad));
   CHK(part.alloc((size_t)3 * nb * sizeof(double)));
-  CHK(obj.alloc((size_t)(maxit + 1) * sizeof(double)));
-  CHK(state.alloc(sizeof(SpxState)));
   double* X[3];
   double* LX[2];
   for (int j = 0; j < 5; ++j) {
@@ -308,9 +265,8 @@ static int tikhonov_simplex_t(gspx_graph* g, double tau, double step, const int3
     if (j < 3) X[j] = p;
     else LX[j - 3] = p;
   }
-  SpxState* sd = (SpxState*)state.p;
-  HIPCHK(hipEventRecord(ctx->ev[0], st));
-  HIPCHK(hipMemsetAsync(state.p, 0, sizeof(SpxState), st));
+  CHK(loop.start());
+  SpxState* sd = loop.state.as<SpxState>();
   hipLaunchKernelGGL(gspx::k_spx_init, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, labels, perm, (int)N, C,
                      lab.as<int>(), X[0], sd);
   SpxState hs{};
@@ -326,41 +282,29 @@ static int tikhonov_simplex_t(gspx_graph* g, double tau, double step, const int3
   a.C = C;
   a.step = step;
   a.tau = tau;
-  double t = 1.0, b = 0.0;  // t_{k-1} and b_{k-1} of launch k (V_0 = X_0: b_0 = 0)
-  for (int64_t k = 1; k <= maxit + 1; ++k) {
+  for (int64_t k = 1; k <= maxit + 1; ++k) {  // loop.b is b_{k-1} at launch k
     a.A = X[(k - 1) % 3];
     a.B = k >= 2 ? X[(k - 2) % 3] : a.A;
     a.LA = LX[(k - 1) % 2];
     a.LB = k >= 2 ? LX[(k - 2) % 2] : a.LA;
     a.X = X[k % 3];
-    a.b = b;
+    a.b = loop.b;
     a.write = k <= maxit;
     CHK(spx_launch_step(a, nb, st));
-    hipLaunchKernelGGL(gspx::k_spx_rule, dim3(1), dim3(256), 0, st, sd, part.as<double>(), nb, (long long)k, tau,
-                       rtol, atol, dtol, xtol, (long long)maxit, (double)U, obj.as<double>());
+    hipLaunchKernelGGL(gspx::k_spx_rule, dim3(1), dim3(256), 0, st, sd, part.as<double>(), nb, (long long)k, tau, tol,
+                       (double)U, loop.obj.as<double>());
     if (k <= maxit) CHK(spmm_internal<double>(g, g->rval.as<double>(), 1.0, 0.0, X[k % 3], LX[k % 2], (unsigned)C,
                                               nullptr, 0));
-    const double tn = (1.0 + std::sqrt(1.0 + 4.0 * t * t)) / 2.0;  // t_k, b_k = (t_{k-1} - 1) / t_k
-    b = (t - 1.0) / tn;
-    t = tn;
-    if (k % gspx::SPX_POLL == 0 && k <= maxit) {
-      int done = 0;
-      HIPCHK(hipMemcpyAsync(&done, &sd->done, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+    loop.advance();
+    if (k % gspx::FISTA_POLL == 0 && k <= maxit) {
+      bool done = false;
+      CHK(loop.poll(&done));
       if (done) break;
     }
   }
-  HIPCHK(hipMemcpyAsync(&hs, sd, sizeof(SpxState), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (!hs.done) return set_err(GSPX_ERR_HIP, "tikhonov_simplex: the stopping rule did not fire");
-  const int64_t n_it = hs.niter;
-  CHK(permute_panel<double>(g, X[n_it % 3], (unsigned)C, x, (unsigned)C, iperm));
-  HIPCHK(hipMemcpyAsync(objective, obj.p, (size_t)(n_it + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(ctx->ev[1], st));
-  CHK(finish_timed(ctx, ms));
-  *niter = n_it;
-  *crit = hs.crit;
-  return GSPX_OK;
+  return loop.finish(
+      [&](int64_t n_it) { return permute_panel<double>(g, X[n_it % 3], (unsigned)C, x, (unsigned)C, iperm); }, objective,
+      niter, crit, ms);
 }
 
 extern "C" int gspx_tikhonov_simplex_dev(gspx_graph* g, double tau, double step, const int32_t* labels_dev,
@@ -368,23 +312,10 @@ extern "C" int gspx_tikhonov_simplex_dev(gspx_graph* g, double tau, double step,
                                          int64_t maxit, void* x_dev, int64_t* niter, int32_t* crit,
                                          double* objective_host, double* kernel_ms) {
   if (!(tau > 0) || !std::isfinite(tau)) return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: tau must be positive and finite");
-  if (!(step > 0) || !std::isfinite(step))
-    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: step must be positive and finite");
-  if (maxit < 1 || maxit > gspx::SPX_MAXIT_LIMIT)
-    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: maxit must be 1..%lld (got %lld)",
-                   gspx::SPX_MAXIT_LIMIT, (long long)maxit);
-  if (n_classes < 1 || n_classes > gspx::SPX_MAX_CLASSES)
-    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: n_classes must be 1..%d (got %d)", gspx::SPX_MAX_CLASSES,
-                   n_classes);
-  if (std::isnan(rtol) || std::isnan(atol) || std::isnan(dtol) || std::isnan(xtol))
-    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: a tolerance is NaN (a negative one disables its criterion)");
-  if (!niter || !crit || !objective_host) return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: null host output");
-  if (g) replay_reset(g->ctx);
-  if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
-  if (g->N > 0 && (!labels_dev || !x_dev)) return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: null device pointer");
-  if (g->dtype != GSPX_F64)
-    return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: the graph computes in float32; the solver needs the float64 graph");
-  if ((double)g->N * n_classes * sizeof(double) > (double)(((size_t)1 << 31) - 65536))
+  const FistaTol tol{rtol, atol, dtol, xtol, (long long)maxit};
+  CHK(fista_check("tikhonov_simplex", g, step, tol, "n_classes", n_classes, gspx::SPX_MAX_CLASSES, labels_dev, x_dev,
+                  niter, crit, objective_host));
+  if (fista_panel_too_large(g->N, n_classes))
     return set_err(GSPX_ERR_INVALID, "tikhonov_simplex: an N x n_classes panel exceeds 2 GiB");
   if (kernel_ms) *kernel_ms = 0;
   if (g->N == 0) {
@@ -392,7 +323,6 @@ extern "C" int gspx_tikhonov_simplex_dev(gspx_graph* g, double tau, double step,
     *crit = 0;
     return GSPX_OK;
   }
-  HIPCHK(hipSetDevice(g->ctx->device));
-  return tikhonov_simplex_t(g, tau, step, labels_dev, n_classes, rtol, atol, dtol, xtol, maxit, (double*)x_dev, niter,
-                            crit, objective_host, kernel_ms);
+  return tikhonov_simplex_t(g, tau, step, labels_dev, n_classes, tol, (double*)x_dev, niter, crit, objective_host,
+                            kernel_ms);
 }

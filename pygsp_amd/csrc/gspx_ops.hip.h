@@ -432,6 +432,26 @@ extern "C" int gspx_graph_download_edges(gspx_graph* g, int32_t* sources, int32_
   return GSPX_OK;
 }
 
+// The vertex walk of k_grad_v / k_div_v (and of the total-variation prox) for N x ld panels in lanes of `vec`
+// elements: fills *w and returns the workgroup count, 8 XCD ranges of at most xcd_cap workgroups (grid-stride beyond).
+template <typename T>
+static unsigned vertex_walk(const gspx_graph* g, int ld, int vec, int xcd_cap, gspx::VertexWalk<T>* w) {
+  w->perm = g->has_perm ? g->perm.as<int>() : nullptr;
+  w->eoff = g->e_off.as<int>();
+  w->toff = g->e_toff.as<int>();
+  w->tedge = g->e_tedge.as<int>();
+  w->edst = g->e_dst.as<int>();
+  w->cs = g->e_cs.as<T>();
+  w->ct = g->e_ct.as<T>();
+  w->N = (int)g->N;
+  w->ld = ld;
+  w->gs = 1;
+  while (w->gs < 64 && w->gs < ld / vec) w->gs <<= 1;
+  w->per_xcd = (int)((g->N + 7) / 8);
+  const int gpb = 256 / w->gs;
+  return 8u * (unsigned)std::min<int64_t>(((int64_t)w->per_xcd + gpb - 1) / gpb, xcd_cap);
+}
+
 template <typename T>
 static int grad_div_t(gspx_graph* g, bool is_div, int64_t Nsig, const T* in, T* out, double* ms) {
   gspx_ctx* ctx = g->ctx;
@@ -447,19 +467,14 @@ static int grad_div_t(gspx_graph* g, bool is_div, int64_t Nsig, const T* in, T* 
   if ((Nsig % TV) == 0 && ((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0 && g->N >= 8 &&
       ctx->opt.edge_vertex_walk) {
     // vertex walk in the internal order (see k_grad_v): lane groups of 16-byte lanes, one per vertex
-    int gs = 1;
-    while (gs < 64 && gs < Nsig / TV) gs <<= 1;
-    const int per_xcd = (int)((g->N + 7) / 8), gpb = 256 / gs;
-    const unsigned nbx = (unsigned)std::min<int64_t>(((int64_t)per_xcd + gpb - 1) / gpb, 8192);
-    const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
+    VertexWalk<T> w{};
+    const unsigned nbv = vertex_walk<T>(g, (int)Nsig, TV, 8192, &w);
     if (is_div)
-      hipLaunchKernelGGL((k_div_v<T, TV>), dim3(nbx * 8), dim3(256), 0, st, perm, g->e_off.as<int>(),
-                         g->e_toff.as<int>(), g->e_tedge.as<int>(), g->e_cs.as<T>(), g->e_ct.as<T>(), in, out,
-                         (int)g->N, (int)Nsig, gs, per_xcd);
+      hipLaunchKernelGGL((k_div_v<T, TV>), dim3(nbv), dim3(256), 0, st, w.perm, w.eoff, w.toff, w.tedge, w.cs, w.ct, in,
+                         out, w.N, w.ld, w.gs, w.per_xcd);
     else
-      hipLaunchKernelGGL((k_grad_v<T, TV>), dim3(nbx * 8), dim3(256), 0, st, perm, g->e_off.as<int>(),
-                         g->e_dst.as<int>(), g->e_cs.as<T>(), g->e_ct.as<T>(), in, out, (int)g->N, (int)Nsig, gs,
-                         per_xcd);
+      hipLaunchKernelGGL((k_grad_v<T, TV>), dim3(nbv), dim3(256), 0, st, w.perm, w.eoff, w.edst, w.cs, w.ct, in, out,
+                         w.N, w.ld, w.gs, w.per_xcd);
   } else if (is_div)
     hipLaunchKernelGGL((k_div<T>), dim3(nb), dim3(256), 0, st, g->e_off.as<int>(), g->e_toff.as<int>(),
                        g->e_tedge.as<int>(), g->e_cs.as<T>(), g->e_ct.as<T>(), in, out, (int)g->N,

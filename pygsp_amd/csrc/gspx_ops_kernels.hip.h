@@ -307,6 +307,43 @@ __global__ __launch_bounds__(256) void k_div(const int* __restrict__ eoff, const
 // (grad) and the edge rows shared by two vertices (div) were touched a moment ago by a neighbouring
 // vertex on the same XCD and come from its L2, where the edge-order kernels above fetch them from HBM
 // again.  Edges of a vertex are consecutive (the list is sorted by source), so grad writes whole runs.
+// VertexWalk holds the edge list and the geometry of this walk (filled by the host's vertex_walk), walk_span gives
+// a thread its share of it.  gspx_optim.hip.h's kernels take the struct and walk the same way; k_grad_v and k_div_v
+// below keep their loose arguments and write the same map out, because passing the struct gave them another
+// instruction stream and one grad timing outside the run-to-run spread (profiles/fista_driver.md).
+template <typename T>
+struct VertexWalk {
+  const int* perm;   // internal position -> vertex, null = identity
+  const int* eoff;   // edges of vertex v as source: eoff[v] .. eoff[v + 1]
+  const int* toff;   // tedge[toff[v] .. toff[v + 1]]: the edges that end in v
+  const int* tedge;
+  const int* edst;
+  const T* cs;       // D's value at the source and at the target of every edge
+  const T* ct;
+  int N, ld;
+  int gs;            // lanes per vertex (a power of two up to 64), 256 / gs vertices per workgroup pass
+  int per_xcd;       // vertices of one XCD's contiguous range: workgroup b works in range b % 8
+};
+
+struct WalkSpan {
+  int lane, grp;      // this thread's lane within its group and the group within the workgroup
+  int cpr;            // VEC-wide chunks per row: lane takes chunks lane, lane + gs, ...
+  int lo, hi, stride; // the group takes internal positions lo, lo + stride, ... < hi
+};
+
+template <typename T>
+__device__ inline WalkSpan walk_span(const VertexWalk<T>& w, int vec) {
+  WalkSpan s;
+  const int gpb = 256 / w.gs, xlo = (int)(blockIdx.x & 7) * w.per_xcd;
+  s.lane = threadIdx.x % w.gs;
+  s.grp = threadIdx.x / w.gs;
+  s.cpr = w.ld / vec;
+  s.hi = min(w.N, xlo + w.per_xcd);
+  s.stride = (int)(gridDim.x >> 3) * gpb;
+  s.lo = xlo + (int)(blockIdx.x >> 3) * gpb + s.grp;
+  return s;
+}
+
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void k_grad_v(const int* __restrict__ perm, const int* __restrict__ eoff,
                                                 const int* __restrict__ edst, const T* __restrict__ cs,

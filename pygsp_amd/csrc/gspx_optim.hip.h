@@ -11,43 +11,26 @@
 //   t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2,  b_{k+1} = (t_k - 1) / t_{k+1}
 // D^T is linear, so the gradient at the extrapolated point is the extrapolation of the gradients: one D and one D^T
 // product per iteration, both on u_k itself, and g_k is recomputed from a_k every time (nothing drifts).  The rule is
-// gspx_learning.hip.h's fista_rule on obj_k and ||a_k - a_{k-1}||_F / sqrt(N Nsig), one objective for the panel.
+// the shared one on obj_k and ||a_k - a_{k-1}||_F / sqrt(N Nsig), one objective for the panel.
 //
 // Launches of iteration k (vertex panels N x Nsig and edge panels n_edges x Nsig, fp64, caller's vertex order; the
-// vertices are WALKED in the internal order with the thread map of k_div_v / k_grad_v):
+// vertices are WALKED in the internal order: gspx_ops_kernels.hip.h's VertexWalk, as in k_div_v / k_grad_v):
 //   k_tv_div        a_k = D u_k (the old a is read first), zt = x - a_k; partial sums of ||a_k||^2, ||a_k - a_{k-1}||^2
 //   k_tv_grad_step  per source vertex: g_k = cs zt[src] + ct zt[dst] over g_{k-1} in place, partial sums of |g_k|, and
 //                   u_{k+1} over u_{k-1} in place (the two u panels swap roles every iteration): three edge panels
-//   k_tv_rule       one workgroup: sums the partials in a fixed order, records obj_k, applies the rule for k >= 1
-// Once the done flag is set every launch returns at once; the host polls it every TV_POLL iterations.  The rule of
+//   k_tv_rule       one workgroup: forms obj_k from the summed partials and hands iteration k to the shared rule
+// The loop around them - momentum, stopping rule, done flag, poll, finish - is gspx_fista.hip.h's.  The rule of
 // iteration k runs before k_tv_div of iteration k + 1, so the accepted a_k and zt = z_k are never overwritten: the
 // result is a copy of zt.  The grid is a function of N and Nsig alone and every sum has one order: the same inputs
-// give the same bits on every call.  b_k does not depend on the data and is a launch argument.  After
-// gspx_learning.hip.h.
+// give the same bits on every call.  After gspx_fista.hip.h; nothing here needs gspx_learning.hip.h.
 #pragma once
 
 namespace gspx {
 
 constexpr int TV_MAX_WIDTH = 256;
-constexpr int TV_POLL = 4;          // the host looks at the done flag every TV_POLL iterations
 constexpr int TV_XCD_BLOCKS = 1024;  // most workgroups per XCD range (grid-stride beyond)
 
-struct TvState {  // device resident
-  int done;
-  int crit;
-  long long niter;
-};
-
-struct TvWalk {  // the edge list and the vertex walk (k_div_v's thread map)
-  const int* perm;
-  const int* eoff;
-  const int* toff;
-  const int* tedge;
-  const int* edst;
-  const double* cs;
-  const double* ct;
-  int N, ld, gs, per_xcd;
-};
+typedef VertexWalk<double> TvWalk;
 
 typedef double tv_d2 __attribute__((ext_vector_type(2)));
 __device__ inline double tv_sq(double v) { return v * v; }
@@ -64,17 +47,15 @@ __device__ inline tv_d2 tv_clip(tv_d2 v, double g) {
 
 // partial[q * gridDim.x + blockIdx.x], q = 0: ||a_k||^2, q = 1: ||a_k - a_{k-1}||^2
 template <int VEC>
-__global__ __launch_bounds__(256) void k_tv_div(TvWalk w, const TvState* state, const double* __restrict__ x,
+__global__ __launch_bounds__(256) void k_tv_div(TvWalk w, const FistaState* state, const double* __restrict__ x,
                                                 const double* __restrict__ u, double* __restrict__ a,
                                                 double* __restrict__ zt, double* __restrict__ partial) {
   if (state->done) return;
   typedef typename VT<double, VEC>::t V;
-  const int ld = w.ld, gs = w.gs;
-  const int lane = threadIdx.x % gs, grp = threadIdx.x / gs, gpb = 256 / gs, cpr = ld / VEC;
-  const int lo = (int)(blockIdx.x & 7) * w.per_xcd, hi = min(w.N, lo + w.per_xcd);
-  const int stride = (int)(gridDim.x >> 3) * gpb;
+  const WalkSpan sp = walk_span(w, VEC);
+  const int ld = w.ld, gs = w.gs, lane = sp.lane, cpr = sp.cpr;
   double s[2] = {0, 0};
-  for (int i = lo + (int)(blockIdx.x >> 3) * gpb + grp; i < hi; i += stride) {
+  for (int i = sp.lo; i < sp.hi; i += sp.stride) {
     const int v = w.perm ? w.perm[i] : i;
     const int e0 = w.eoff[v], e1 = w.eoff[v + 1], t0 = w.toff[v], t1 = w.toff[v + 1];
     for (int c = lane; c < cpr; c += gs) {
@@ -112,18 +93,16 @@ __global__ __launch_bounds__(256) void k_tv_div(TvWalk w, const TvState* state, 
 // partial[blockIdx.x] = sum |g_k| over the workgroup's edges.  g holds g_{k-1} and receives g_k; un holds u_{k-1} and
 // receives u_{k+1}; every edge belongs to one source vertex, so one lane reads and writes each entry.
 template <int VEC>
-__global__ __launch_bounds__(256) void k_tv_grad_step(TvWalk w, const TvState* state, const double* __restrict__ zt,
+__global__ __launch_bounds__(256) void k_tv_grad_step(TvWalk w, const FistaState* state, const double* __restrict__ zt,
                                                       const double* __restrict__ u, double* __restrict__ un,
                                                       double* __restrict__ g, double b, double step, double gamma,
                                                       double* __restrict__ partial) {
   if (state->done) return;
   typedef typename VT<double, VEC>::t V;
-  const int ld = w.ld, gs = w.gs;
-  const int lane = threadIdx.x % gs, grp = threadIdx.x / gs, gpb = 256 / gs, cpr = ld / VEC;
-  const int lo = (int)(blockIdx.x & 7) * w.per_xcd, hi = min(w.N, lo + w.per_xcd);
-  const int stride = (int)(gridDim.x >> 3) * gpb;
+  const WalkSpan sp = walk_span(w, VEC);
+  const int ld = w.ld, gs = w.gs, lane = sp.lane, cpr = sp.cpr;
   double s[1] = {0};
-  for (int i = lo + (int)(blockIdx.x >> 3) * gpb + grp; i < hi; i += stride) {
+  for (int i = sp.lo; i < sp.hi; i += sp.stride) {
     const int v = w.perm ? w.perm[i] : i;
     const int e0 = w.eoff[v], e1 = w.eoff[v + 1];
     for (int c = lane; c < cpr; c += gs) {
@@ -158,41 +137,24 @@ __global__ __launch_bounds__(256) void k_tv_grad_step(TvWalk w, const TvState* s
   block_sums<1>(s, partial + blockIdx.x, gridDim.x);
 }
 
-// After the two panel launches of iteration k: obj_k = 1/2 ||a_k||^2 + gamma ||g_k||_1 and, for k >= 1, the rule.
-// partial: [3][nb], the two slabs of k_tv_div then the one of k_tv_grad_step.  One workgroup, thread t sums partials
-// t, t + 256, ... in order.
-__global__ __launch_bounds__(256) void k_tv_rule(TvState* state, const double* __restrict__ partial, int nb,
-                                                 long long k, double gamma, double rtol, double atol, double dtol,
-                                                 double xtol, long long maxit, double nc, double* __restrict__ obj) {
+// After the two panel launches of iteration k: obj_k = 1/2 ||a_k||^2 + gamma ||g_k||_1, judged as iteration k.
+// partial: [3][nb], the two slabs of k_tv_div then the one of k_tv_grad_step.
+__global__ __launch_bounds__(256) void k_tv_rule(FistaState* state, const double* __restrict__ partial, int nb,
+                                                 long long k, double gamma, FistaTol tol, double nc,
+                                                 double* __restrict__ obj) {
   if (state->done) return;
   __shared__ double tot[3];
-  double v[3] = {0, 0, 0};
-  for (int b = threadIdx.x; b < nb; b += 256) {
-    v[0] += partial[b];
-    v[1] += partial[(size_t)nb + b];
-    v[2] += partial[(size_t)2 * nb + b];
-  }
-  block_sums<3>(v, tot, 1);
-  __syncthreads();
+  fista_totals<3>(partial, nb, tot);
   if (threadIdx.x != 0) return;
-  const double cur = 0.5 * tot[0] + gamma * tot[2];
-  obj[k] = cur;
-  if (k < 1) return;
-  const int crit = fista_rule(cur, obj[k - 1], tot[1], nc, k, rtol, atol, dtol, xtol, maxit);
-  if (crit) {
-    state->crit = crit;
-    state->niter = k;
-    state->done = 1;
-  }
+  fista_judge(state, obj, k, 0.5 * tot[0] + gamma * tot[2], tot[1], nc, tol);
 }
 
 }  // namespace gspx
 
-using gspx::TvState;
 using gspx::TvWalk;
 
 template <int VEC>
-static void tv_launch_iteration(const TvWalk& w, int nb, hipStream_t st, TvState* sd, const double* x, const double* u,
+static void tv_launch_iteration(const TvWalk& w, int nb, hipStream_t st, FistaState* sd, const double* x, const double* u,
                                 double* un, double* a, double* zt, double* g, double b, double step, double gamma,
                                 double* partial) {
   hipLaunchKernelGGL((gspx::k_tv_div<VEC>), dim3(nb), dim3(256), 0, st, w, sd, x, u, a, zt, partial);
@@ -200,12 +162,11 @@ static void tv_launch_iteration(const TvWalk& w, int nb, hipStream_t st, TvState
                      partial + (size_t)2 * nb);
 }
 
-static int prox_tv_t(gspx_graph* g, double gamma, double step, int ld, const double* x, double* z, double rtol,
-                     double atol, double dtol, double xtol, int64_t maxit, int64_t* niter, int32_t* crit,
-                     double* objective, double* ms) {
+static int prox_tv_t(gspx_graph* g, double gamma, double step, int ld, const double* x, double* z, const FistaTol& tol,
+                     int64_t* niter, int32_t* crit, double* objective, double* ms) {
   gspx_ctx* ctx = g->ctx;
   hipStream_t st = ctx->stream;
-  const int64_t N = g->N, E = g->n_edges;
+  const int64_t N = g->N, E = g->n_edges, maxit = tol.maxit;
   const size_t VU = (size_t)N * ld;
   // panels 256-byte aligned: a, zt | u (two, swapping roles) and g; an edge panel of an edgeless graph holds one row
   const size_t pv = (VU * sizeof(double) + 255) & ~(size_t)255;
@@ -214,86 +175,51 @@ static int prox_tv_t(gspx_graph* g, double gamma, double step, int ld, const dou
   if (total > ((size_t)std::max<int64_t>(ctx->opt.ws_limit_mb, 1) << 20))
     return set_err(GSPX_ERR_INVALID, "prox_tv: %lld signals need %zu MiB of workspace (raise ws_limit_mb)", (long long)ld,
                    total >> 20);
+  FistaLoop loop;
+  CHK(loop.init(g, "prox_tv", tol));
   CHK(ctx->ws_t.ensure(total));
   char* base = ctx->ws_t.as<char>();
   double* a = (double*)base;
   double* zt = (double*)(base + pv);
   double* U[2] = {(double*)(base + 2 * pv), (double*)(base + 2 * pv + pe)};
   double* G = (double*)(base + 2 * pv + 2 * pe);
-  TvWalk w{};
-  w.perm = g->has_perm ? g->perm.as<int>() : nullptr;
-  w.eoff = g->e_off.as<int>();
-  w.toff = g->e_toff.as<int>();
-  w.tedge = g->e_tedge.as<int>();
-  w.edst = g->e_dst.as<int>();
-  w.cs = g->e_cs.as<double>();
-  w.ct = g->e_ct.as<double>();
-  w.N = (int)N;
-  w.ld = ld;
   const int vec = (ld % 2 == 0 && ((uintptr_t)x % 16) == 0) ? 2 : 1;  // 16-byte lanes where the rows allow them
-  w.gs = 1;
-  while (w.gs < 64 && w.gs < ld / vec) w.gs <<= 1;
-  w.per_xcd = (int)((N + 7) / 8);
-  const int gpb = 256 / w.gs;
+  TvWalk w{};
   // a function of N and Nsig alone (and of the alignment of x): the partial sums keep one order
-  const int nb = 8 * (int)std::min<int64_t>(((int64_t)w.per_xcd + gpb - 1) / gpb, gspx::TV_XCD_BLOCKS);
-  DevMem part, obj, state;
+  const int nb = (int)vertex_walk<double>(g, ld, vec, gspx::TV_XCD_BLOCKS, &w);
+  DevMem part;
   CHK(part.alloc((size_t)3 * nb * sizeof(double)));
-  CHK(obj.alloc((size_t)(maxit + 1) * sizeof(double)));
-  CHK(state.alloc(sizeof(TvState)));
-  TvState* sd = (TvState*)state.p;
-  HIPCHK(hipEventRecord(ctx->ev[0], st));
-  HIPCHK(hipMemsetAsync(state.p, 0, sizeof(TvState), st));
+  CHK(loop.start());
   HIPCHK(hipMemsetAsync(base, 0, total, st));  // u_0 = u_{-1} = 0, a_{-1} = 0, g_{-1} = 0 (b_0 = 0 multiplies it)
-  double t = 1.0, b = 0.0;  // t_k and b_k of iteration k
-  for (int64_t k = 0; k <= maxit; ++k) {
+  for (int64_t k = 0; k <= maxit; ++k) {  // loop.b is b_k at iteration k
     double* u = U[k % 2];
     double* un = U[(k + 1) % 2];
-    if (vec == 2) tv_launch_iteration<2>(w, nb, st, sd, x, u, un, a, zt, G, b, step, gamma, part.as<double>());
-    else tv_launch_iteration<1>(w, nb, st, sd, x, u, un, a, zt, G, b, step, gamma, part.as<double>());
-    hipLaunchKernelGGL(gspx::k_tv_rule, dim3(1), dim3(256), 0, st, sd, part.as<double>(), nb, (long long)k, gamma, rtol,
-                       atol, dtol, xtol, (long long)maxit, (double)VU, obj.as<double>());
-    const double tn = (1.0 + std::sqrt(1.0 + 4.0 * t * t)) / 2.0;  // t_{k+1}, b_{k+1} = (t_k - 1) / t_{k+1}
-    b = (t - 1.0) / tn;
-    t = tn;
-    if (k > 0 && k % gspx::TV_POLL == 0 && k < maxit) {
-      int done = 0;
-      HIPCHK(hipMemcpyAsync(&done, &sd->done, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+    if (vec == 2) tv_launch_iteration<2>(w, nb, st, loop.flags, x, u, un, a, zt, G, loop.b, step, gamma, part.as<double>());
+    else tv_launch_iteration<1>(w, nb, st, loop.flags, x, u, un, a, zt, G, loop.b, step, gamma, part.as<double>());
+    hipLaunchKernelGGL(gspx::k_tv_rule, dim3(1), dim3(256), 0, st, loop.flags, part.as<double>(), nb, (long long)k, gamma,
+                       tol, (double)VU, loop.obj.as<double>());
+    loop.advance();
+    if (k > 0 && k % gspx::FISTA_POLL == 0 && k < maxit) {
+      bool done = false;
+      CHK(loop.poll(&done));
       if (done) break;
     }
   }
-  TvState hs{};
-  HIPCHK(hipMemcpyAsync(&hs, sd, sizeof(TvState), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (!hs.done) return set_err(GSPX_ERR_HIP, "prox_tv: the stopping rule did not fire");
-  HIPCHK(hipMemcpyAsync(z, zt, VU * sizeof(double), hipMemcpyDeviceToDevice, st));  // z_niter = x - a_niter
-  HIPCHK(hipMemcpyAsync(objective, obj.p, (size_t)(hs.niter + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(ctx->ev[1], st));
-  CHK(finish_timed(ctx, ms));
-  *niter = hs.niter;
-  *crit = hs.crit;
-  return GSPX_OK;
+  return loop.finish(  // z_niter = x - a_niter
+      [&](int64_t) -> int {
+        HIPCHK(hipMemcpyAsync(z, zt, VU * sizeof(double), hipMemcpyDeviceToDevice, st));
+        return GSPX_OK;
+      },
+      objective, niter, crit, ms);
 }
 
 extern "C" int gspx_prox_tv_dev(gspx_graph* g, double gamma, double step, int64_t Nsig, const void* x_dev, void* z_dev,
                                 double rtol, double atol, double dtol, double xtol, int64_t maxit, int64_t* niter,
                                 int32_t* crit, double* objective_host, double* kernel_ms) {
   if (!(gamma >= 0) || !std::isfinite(gamma)) return set_err(GSPX_ERR_INVALID, "prox_tv: gamma must be finite and >= 0");
-  if (!(step > 0) || !std::isfinite(step)) return set_err(GSPX_ERR_INVALID, "prox_tv: step must be positive and finite");
-  if (maxit < 1 || maxit > gspx::SPX_MAXIT_LIMIT)
-    return set_err(GSPX_ERR_INVALID, "prox_tv: maxit must be 1..%lld (got %lld)", gspx::SPX_MAXIT_LIMIT, (long long)maxit);
-  if (Nsig < 1 || Nsig > gspx::TV_MAX_WIDTH)
-    return set_err(GSPX_ERR_INVALID, "prox_tv: number of signals must be 1..%d (got %lld)", gspx::TV_MAX_WIDTH,
-                   (long long)Nsig);
-  if (std::isnan(rtol) || std::isnan(atol) || std::isnan(dtol) || std::isnan(xtol))
-    return set_err(GSPX_ERR_INVALID, "prox_tv: a tolerance is NaN (a negative one disables its criterion)");
-  if (!niter || !crit || !objective_host) return set_err(GSPX_ERR_INVALID, "prox_tv: null host output");
-  if (g) replay_reset(g->ctx);
-  if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
-  if (g->N > 0 && (!x_dev || !z_dev)) return set_err(GSPX_ERR_INVALID, "prox_tv: null device pointer");
-  if (g->dtype != GSPX_F64)
-    return set_err(GSPX_ERR_INVALID, "prox_tv: the graph computes in float32; the solver needs the float64 graph");
+  const FistaTol tol{rtol, atol, dtol, xtol, (long long)maxit};
+  CHK(fista_check("prox_tv", g, step, tol, "number of signals", Nsig, gspx::TV_MAX_WIDTH, x_dev, z_dev, niter, crit,
+                  objective_host));
   if (kernel_ms) *kernel_ms = 0;
   if (g->N == 0) {
     *niter = 0;
@@ -301,9 +227,8 @@ extern "C" int gspx_prox_tv_dev(gspx_graph* g, double gamma, double step, int64_
     return GSPX_OK;
   }
   CHK(edges_for(g));
-  const double lim = (double)(((size_t)1 << 31) - 65536);
-  if ((double)g->N * Nsig * sizeof(double) > lim || (double)g->n_edges * Nsig * sizeof(double) > lim)
+  if (fista_panel_too_large(g->N, Nsig) || fista_panel_too_large(g->n_edges, Nsig))
     return set_err(GSPX_ERR_INVALID, "prox_tv: an N x Nsig or n_edges x Nsig panel exceeds 2 GiB");
-  return prox_tv_t(g, gamma, step, (int)Nsig, (const double*)x_dev, (double*)z_dev, rtol, atol, dtol, xtol, maxit,
-                   niter, crit, objective_host, kernel_ms);
+  return prox_tv_t(g, gamma, step, (int)Nsig, (const double*)x_dev, (double*)z_dev, tol, niter, crit, objective_host,
+                   kernel_ms);
 }

@@ -701,6 +701,40 @@ def auto_order(W, coords=None, device=0, ctx=None):
     return perm
 
 
+class _SolverRun:
+    """The stopping rule going into, and the outputs coming out of, one call of a FISTA solver entry point
+    (gspx_tikhonov_simplex_dev, gspx_prox_tv_dev): `rule` = rtol, atol, dtol, xtol (None -> -1.0, off) and maxit,
+    `outputs` = niter, crit, the objective sequence and the device time, in the order both entry points take them."""
+    CRITERIA = {1: "ATOL", 2: "DTOL", 3: "RTOL", 4: "XTOL", 5: "MAXIT"}
+
+    def __init__(self, rtol, atol, dtol, xtol, maxit):
+        maxit = int(maxit)
+        self.rule = tuple(-1.0 if v is None else float(v) for v in (rtol, atol, dtol, xtol)) + (maxit,)
+        self.obj = np.zeros(max(maxit, 0) + 1, dtype=np.float64)
+        self.niter, self.crit, self.ms = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0)
+        self.outputs = (ctypes.byref(self.niter), ctypes.byref(self.crit), _capi.ptr(self.obj), ctypes.byref(self.ms))
+
+    def info(self):
+        n = int(self.niter.value)
+        return {"niter": n, "crit": self.CRITERIA.get(self.crit.value), "objective": self.obj[:n + 1].copy(),
+                "ms": self.ms.value}
+
+
+def _float64_device_graph(G):
+    """The float64 device graph of G: a pygsp_amd graph's own, or the plugin's for a reference pygsp graph."""
+    if hasattr(G, "device_graph"):
+        return G.device_graph(np.float64)
+    from . import plugin
+    return plugin.device_graph_for(G, dtype=np.float64)
+
+
+def _refuse_unknown_keywords(function, kwargs, known):
+    unknown = sorted(set(kwargs) - set(known))
+    if unknown:
+        raise TypeError("{}() got unexpected keyword argument(s) {}".format(
+            function, ", ".join(repr(k) for k in unknown)))
+
+
 class DeviceGraph:
     """Device-resident Laplacian (gspx_graph): built on the GPU from W, or uploaded as L."""
 
@@ -1167,36 +1201,23 @@ class DeviceGraph:
         lab = np.ascontiguousarray(np.asarray(labels).reshape(-1), dtype=np.int32)
         if lab.size != self.N:
             raise ValueError("labels must hold one entry per vertex")
-        n_classes, maxit = int(n_classes), int(maxit)
-        off = lambda v: -1.0 if v is None else float(v)
-        obj = np.zeros(max(maxit, 0) + 1, dtype=np.float64)
-        niter, crit, ms = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0)
+        n_classes, run = int(n_classes), _SolverRun(rtol, atol, dtol, xtol, maxit)
         with self.ctx._temporaries() as t:
             bl, bx = t.upload(lab), t.alloc(self.N * max(n_classes, 1) * 8)
             self.ctx.call(_capi.load().gspx_tikhonov_simplex_dev,
-                self._h, float(tau), float(step), ctypes.c_void_p(bl.ptr), n_classes, off(rtol), off(atol), off(dtol),
-                off(xtol), maxit, ctypes.c_void_p(bx.ptr), ctypes.byref(niter), ctypes.byref(crit), _capi.ptr(obj),
-                ctypes.byref(ms))
+                self._h, float(tau), float(step), ctypes.c_void_p(bl.ptr), n_classes, *run.rule,
+                ctypes.c_void_p(bx.ptr), *run.outputs)
             X = bx.download((self.N, n_classes), np.float64)
-        crits = {1: "ATOL", 2: "DTOL", 3: "RTOL", 4: "XTOL", 5: "MAXIT"}
-        info = {"niter": int(niter.value), "crit": crits.get(crit.value), "objective": obj[:niter.value + 1].copy(),
-                "ms": ms.value}
-        return X, info
+        return X, run.info()
 
     # ---- optimization (proximal operators) ----------------------------------------------------------
     def prox_tv_dev(self, x_ptr, z_ptr, nsig, gamma, step, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
         """gspx_prox_tv_dev on device pointers (N x nsig float64 panels, caller's vertex order); returns info."""
-        maxit = int(maxit)
-        off = lambda v: -1.0 if v is None else float(v)
-        obj = np.zeros(max(maxit, 0) + 1, dtype=np.float64)
-        niter, crit, ms = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0)
+        run = _SolverRun(rtol, atol, dtol, xtol, maxit)
         self.ctx.call(_capi.load().gspx_prox_tv_dev,
-            self._h, float(gamma), float(step), int(nsig), ctypes.c_void_p(x_ptr), ctypes.c_void_p(z_ptr), off(rtol),
-            off(atol), off(dtol), off(xtol), maxit, ctypes.byref(niter), ctypes.byref(crit), _capi.ptr(obj),
-            ctypes.byref(ms))
-        crits = {1: "ATOL", 2: "DTOL", 3: "RTOL", 4: "XTOL", 5: "MAXIT"}
-        return {"niter": int(niter.value), "crit": crits.get(crit.value), "objective": obj[:niter.value + 1].copy(),
-                "ms": ms.value}
+            self._h, float(gamma), float(step), int(nsig), ctypes.c_void_p(x_ptr), ctypes.c_void_p(z_ptr), *run.rule,
+            *run.outputs)
+        return run.info()
 
     def prox_tv(self, x, gamma, step, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
         """argmin_z 1/2 ||x - z||^2 + gamma ||D^T z||_1 for x (N,) or (N, Nsig), Nsig <= 256, by FISTA on the dual

@@ -12,6 +12,8 @@ device (gspx_tikhonov_simplex_dev, DESIGN.md "Simplex-constrained classification
 """
 import numpy as np
 
+from . import engine
+
 
 def _one_hot(labels):
     """Integer class labels -> (N, classes) indicator matrix (what learning.py:36-39 calls logits)."""
@@ -76,13 +78,6 @@ def simplex_step(G, tau):
     return 0.5 / (1 + tau * G.lmax)
 
 
-def _simplex_device_graph(G):
-    if hasattr(G, "device_graph"):
-        return G.device_graph(np.float64)
-    from . import plugin
-    return plugin.device_graph_for(G, dtype=np.float64)
-
-
 def classification_tikhonov_simplex(G, y, M, tau=0.1, **kwargs):
     """Classification on the graph by Tikhonov minimisation, every row of the result on the probability simplex
     (learning.py:111-180): argmin_X tau tr(X^T L X) + sum_i m_i ||X_i - Y_i||^2 subject to X >= 0 and X 1 = 1, Y the
@@ -102,10 +97,7 @@ def classification_tikhonov_simplex(G, y, M, tau=0.1, **kwargs):
 
 def simplex_solve(G, y, M, tau=0.1, **kwargs):
     """classification_tikhonov_simplex that also returns the solver's info dict (niter, crit, objective, ms)."""
-    unknown = sorted(set(kwargs) - set(SIMPLEX_OPTIONS))
-    if unknown:
-        raise TypeError("classification_tikhonov_simplex() got unexpected keyword argument(s) {}".format(
-            ", ".join(repr(k) for k in unknown)))
+    engine._refuse_unknown_keywords("classification_tikhonov_simplex", kwargs, SIMPLEX_OPTIONS)
     if tau <= 0:
         raise ValueError("Tau should be greater than 0.")
     if np.size(M) != G.n_vertices:
@@ -113,4 +105,4 @@ def simplex_solve(G, y, M, tau=0.1, **kwargs):
     labels, n_classes = simplex_labels(y, M)
     opts = {k: kwargs[k] for k in ("rtol", "atol", "dtol", "xtol", "maxit") if k in kwargs}
     step = simplex_step(G, tau)
-    return _simplex_device_graph(G).tikhonov_simplex(tau, step, labels, n_classes, **opts)
+    return engine._float64_device_graph(G).tikhonov_simplex(tau, step, labels, n_classes, **opts)

@@ -23,11 +23,7 @@ def tv_step(G, nu=1):
 def _tv_device_graph(G):
     """The float64 device graph holding G's edge list: its own upper triangle, or Graph.get_edge_list handed over
     for a directed graph or one with self-loops (as Graph.grad / Graph.div do for the graph's compute dtype)."""
-    if hasattr(G, "device_graph"):
-        dev = G.device_graph(np.float64)
-    else:
-        from . import plugin
-        dev = plugin.device_graph_for(G, dtype=np.float64)
+    dev = engine._float64_device_graph(G)
     if G.is_directed() or G.W.diagonal().any():
         if getattr(G, "_edges_given_to", None) is not dev and getattr(dev, "_tv_edges_from", None) is not G.W:
             sources, targets, weights = G.get_edge_list()
@@ -60,9 +56,7 @@ def prox_tv(x, gamma, G, A=None, At=None, nu=1, tol=10e-4, maxit=200, use_matrix
 def prox_tv_solve(x, gamma, G, A=None, At=None, nu=1, tol=10e-4, maxit=200, use_matrix=True, **kwargs):
     """prox_tv that also returns the solver's info dict (niter, crit, objective, ms): one dict for up to 256 columns,
     a list of dicts, one per batch of 256 columns, beyond."""
-    unknown = sorted(set(kwargs) - set(TV_OPTIONS))
-    if unknown:
-        raise TypeError("prox_tv() got unexpected keyword argument(s) {}".format(", ".join(repr(k) for k in unknown)))
+    engine._refuse_unknown_keywords("prox_tv", kwargs, TV_OPTIONS)
     if A is not None or At is not None:
         raise NotImplementedError("prox_tv: A / At are host functions and cannot run inside the device loop")
     gamma = float(gamma)

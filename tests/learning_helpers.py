@@ -12,7 +12,7 @@ import math
 
 import numpy as np
 
-CRITERIA = ("ATOL", "DTOL", "RTOL", "XTOL", "MAXIT")
+from fista_helpers import CRITERIA, assert_rule_is_decisive, momentum, stopping_rule, threshold_between  # noqa: F401
 
 
 def project_simplex(Z):
@@ -76,33 +76,11 @@ def solve(L, labels, n_classes, tau, step, rtol=1e-3, atol=None, dtol=None, xtol
         obj.append(o)
         dx = np.linalg.norm(Xn - X) / math.sqrt(N * n_classes)
         dxs.append(dx)
-        diff = abs(o - prev)
-        den = o if o != 0 else (prev if prev != 0 else 1.0)
-        crit = None
-        if atol is not None and o < atol:
-            crit = "ATOL"
-        elif dtol is not None and diff < dtol:
-            crit = "DTOL"
-        elif rtol is not None and diff / den < rtol:
-            crit = "RTOL"
-        elif xtol is not None and dx < xtol:
-            crit = "XTOL"
-        elif k >= maxit:
-            crit = "MAXIT"
+        crit = stopping_rule(o, prev, dx, k, rtol, atol, dtol, xtol, maxit)
         if crit:
             return Xn, {"niter": k, "crit": crit, "objective": np.array(obj), "dx": np.array(dxs)}
-        tn = (1.0 + math.sqrt(1.0 + 4.0 * t * t)) / 2.0
-        b = (t - 1.0) / tn
-        t = tn
+        t, b = momentum(t)
         Xp, LXp, X, LX = X, LX, Xn, LXn
-
-
-def threshold_between(values, k0):
-    """A threshold that values[k0] falls below by a relative 1e-6 and that no value lies within 1e-9 of (relative): a
-    criterion 'value < threshold' then fires at the same index on both sides of a comparison."""
-    th = values[k0] * (1 + 1e-6)
-    assert np.min(np.abs(np.asarray(values) - th)) > 1e-9 * th
-    return th
 
 
 def golden_problem(g):

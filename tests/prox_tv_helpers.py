@@ -15,7 +15,7 @@ import math
 import numpy as np
 from scipy import sparse
 
-from learning_helpers import threshold_between  # noqa: F401  (the tests take their thresholds from it)
+from fista_helpers import assert_rule_is_decisive, momentum, stopping_rule, threshold_between  # noqa: F401
 
 
 def incidence(W):
@@ -66,38 +66,9 @@ def solve(D, x, gamma, step, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=2
         obj.append(o)
         dx = np.linalg.norm(an - a) / math.sqrt(N * S)
         dxs.append(dx)
-        diff = abs(o - prev)
-        den = o if o != 0 else (prev if prev != 0 else 1.0)
-        crit = None
-        if atol is not None and o < atol:
-            crit = "ATOL"
-        elif dtol is not None and diff < dtol:
-            crit = "DTOL"
-        elif rtol is not None and diff / den < rtol:
-            crit = "RTOL"
-        elif xtol is not None and dx < xtol:
-            crit = "XTOL"
-        elif k >= maxit:
-            crit = "MAXIT"
+        crit = stopping_rule(o, prev, dx, k, rtol, atol, dtol, xtol, maxit)
         if crit:
             z = (x2 - an).reshape(x.shape)
             return z, {"niter": k, "crit": crit, "objective": np.array(obj), "dx": np.array(dxs), "u": un}
-        tn = (1.0 + math.sqrt(1.0 + 4.0 * t * t)) / 2.0
-        b = (t - 1.0) / tn
-        t = tn
+        t, b = momentum(t)
         up, gp, u, g, a = u, g, un, gn, an
-
-
-def assert_rule_is_decisive(info, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200, margin=1e-6):
-    """A condition on the INPUTS of a comparison: at the stopping iteration and at every earlier one, each quantity an
-    enabled criterion compares lies at least a relative `margin` away from its threshold, so that rounding
-    differences between two implementations cannot move niter or crit.  threshold_between puts a threshold at
-    value * (1 + 1e-6), which is that margin exactly up to the rounding of the product: the distance is therefore
-    measured against threshold / (1 + margin), with 1e-9 of slack for that rounding."""
-    obj, dx = info["objective"], info["dx"]
-    for k in range(1, info["niter"] + 1):
-        diff = abs(obj[k] - obj[k - 1])
-        den = obj[k] if obj[k] != 0 else (obj[k - 1] if obj[k - 1] != 0 else 1.0)
-        for value, th in ((obj[k], atol), (diff, dtol), (diff / den, rtol), (dx[k - 1], xtol)):
-            if th is not None:
-                assert abs(value - th) >= margin * (1 - 1e-9) * abs(th) / (1 + margin), (k, value, th)

@@ -3,6 +3,7 @@ iteration (tests/learning_helpers.py): the same niter and stopping criterion, ob
 relative, X within 1e-10, on the golden graph and on sensor graphs up to 100k vertices; every projection build;
 determinism; the float32 mirror graph; the real pygsp through plugin.install(learning=True) where one is importable.
 Needs a real MI355X: `-m gpu`."""
+import ctypes
 import importlib.util
 
 import numpy as np
@@ -10,7 +11,7 @@ import pytest
 
 import learning_helpers as lh
 from conftest import load_golden
-from pygsp_amd import graphs, learning
+from pygsp_amd import _capi, graphs, learning
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +125,29 @@ def test_float32_mirror_graph_gives_the_float64_result():
     X32 = learning.classification_tikhonov_simplex(G32, y, M, tau=0.5)
     assert X32.dtype == np.float64
     assert X32.tobytes() == X64.tobytes()
+
+
+def test_refusals_that_need_a_graph():
+    """The two shared refusals that the host test cannot reach, word for word as before the solvers shared one argument
+    check: a float32 graph, and a panel past 2 GiB (N > 1048544 at 256 classes; it fires before anything is allocated
+    or read, so the label buffer stands in for the result pointer)."""
+    from scipy import sparse
+    n = 1_048_600
+    big = graphs.Graph(sparse.diags([np.ones(n - 1), np.ones(n - 1)], [1, -1]).tocsr()).device_graph(np.float64)
+    small32 = graphs.Graph(sparse.diags([np.ones(4), np.ones(4)], [1, -1]).tocsr(),
+                           compute_dtype=np.float32).device_graph(np.float32)
+    obj = np.zeros(201)
+    niter, crit, ms = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_double()
+    for dev, classes, text in (
+            (small32, 2, "tikhonov_simplex: the graph computes in float32; the solver needs the float64 graph"),
+            (big, 256, "tikhonov_simplex: an N x n_classes panel exceeds 2 GiB")):
+        with dev.ctx._temporaries() as t:
+            lab = t.upload(np.zeros(dev.N, dtype=np.int32))
+            with pytest.raises(ValueError) as e:
+                _capi.check(_capi.load().gspx_tikhonov_simplex_dev(
+                    dev._h, 0.1, 0.2, ctypes.c_void_p(lab.ptr), classes, 1e-3, -1.0, -1.0, -1.0, 200,
+                    ctypes.c_void_p(lab.ptr), ctypes.byref(niter), ctypes.byref(crit), _capi.ptr(obj), ctypes.byref(ms)))
+        assert str(e.value) == text
 
 
 @pytest.mark.skipif(importlib.util.find_spec("pygsp") is None, reason="needs an importable pygsp next to the GPU")

@@ -245,6 +245,23 @@ def test_entry_point_errors(sensor2000):
         dev32.prox_tv(np.zeros(5), 0.1, 0.1)
 
 
+def test_refusals_that_need_a_graph():
+    """The two shared refusals that the host test cannot reach, word for word as before the solvers shared one argument
+    check: a float32 graph, and a panel past 2 GiB (N > 1048544 at 256 columns; it fires before anything is allocated
+    or read, so a small buffer stands in for both panels)."""
+    n = 1_048_600
+    big = graphs.Graph(sparse.diags([np.ones(n - 1), np.ones(n - 1)], [1, -1]).tocsr()).device_graph(np.float64)
+    small32 = graphs.Graph(_path(5), compute_dtype=np.float32).device_graph(np.float32)
+    for dev, nsig, text in (
+            (small32, 1, "prox_tv: the graph computes in float32; the solver needs the float64 graph"),
+            (big, 256, "prox_tv: an N x Nsig or n_edges x Nsig panel exceeds 2 GiB")):
+        with dev.ctx._temporaries() as t:
+            b = t.alloc(4096)
+            with pytest.raises(ValueError) as e:
+                dev.prox_tv_dev(b.ptr, b.ptr, nsig, 0.1, 0.1)
+        assert str(e.value) == text
+
+
 @pytest.mark.skipif(importlib.util.find_spec("pygsp") is None, reason="needs an importable pygsp next to the GPU")
 def test_real_pygsp_through_the_seam():
     import pygsp

@@ -258,3 +258,24 @@ def test_entry_point_refuses_bad_arguments_without_a_device():
                      ({}, "null graph")):
         with pytest.raises(ValueError, match=what):
             _capi.check(call(**kw))
+    # the refusals that every FISTA entry point makes, word for word as before the solvers shared one argument check
+    # (the float32-graph and 2 GiB refusals need a graph: test_refusals_that_need_a_graph in tests/test_gpu_f_learning.py)
+    for kw, text in ((dict(step=-1.0), "tikhonov_simplex: step must be positive and finite"),
+                     (dict(maxit=0), "tikhonov_simplex: maxit must be 1..10000000 (got 0)"),
+                     (dict(maxit=10000001), "tikhonov_simplex: maxit must be 1..10000000 (got 10000001)"),
+                     (dict(classes=257), "tikhonov_simplex: n_classes must be 1..256 (got 257)"),
+                     (dict(xtol=float("nan")),
+                      "tikhonov_simplex: a tolerance is NaN (a negative one disables its criterion)"),
+                     (dict(out=None), "tikhonov_simplex: null host output"),
+                     ({}, "null graph")):
+        with pytest.raises(ValueError) as e:
+            _capi.check(call(**kw))
+        assert str(e.value) == text
+    # in the order of before: tau, step, maxit, n_classes, tolerances, host outputs, graph
+    order = (dict(tau=0.0), dict(step=0.0), dict(maxit=0), dict(classes=0), dict(rtol=float("nan")), dict(out=None))
+    for i, what in enumerate(("tau", "step", "maxit", "n_classes", "NaN", "null host")):
+        bad = {}
+        for later in order[i:]:
+            bad.update(later)
+        with pytest.raises(ValueError, match=what):
+            _capi.check(call(**bad))

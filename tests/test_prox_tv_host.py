@@ -196,3 +196,23 @@ def test_entry_point_refuses_bad_arguments_without_a_device():
                      ({}, "null graph")):
         with pytest.raises(ValueError, match=what):
             _capi.check(call(**kw))
+    # the refusals that every FISTA entry point makes, word for word as before the solvers shared one argument check
+    # (the float32-graph and 2 GiB refusals need a graph: test_refusals_that_need_a_graph in tests/test_gpu_i_prox_tv.py)
+    for kw, text in ((dict(step=0.0), "prox_tv: step must be positive and finite"),
+                     (dict(maxit=0), "prox_tv: maxit must be 1..10000000 (got 0)"),
+                     (dict(maxit=10000001), "prox_tv: maxit must be 1..10000000 (got 10000001)"),
+                     (dict(nsig=257), "prox_tv: number of signals must be 1..256 (got 257)"),
+                     (dict(dtol=float("nan")), "prox_tv: a tolerance is NaN (a negative one disables its criterion)"),
+                     (dict(out=None), "prox_tv: null host output"),
+                     ({}, "null graph")):
+        with pytest.raises(ValueError) as e:
+            _capi.check(call(**kw))
+        assert str(e.value) == text
+    # in the order of before: gamma, step, maxit, number of signals, tolerances, host outputs, graph
+    order = (dict(gamma=-1.0), dict(step=0.0), dict(maxit=0), dict(nsig=0), dict(rtol=float("nan")), dict(out=None))
+    for i, what in enumerate(("gamma", "step", "maxit", "signals", "NaN", "null host")):
+        bad = {}
+        for later in order[i:]:
+            bad.update(later)
+        with pytest.raises(ValueError, match=what):
+            _capi.check(call(**bad))

@@ -109,6 +109,17 @@ int gspx_lanczos_combine_dev(gspx_graph* g, int order, int64_t Nsig, const void*
 int gspx_tikhonov_cg_dev(gspx_graph* g, double tau, const void* mask_dev, int64_t Nsig,
                          const void* y_dev, void* x_dev, double rtol, double atol, int64_t maxiter,
                          int32_t* iterations, double* kernel_ms);
+/* Harmonic extension (regression_tikhonov with tau = 0, pygsp/learning.py:349-367): x = y on the measured vertices
+ * (mask != 0); on the others x_u solves L_uu x_u = -L_ul y_l, one conjugate-gradient run per column, the recurrence
+ * and stopping rule of gspx_tikhonov_cg_dev (x0 = 0, ||r|| < max(atol, rtol ||b||), b = -L_ul y_l), all columns
+ * advanced together.  L is the graph's Laplacian of whatever lap_type it was built with.  y is READ ONLY AT MEASURED
+ * ROWS (a select, not a product: NaN at unmeasured rows is harmless).  A component without a measured vertex has
+ * b = 0 there and keeps x = 0 (the minimum-norm solution; the reference's spsolve fails on it).  mask_dev: N values
+ * of the compute dtype; y_dev, x_dev: N x Nsig, compute dtype, caller's vertex order, distinct buffers; iterations:
+ * Nsig ints (HOST) or NULL; fp32 and fp64 graphs; any Nsig >= 0 in column batches of at most 256.  The same inputs
+ * give the same bits on every call. */
+int gspx_dirichlet_cg_dev(gspx_graph* g, const void* mask_dev, int64_t Nsig, const void* y_dev, void* x_dev,
+                          double rtol, double atol, int64_t maxiter, int32_t* iterations, double* kernel_ms);
 /* classification_tikhonov_simplex (pygsp/learning.py:111-180): argmin over X (N x n_classes, every row on the
  * probability simplex) of tau sum(X * L X) + sum_i m_i ||X_i - Y_i||^2, by accelerated forward-backward (FISTA) with
  * the fixed `step`, started at X_0 = Y; Y is one-hot, zero rows where unmeasured.  float64 graphs only.

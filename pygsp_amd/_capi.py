@@ -91,6 +91,7 @@ SIGNATURES = {
     "gspx_lanczos_combine_dev": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _c.c_int, _P, _P, _c.c_int64, _P]),
     "gspx_tikhonov_cg_dev": (_c.c_int, [_P, _c.c_double, _P, _c.c_int64, _P, _P, _c.c_double,
                                          _c.c_double, _c.c_int64, _P, _P]),
+    "gspx_dirichlet_cg_dev": (_c.c_int, [_P, _P, _c.c_int64, _P, _P, _c.c_double, _c.c_double, _c.c_int64, _P, _P]),
     "gspx_tikhonov_simplex_dev": (_c.c_int, [_P, _c.c_double, _c.c_double, _P, _c.c_int, _c.c_double, _c.c_double,
                                               _c.c_double, _c.c_double, _c.c_int64, _P, _c.POINTER(_c.c_int64),
                                               _c.POINTER(_c.c_int32), _P, _c.POINTER(_c.c_double)]),

@@ -159,11 +159,106 @@ extern "C" int gspx_dirichlet_energy_dev(gspx_graph* g, int64_t Nsig, const void
                               : dirichlet_t<double>(g, Nsig, (const double*)x_dev, gram_host, kernel_ms);
 }
 
-// ---- Tikhonov regression, tau > 0: (diag(M) + tau L) x = M y by conjugate gradients ----------------
+// ---- conjugate gradients, one system per column: what the two learners below share ----------------------
 // One independent system per column, all columns advanced together; the recurrence and the stopping
 // rule are those of scipy.sparse.linalg.cg (x0 = 0, no preconditioner; stop when
 // ||r|| < max(atol, rtol ||b||), checked at the top of every iteration), which is what
 // learning.regression_tikhonov calls column by column (learning.py:324-337).
+template <typename T> struct CgPanels { T *X, *R, *P, *Q, *B; };  // N x ld each, internal vertex order
+
+static int64_t cg_max_ld(gspx_graph* g, size_t elt) { return std::min<int64_t>(ops_max_ld(g, elt, 5), 256); }
+
+template <typename T> static int cg_panels(gspx_graph* g, unsigned ld, CgPanels<T>* w) {
+  const size_t U = (size_t)g->N * ld;
+  CHK(g->ctx->ws_t.ensure(5 * U * sizeof(T) + 256));
+  w->X = g->ctx->ws_t.as<T>();
+  w->R = w->X + U;
+  w->P = w->R + U;
+  w->Q = w->P + U;
+  w->B = w->Q + U;
+  return GSPX_OK;
+}
+
+// The iteration on one column batch: A = `vals` on the graph's internal CSR pattern, the right-hand side already in
+// w.R; leaves the solution in w.X (internal order) and the counts in iters[0 .. ld) (HOST, may be null).  w.B is not
+// touched.  scal / partial: the callers' scratch, grown here and kept from batch to batch.
+template <typename T>
+static int cg_iterate(gspx_graph* g, const T* vals, const CgPanels<T>& w, unsigned ld, double rtol, double atol,
+                      int64_t maxiter, DevMem& scal, DevMem& partial, int32_t* iters) {
+  gspx_ctx* ctx = g->ctx;
+  hipStream_t st = ctx->stream;
+  const int64_t N = g->N;
+  const int nred = (int)std::min<int64_t>(4096, std::max<int64_t>(1, N / 64));
+  const int ldp = col_pow2((int)ld);
+  const size_t U = (size_t)N * ld;
+  T *X = w.X, *R = w.R, *P = w.P, *Q = w.Q;
+  CHK(scal.ensure((size_t)ld * (7 * sizeof(double) + 2 * sizeof(int)) + 64));
+  CHK(partial.ensure((size_t)nred * ld * sizeof(double)));
+  CgScalars s;
+  double* d = scal.as<double>();
+  s.rho_prev = d; s.rho_cur = d + ld; s.pq = d + 2 * ld; s.atol = d + 3 * ld; s.alpha = d + 4 * ld;
+  s.beta = d + 5 * ld;
+  double* rr = d + 6 * ld;
+  s.active = (int*)(d + 7 * ld);
+  s.iters = s.active + ld;
+  s.any_active = s.iters + ld;
+  const unsigned nbU = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
+  const int nbl = (int)((ld + 63) / 64);
+  auto coldot = [&](const T* a_, const T* b_, double* out) {
+    hipLaunchKernelGGL((k_coldot_partial<T>), dim3(nred), dim3(256), 0, st, a_, b_, (int)N, (int)ld,
+                       ldp, partial.as<double>());
+    sum_parts(partial.as<double>(), nred, ld, out, st);
+  };
+  HIPCHK(hipMemsetAsync(X, 0, U * sizeof(T), st));
+  HIPCHK(hipMemsetAsync(P, 0, U * sizeof(T), st));
+  coldot(R, R, rr);
+  hipLaunchKernelGGL(k_cg_init, dim3(nbl), dim3(64), 0, st, s, rr, (int)ld, rtol, atol);
+  for (int64_t it = 0; it < maxiter; ++it) {
+    // (rr = ||r||^2 per column: from the coldot above for the first iteration, afterwards accumulated by the
+    // update kernel of the previous one - k_cg_xr_dot - in the very same order)
+    HIPCHK(hipMemsetAsync(s.any_active, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_cg_pre, dim3(nbl), dim3(64), 0, st, s, rr, (int)ld, it == 0 ? 1 : 0);
+    // every fourth iteration the host looks whether any column is still active (a device-to-host copy and a
+    // stream synchronisation: ~30 us of a 0.4 ms iteration); in between the device carries on - converged columns
+    // are frozen by their `active` flag, so up to three iterations at the end do nothing and change nothing
+    if (it < 2 || (it & 3) == 0 || it + 1 == maxiter) {
+      int any = 0;
+      HIPCHK(hipMemcpyAsync(&any, s.any_active, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      if (!any) break;
+    }
+    hipLaunchKernelGGL((k_cg_p<T>), dim3(nbU), dim3(256), 0, st, R, P, U, (int)ld, s);
+    CHK(spmm_internal<T>(g, vals, T(1), T(0), P, Q, ld, nullptr, 0));
+    coldot(P, Q, s.pq);
+    hipLaunchKernelGGL(k_cg_post, dim3(nbl), dim3(64), 0, st, s, s.pq, (int)ld);
+    hipLaunchKernelGGL((k_cg_xr_dot<T>), dim3(nred), dim3(256), 0, st, X, R, P, Q, (int)N, (int)ld, ldp, s,
+                       partial.as<double>());
+    sum_parts(partial.as<double>(), nred, ld, rr, st);
+  }
+  if (iters) {
+    std::vector<int> hi(ld);
+    HIPCHK(hipMemcpyAsync(hi.data(), s.iters, ld * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (unsigned c = 0; c < ld; ++c) iters[c] = hi[c];
+  }
+  return GSPX_OK;
+}
+
+// columns [c0, c0 + ld) of the caller's N x Nsig result from the internal-order panel X
+template <typename T>
+static int cg_store(gspx_graph* g, const T* X, unsigned ld, T* x, int64_t c0, int64_t Nsig) {
+  if ((int64_t)ld == Nsig) return permute_panel<T>(g, X, ld, x, ld, g->has_perm ? g->iperm.as<int>() : nullptr);
+  // a column batch of a wider result: ld columns into rows of pitch Nsig (permute_panel copies whole rows of
+  // the output's pitch: it would carry Nsig columns of every row of X, over the other batches' columns and,
+  // from the second batch on, c0 elements past the end of x)
+  const size_t U = (size_t)g->N * ld;
+  const unsigned nbo = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
+  hipLaunchKernelGGL((k_permute_out_pad<T>), dim3(nbo), dim3(256), 0, g->ctx->stream, X, ld, x + c0, (unsigned)Nsig,
+                     ld, (int)g->N, g->has_perm ? g->perm.as<int>() : nullptr);
+  return GSPX_OK;
+}
+
+// ---- Tikhonov regression, tau > 0: (diag(M) + tau L) x = M y by conjugate gradients ----------------
 template <typename T>
 static int tikhonov_t(gspx_graph* g, double tau, const T* mask, int64_t Nsig, const T* y, T* x,
                       double rtol, double atol, int64_t maxiter, int32_t* iters, double* ms) {
@@ -172,10 +267,9 @@ static int tikhonov_t(gspx_graph* g, double tau, const T* mask, int64_t Nsig, co
   const int64_t N = g->N;
   if (ms) *ms = 0;
   if (N == 0 || Nsig == 0) return GSPX_OK;
-  int64_t max_ld = std::min<int64_t>(ops_max_ld(g, sizeof(T), 5), 256);
+  const int64_t max_ld = cg_max_ld(g, sizeof(T));
   if (max_ld < 1) return set_err(GSPX_ERR_INVALID, "graph too large: one signal column exceeds 2 GiB");
   const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
-  const int* iperm = g->has_perm ? g->iperm.as<int>() : nullptr;
   const int nbN = std::max(1, (int)((N + 255) / 256));
   // A = tau L + diag(M) on the internal layout
   DevMem mint, aval, scal, partial;
@@ -186,82 +280,30 @@ static int tikhonov_t(gspx_graph* g, double tau, const T* mask, int64_t Nsig, co
   CHK(permute_panel<T>(g, mask, 1, mint.as<T>(), 1, perm));
   hipLaunchKernelGGL((k_affine_values<T>), dim3(nbN), dim3(256), 0, st, g->rptr.as<int>(),
                      g->rcol.as<int>(), g->rval.as<T>(), (int)N, (T)tau, mint.as<T>(), aval.as<T>());
-  const int nred = (int)std::min<int64_t>(4096, std::max<int64_t>(1, N / 64));
   for (int64_t c0 = 0; c0 < Nsig; c0 += max_ld) {
     const unsigned ld = (unsigned)std::min<int64_t>(max_ld, Nsig - c0);
-    const int ldp = col_pow2((int)ld);
     const size_t U = (size_t)N * ld;
-    CHK(ctx->ws_t.ensure(5 * U * sizeof(T) + 256));
-    T* X = ctx->ws_t.as<T>();
-    T* R = X + U;
-    T* P = R + U;
-    T* Q = P + U;
-    T* B = Q + U;
-    CHK(scal.ensure((size_t)ld * (7 * sizeof(double) + 2 * sizeof(int)) + 64));
-    CHK(partial.ensure((size_t)nred * ld * sizeof(double)));
-    CgScalars s;
-    double* d = scal.as<double>();
-    s.rho_prev = d; s.rho_cur = d + ld; s.pq = d + 2 * ld; s.atol = d + 3 * ld; s.alpha = d + 4 * ld;
-    s.beta = d + 5 * ld;
-    double* rr = d + 6 * ld;
-    s.active = (int*)(d + 7 * ld);
-    s.iters = s.active + ld;
-    s.any_active = s.iters + ld;
+    CgPanels<T> w;
+    CHK(cg_panels<T>(g, ld, &w));
     const unsigned nbU = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
-    const int nbl = (int)((ld + 63) / 64);
-    auto coldot = [&](const T* a_, const T* b_, double* out) {
-      hipLaunchKernelGGL((k_coldot_partial<T>), dim3(nred), dim3(256), 0, st, a_, b_, (int)N, (int)ld,
-                         ldp, partial.as<double>());
-      sum_parts(partial.as<double>(), nred, ld, out, st);
-    };
-    // b = M y (learning.py:325-326 zeroes the unmeasured entries), r = b, x = 0
-    CHK(permute_panel<T>(g, y + c0, (unsigned)Nsig, B, ld, perm));
-    hipLaunchKernelGGL((k_rowscale<T>), dim3(nbU), dim3(256), 0, st, mint.as<T>(), B, R, U, (int)ld);
-    HIPCHK(hipMemsetAsync(X, 0, U * sizeof(T), st));
-    HIPCHK(hipMemsetAsync(P, 0, U * sizeof(T), st));
-    coldot(R, R, rr);
-    hipLaunchKernelGGL(k_cg_init, dim3(nbl), dim3(64), 0, st, s, rr, (int)ld, rtol, atol);
-    for (int64_t it = 0; it < maxiter; ++it) {
-      // (rr = ||r||^2 per column: from the coldot above for the first iteration, afterwards accumulated by the
-      // update kernel of the previous one - k_cg_xr_dot - in the very same order)
-      HIPCHK(hipMemsetAsync(s.any_active, 0, sizeof(int), st));
-      hipLaunchKernelGGL(k_cg_pre, dim3(nbl), dim3(64), 0, st, s, rr, (int)ld, it == 0 ? 1 : 0);
-      // every fourth iteration the host looks whether any column is still active (a device-to-host copy and a
-      // stream synchronisation: ~30 us of a 0.4 ms iteration); in between the device carries on - converged columns
-      // are frozen by their `active` flag, so up to three iterations at the end do nothing and change nothing
-      if (it < 2 || (it & 3) == 0 || it + 1 == maxiter) {
-        int any = 0;
-        HIPCHK(hipMemcpyAsync(&any, s.any_active, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (!any) break;
-      }
-      hipLaunchKernelGGL((k_cg_p<T>), dim3(nbU), dim3(256), 0, st, R, P, U, (int)ld, s);
-      CHK(spmm_internal<T>(g, aval.as<T>(), T(1), T(0), P, Q, ld, nullptr, 0));
-      coldot(P, Q, s.pq);
-      hipLaunchKernelGGL(k_cg_post, dim3(nbl), dim3(64), 0, st, s, s.pq, (int)ld);
-      hipLaunchKernelGGL((k_cg_xr_dot<T>), dim3(nred), dim3(256), 0, st, X, R, P, Q, (int)N, (int)ld, ldp, s,
-                         partial.as<double>());
-      sum_parts(partial.as<double>(), nred, ld, rr, st);
-    }
-    if ((int64_t)ld == Nsig) {
-      CHK(permute_panel<T>(g, X, ld, x, ld, iperm));
-    } else {
-      // a column batch of a wider result: ld columns into rows of pitch Nsig (permute_panel copies whole rows of
-      // the output's pitch: it would carry Nsig columns of every row of X, over the other batches' columns and,
-      // from the second batch on, c0 elements past the end of x)
-      const unsigned nbo = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
-      hipLaunchKernelGGL((k_permute_out_pad<T>), dim3(nbo), dim3(256), 0, st, X, ld, x + c0, (unsigned)Nsig, ld, (int)N,
-                         perm);
-    }
-    if (iters) {
-      std::vector<int> hi(ld);
-      HIPCHK(hipMemcpyAsync(hi.data(), s.iters, ld * sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      for (unsigned c = 0; c < ld; ++c) iters[c0 + c] = hi[c];
-    }
+    // b = M y (learning.py:325-326 zeroes the unmeasured entries), r = b
+    CHK(permute_panel<T>(g, y + c0, (unsigned)Nsig, w.B, ld, perm));
+    hipLaunchKernelGGL((k_rowscale<T>), dim3(nbU), dim3(256), 0, st, mint.as<T>(), w.B, w.R, U, (int)ld);
+    CHK(cg_iterate<T>(g, aval.as<T>(), w, ld, rtol, atol, maxiter, scal, partial, iters ? iters + c0 : nullptr));
+    CHK(cg_store<T>(g, w.X, ld, x, c0, Nsig));
   }
   HIPCHK(hipEventRecord(ctx->ev[1], st));
   return finish_timed(ctx, ms);
+}
+
+// the argument checks the two conjugate-gradient entry points share
+static int cg_check_args(const char* who, gspx_graph* g, const void* mask_dev, int64_t Nsig, const void* y_dev,
+                         const void* x_dev, double rtol, double atol, int64_t maxiter) {
+  if (Nsig < 0 || maxiter < 0 || !(rtol >= 0) || !(atol >= 0))
+    return set_err(GSPX_ERR_INVALID, "%s: bad argument", who);
+  if (Nsig > 0 && g->N > 0 && (!mask_dev || !y_dev || !x_dev))
+    return set_err(GSPX_ERR_INVALID, "null pointer");
+  return GSPX_OK;
 }
 
 extern "C" int gspx_tikhonov_cg_dev(gspx_graph* g, double tau, const void* mask_dev, int64_t Nsig,
@@ -270,16 +312,71 @@ extern "C" int gspx_tikhonov_cg_dev(gspx_graph* g, double tau, const void* mask_
   if (g) replay_reset(g->ctx);
   if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
   if (!(tau > 0) || !std::isfinite(tau)) return set_err(GSPX_ERR_INVALID, "tau must be positive and finite");
-  if (Nsig < 0 || maxiter < 0 || !(rtol >= 0) || !(atol >= 0))
-    return set_err(GSPX_ERR_INVALID, "tikhonov_cg: bad argument");
-  if (Nsig > 0 && g->N > 0 && (!mask_dev || !y_dev || !x_dev))
-    return set_err(GSPX_ERR_INVALID, "null pointer");
+  CHK(cg_check_args("tikhonov_cg", g, mask_dev, Nsig, y_dev, x_dev, rtol, atol, maxiter));
   HIPCHK(hipSetDevice(g->ctx->device));
   return g->dtype == GSPX_F32
              ? tikhonov_t<float>(g, tau, (const float*)mask_dev, Nsig, (const float*)y_dev,
                                  (float*)x_dev, rtol, atol, maxiter, iterations, kernel_ms)
              : tikhonov_t<double>(g, tau, (const double*)mask_dev, Nsig, (const double*)y_dev,
                                   (double*)x_dev, rtol, atol, maxiter, iterations, kernel_ms);
+}
+
+// ---- harmonic extension (regression_tikhonov with tau = 0, learning.py:349-367) ------------------------
+// x = y on the measured vertices, L_uu x_u = -L_ul y_l on the others.  The operator is one more value array on the
+// graph's CSR pattern (k_dirichlet_values: P_u L P_u); with r = p = 0 on the measured rows from the start every
+// iterate stays zero there, so cg_iterate runs CG on the block L_uu, which is positive definite on every component
+// that holds a measured vertex.  On a component without one b = 0 and x stays 0.
+template <typename T>
+static int dirichlet_cg_t(gspx_graph* g, const T* mask, int64_t Nsig, const T* y, T* x, double rtol, double atol,
+                          int64_t maxiter, int32_t* iters, double* ms) {
+  gspx_ctx* ctx = g->ctx;
+  hipStream_t st = ctx->stream;
+  const int64_t N = g->N;
+  if (ms) *ms = 0;
+  if (N == 0 || Nsig == 0) return GSPX_OK;
+  const int64_t max_ld = cg_max_ld(g, sizeof(T));
+  if (max_ld < 1) return set_err(GSPX_ERR_INVALID, "graph too large: one signal column exceeds 2 GiB");
+  const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
+  const int nbN = std::max(1, (int)((N + 255) / 256));
+  DevMem mint, aval, scal, partial;
+  CHK(mint.alloc((size_t)N * sizeof(T)));
+  CHK(aval.alloc(((size_t)g->nnz_int + 64) * sizeof(T)));
+  HIPCHK(hipMemsetAsync(aval.p, 0, ((size_t)g->nnz_int + 64) * sizeof(T), st));
+  HIPCHK(hipEventRecord(ctx->ev[0], st));
+  CHK(permute_panel<T>(g, mask, 1, mint.as<T>(), 1, perm));
+  hipLaunchKernelGGL((k_dirichlet_values<T>), dim3(nbN), dim3(256), 0, st, g->rptr.as<int>(), g->rcol.as<int>(),
+                     g->rval.as<T>(), (int)N, mint.as<T>(), aval.as<T>());
+  for (int64_t c0 = 0; c0 < Nsig; c0 += max_ld) {
+    const unsigned ld = (unsigned)std::min<int64_t>(max_ld, Nsig - c0);
+    const size_t U = (size_t)N * ld;
+    CgPanels<T> w;
+    CHK(cg_panels<T>(g, ld, &w));
+    const unsigned nbU = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
+    // B = y where measured, 0 elsewhere (y is read there, never multiplied); r = -(L B) on the unmeasured rows
+    CHK(permute_panel<T>(g, y + c0, (unsigned)Nsig, w.B, ld, perm));
+    hipLaunchKernelGGL((k_dirichlet_select<T>), dim3(nbU), dim3(256), 0, st, mint.as<T>(), w.B, U, (int)ld);
+    CHK(spmm_internal<T>(g, g->rval.as<T>(), T(1), T(0), w.B, w.Q, ld, nullptr, 0));
+    hipLaunchKernelGGL((k_dirichlet_rhs<T>), dim3(nbU), dim3(256), 0, st, mint.as<T>(), w.Q, w.R, U, (int)ld);
+    CHK(cg_iterate<T>(g, aval.as<T>(), w, ld, rtol, atol, maxiter, scal, partial, iters ? iters + c0 : nullptr));
+    hipLaunchKernelGGL((k_dirichlet_merge<T>), dim3(nbU), dim3(256), 0, st, mint.as<T>(), w.B, w.X, U, (int)ld);
+    CHK(cg_store<T>(g, w.X, ld, x, c0, Nsig));
+  }
+  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  return finish_timed(ctx, ms);
+}
+
+extern "C" int gspx_dirichlet_cg_dev(gspx_graph* g, const void* mask_dev, int64_t Nsig, const void* y_dev,
+                                     void* x_dev, double rtol, double atol, int64_t maxiter, int32_t* iterations,
+                                     double* kernel_ms) {
+  if (g) replay_reset(g->ctx);
+  if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
+  CHK(cg_check_args("dirichlet_cg", g, mask_dev, Nsig, y_dev, x_dev, rtol, atol, maxiter));
+  HIPCHK(hipSetDevice(g->ctx->device));
+  return g->dtype == GSPX_F32
+             ? dirichlet_cg_t<float>(g, (const float*)mask_dev, Nsig, (const float*)y_dev, (float*)x_dev, rtol, atol,
+                                     maxiter, iterations, kernel_ms)
+             : dirichlet_cg_t<double>(g, (const double*)mask_dev, Nsig, (const double*)y_dev, (double*)x_dev, rtol,
+                                      atol, maxiter, iterations, kernel_ms);
 }
 
 // ---- differential operator (undirected graphs, no self loops) ------------------------------------------

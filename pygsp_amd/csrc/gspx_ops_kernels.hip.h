@@ -8,6 +8,7 @@
 //   compute_differential_operator   pygsp/graphs/difference.py:26-166  D (incidence matrix)
 //   grad / div                      pygsp/graphs/difference.py:168-331 D.T.dot(x), D.dot(y)
 //   regression_tikhonov (tau > 0)   pygsp/learning.py:324-337          scipy.sparse.linalg.cg
+//   regression_tikhonov (tau = 0)   pygsp/learning.py:349-367          spsolve(L_uu, -L_ul y_l): here CG on L_uu
 #pragma once
 
 #include "gspx_kernels.hip.h"
@@ -29,6 +30,45 @@ __global__ void k_affine_values(const int* __restrict__ rptr, const int* __restr
     if (c == i) v += mi;
     out[j] = (c == N) ? T(0) : v;
   }
+}
+
+// A = P_u L P_u on the internal layout, P_u = diag(m == 0): the entries of L between two unmeasured vertices, zero
+// elsewhere, so that CG on it with r = p = 0 on the measured rows is CG on the block L_uu (harmonic extension).
+// m is indexed by internal row and has N entries: a pad (col == N) is recognised before m is read.
+template <typename T>
+__global__ void k_dirichlet_values(const int* __restrict__ rptr, const int* __restrict__ rcol,
+                                   const T* __restrict__ rval, int N, const T* __restrict__ m,
+                                   T* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const bool free_row = m[i] == T(0);
+  for (int j = rptr[i] & ~3; j < (rptr[i + 1] & ~3); ++j) {
+    const int c = rcol[j];
+    out[j] = (c != N && free_row && m[c] == T(0)) ? rval[j] : T(0);
+  }
+}
+// b[i][c] = m[i] != 0 ? b[i][c] : 0 in place (a select: NaN at an unmeasured row does not get through)
+template <typename T>
+__global__ void k_dirichlet_select(const T* __restrict__ m, T* __restrict__ b, size_t total, int ld) {
+  const unsigned n = (unsigned)total, step = gridDim.x * blockDim.x;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+    if (m[i / (unsigned)ld] == T(0)) b[i] = T(0);
+}
+// r = -(L b) on the unmeasured rows, 0 on the measured ones (q = L b): the right-hand side -L_ul y_l, embedded
+template <typename T>
+__global__ void k_dirichlet_rhs(const T* __restrict__ m, const T* __restrict__ q, T* __restrict__ r,
+                                size_t total, int ld) {
+  const unsigned n = (unsigned)total, step = gridDim.x * blockDim.x;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+    r[i] = m[i / (unsigned)ld] == T(0) ? -q[i] : T(0);
+}
+// x = b on the measured rows (the iterate is zero there), untouched elsewhere
+template <typename T>
+__global__ void k_dirichlet_merge(const T* __restrict__ m, const T* __restrict__ b, T* __restrict__ x,
+                                  size_t total, int ld) {
+  const unsigned n = (unsigned)total, step = gridDim.x * blockDim.x;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step)
+    if (m[i / (unsigned)ld] != T(0)) x[i] = b[i];
 }
 
 // ---- column-wise reductions over N x ld row-major panels ------------------------------------------

@@ -1190,6 +1190,31 @@ class DeviceGraph:
             x = bx.download(y2.shape, self.dtype)
         return (x[:, 0] if one_d else x), iters, ms
 
+    def dirichlet_cg_dev(self, mask_ptr, y_ptr, x_ptr, nsig, rtol=None, atol=0.0, maxiter=None):
+        rtol = (1e-10 if self.dtype == np.float64 else 1e-5) if rtol is None else float(rtol)
+        maxiter = 10 * self.N if maxiter is None else int(maxiter)
+        iters = np.zeros(max(int(nsig), 1), dtype=np.int32)
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_dirichlet_cg_dev,
+            self._h, ctypes.c_void_p(mask_ptr), int(nsig), ctypes.c_void_p(y_ptr), ctypes.c_void_p(x_ptr), rtol,
+            float(atol), maxiter, _capi.ptr(iters), ctypes.byref(ms))
+        return iters[:int(nsig)], ms.value
+
+    def dirichlet_cg(self, mask, y, rtol=None, atol=0.0, maxiter=None):
+        """Harmonic extension: x = y on the measured vertices (mask != 0) and L_uu x_u = -L_ul y_l on the others,
+        per column by conjugate gradients (gspx_dirichlet_cg_dev); y is read at measured vertices only.  rtol None:
+        1e-10 on a float64 graph, 1e-5 on a float32 one; maxiter None: 10 N.  Returns (x, iterations per column,
+        device ms)."""
+        y2, one_d = self._panel(y, self.N, "dirichlet_cg")
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=self.dtype)
+        if m.size != self.N:
+            raise ValueError("M should be of size [G.n_vertices,]")
+        with self.ctx._temporaries() as t:
+            bm, by, bx = t.upload(m), t.upload(y2), t.alloc(y2.nbytes)
+            iters, ms = self.dirichlet_cg_dev(bm.ptr, by.ptr, bx.ptr, y2.shape[1], rtol, atol, maxiter)
+            x = bx.download(y2.shape, self.dtype)
+        return (x[:, 0] if one_d else x), iters, ms
+
     def tikhonov_simplex(self, tau, step, labels, n_classes, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
         """FISTA on the simplex-constrained Tikhonov problem of learning.classification_tikhonov_simplex
         (gspx_tikhonov_simplex_dev), on this float64 graph.  labels: N ints in the graph's vertex order, the class

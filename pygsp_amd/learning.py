@@ -1,10 +1,15 @@
-"""Mirror of pygsp.learning for the solver loop that runs on the device.
+"""Mirror of pygsp.learning for the solver loops that run on the device.
 
 regression_tikhonov / classification_tikhonov with tau > 0 solve (diag(M) + tau L) x = M y by
 conjugate gradients (pygsp/learning.py:324-337, one scipy.sparse.linalg.cg call per column); here
 all columns advance together on the GPU with the same recurrence and stopping rule
-(gspx_tikhonov_cg_dev).  The tau = 0 branch of the reference is a direct sparse solve
-(spsolve, learning.py:342-367), not a sparse-product loop: it is not part of this engine and raises.
+(gspx_tikhonov_cg_dev).
+
+tau = 0, the reference's default, is harmonic interpolation: x = y on the measured vertices and L_uu x_u = -L_ul y_l
+on the others, which the reference hands to a direct sparse solve (spsolve, learning.py:349-367).  L_uu is symmetric
+positive definite on every component that holds a measured vertex, so the same conjugate-gradient loop solves it on
+the device (gspx_dirichlet_cg_dev, DESIGN.md "Harmonic extension").  It is an iterative answer where the reference
+gives a direct one, so it is opt-in: ``solver="cg"``; without it tau = 0 raises as before.
 
 classification_tikhonov_simplex (learning.py:111-180) keeps every row of the solution on the probability simplex.
 The reference hands it to pyunlocbox's accelerated forward-backward solver; here the same iteration runs on the
@@ -29,24 +34,35 @@ def _measured_only(y, mask):
     return out, keep
 
 
-def regression_tikhonov(G, y, M, tau=0, rtol=1e-5, atol=0.0, maxiter=None):
-    """argmin_x ||M x - y||^2 + tau x^T L x for tau > 0 (learning.py:254-337).
+def regression_tikhonov(G, y, M, tau=0, rtol=None, atol=0.0, maxiter=None, solver=None):
+    """argmin_x ||M x - y||^2 + tau x^T L x for tau > 0 (learning.py:254-337); for tau = 0 and ``solver="cg"``
+    argmin_x x^T L x subject to x = y on the measured vertices (learning.py:349-367).
 
     y: (N,) or (N, Nsig) measurements, M: boolean mask of the measured vertices.  rtol / atol /
-    maxiter are scipy.sparse.linalg.cg's (the reference uses its defaults).
+    maxiter are scipy.sparse.linalg.cg's; rtol None is 1e-5 for tau > 0 (the reference uses scipy's defaults) and,
+    for tau = 0, 1e-10 on a float64 graph and 1e-5 on a float32 one (the reference solves that branch directly).
+    solver: None or "cg".  tau = 0 runs on the device with "cg" only and raises NotImplementedError without it; on
+    a component without a measured vertex the "cg" answer is zero (the reference's spsolve fails there).
     """
     if np.size(M) != G.n_vertices:
         raise ValueError("M should be of size [G.n_vertices,]")
-    if not tau > 0:
-        raise NotImplementedError("tau = 0 is a direct sparse solve in the reference "
-                                  "(learning.py:342-367), not a device path; use tau > 0")
+    if solver not in (None, "cg"):
+        raise ValueError("solver must be None or 'cg', got {!r}".format(solver))
     rhs, keep = _measured_only(y, M)
-    solution, _, _ = G.device_graph().tikhonov_cg(tau, keep, rhs, rtol=rtol, atol=atol, maxiter=maxiter)
+    if tau > 0:
+        solution, _, _ = G.device_graph().tikhonov_cg(tau, keep, rhs, rtol=1e-5 if rtol is None else rtol, atol=atol,
+                                                      maxiter=maxiter)
+    elif tau == 0 and solver == "cg":
+        solution, _, _ = G.device_graph().dirichlet_cg(keep, rhs, rtol=rtol, atol=atol, maxiter=maxiter)
+    else:
+        raise NotImplementedError("tau = 0 is a direct sparse solve in the reference (learning.py:342-367); pass "
+                                  "solver=\"cg\" for conjugate gradients on the device, or use tau > 0")
     return solution
 
 
 def classification_tikhonov(G, y, M, tau=0, **kwargs):
-    """Tikhonov regression of the one-hot encoded labels (learning.py:170-251)."""
+    """Tikhonov regression of the one-hot encoded labels (learning.py:170-251); the keywords are
+    regression_tikhonov's (tau = 0 needs ``solver="cg"``)."""
     labels, _ = _measured_only(y, M)
     return regression_tikhonov(G, _one_hot(labels), M, tau, **kwargs)
 

@@ -229,20 +229,25 @@ def _feature_functions(pygsp_module, saved):
 _LEARNING = ("classification_tikhonov_simplex", "regression_tikhonov")
 
 
-def _learning_functions(saved):
+def _learning_functions(saved, harmonic=False):
     """classification_tikhonov_simplex on the device (pygsp_amd.learning, no pyunlocbox) and regression_tikhonov whose
-    tau > 0 branch with a sparse L runs the device conjugate gradients; tau <= 0 and a dense L call the saved
-    original.  classification_tikhonov looks regression_tikhonov up at call time and follows."""
+    tau > 0 branch with a sparse L runs the device conjugate gradients and, with `harmonic`, whose tau = 0 branch
+    runs them on L_uu (DeviceGraph.dirichlet_cg at its default rtol); tau < 0, a dense L and, without `harmonic`,
+    tau = 0 call the saved original.  classification_tikhonov looks regression_tikhonov up at call time and follows."""
     from . import learning
 
     def regression_tikhonov(G, y, M, tau=0):
-        if not (tau > 0 and sparse.issparse(G.L)):
+        on_device = tau > 0 or (harmonic and tau == 0)
+        if not (on_device and sparse.issparse(G.L)):
             return saved["regression_tikhonov"](G, y, M, tau)
         keep = np.asarray(M).reshape(-1).astype(bool)
         y = np.array(y, dtype=np.float64, copy=True)
         y[~keep] = 0  # (learning.py:326: NaN may sit at unmeasured vertices)
-        # the reference's cg with scipy's defaults: rtol 1e-5, atol 0, maxiter 10 N (learning.py:328-335)
-        solution, _, _ = device_graph_for(G).tikhonov_cg(tau, keep, y)
+        if tau > 0:
+            # the reference's cg with scipy's defaults: rtol 1e-5, atol 0, maxiter 10 N (learning.py:328-335)
+            solution, _, _ = device_graph_for(G).tikhonov_cg(tau, keep, y)
+        else:
+            solution, _, _ = device_graph_for(G).dirichlet_cg(keep, y)
         return np.asarray(solution, dtype=np.float64)
 
     def classification_tikhonov_simplex(G, y, M, tau=0.1, **kwargs):
@@ -311,7 +316,7 @@ def _extract_components_on_device(self):
 
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
-            lanczos=False, features=False, learning=False, topology=False, optimization=False):
+            lanczos=False, features=False, learning=False, topology=False, optimization=False, harmonic=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -336,6 +341,10 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     `learning` (default False): also replace ``pygsp.learning.classification_tikhonov_simplex`` (on the device, without
     pyunlocbox) and ``regression_tikhonov`` (tau > 0 with a sparse L: the device conjugate gradients; otherwise the
     original); ``classification_tikhonov`` looks ``regression_tikhonov`` up at call time and follows.
+    `harmonic` (default False; needs ``learning=True``): the wrapped ``regression_tikhonov`` also serves tau = 0, the
+    reference's default, with a sparse L on the device: conjugate gradients on L_uu (gspx_dirichlet_cg_dev, rtol 1e-10
+    on a float64 graph, 1e-5 on a float32 one) where the reference calls spsolve.  An iterative answer in place of a
+    direct one, hence its own flag; a component without a measured vertex gets zeros where spsolve fails.
     `topology` (default False): also replace ``Graph.is_connected`` and ``Graph.extract_components`` so that undirected
     graphs are labelled on the device (gspx_graph_components); directed graphs keep the reference's code.
     `optimization` (default False): also replace ``pygsp.optimization.prox_tv`` with pygsp_amd.optimization.prox_tv (the
@@ -346,6 +355,8 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         raise ValueError("laplacian must be 'device' or 'host'")
     if lmax not in ("device", "reference"):
         raise ValueError("lmax must be 'device' or 'reference'")
+    if harmonic and not learning:
+        raise ValueError("harmonic=True needs learning=True")
     if pygsp_module is None:
         import pygsp as pygsp_module
     if devices is not None:
@@ -379,7 +390,7 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         _apply(on["Graph"], methods)
     for name, asked, names, replacements in (
             ("features", features, _FEATURES, lambda saved: _feature_functions(pygsp_module, saved)),
-            ("learning", learning, _LEARNING, _learning_functions),
+            ("learning", learning, _LEARNING, lambda saved: _learning_functions(saved, harmonic)),
             ("optimization", optimization, _OPTIMIZATION, _optimization_functions)):
         if on[name] is not None:
             _apply(on[name], replacements(_originals(on[name], names)) if asked else {})

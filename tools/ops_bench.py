@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Measure the operators of SURVEY 8(f) row 3 on the headline graph (Sensor N=1e6, k=8), device
-resident, with scipy on the host cores beside them.  One JSON object on stdout.
+resident, with scipy on the host cores beside them (the tau = 0 harmonic extension: its true residual).  One JSON
+object on stdout.
 usage (GPU box): python tools/ops_bench.py [--vertices 1000000] [--nsig 64]"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -69,7 +70,21 @@ for dtype in (np.float64, np.float32):
                           "ms_per_iteration": ms / max(int(iters.max()), 1),
                           "scipy_cg_1core_1column_ms": t_cpu * 1e3,
                           "rel_err_col0": float(np.max(np.abs(xs[:, 0] - xr)) / np.max(np.abs(xr)))}
-    for b in (bm, byy, bxx, bx, by):
+    # ---- harmonic extension (tau = 0): CG on L_uu, 40 % of the vertices measured; the true residual of column 0 on the host
+    hrng = np.random.default_rng(1)  # (its own stream: the legs above draw what they drew before this one existed)
+    hmask = hrng.uniform(size=N) > 0.6
+    Yh = (np.sin(6 * coords[:, :1]) + 0.1 * hrng.standard_normal((N, cols))).astype(dtype)
+    bhm, bhy = ctx.upload(hmask.astype(dtype)), ctx.upload(Yh)
+    iters, ms = dev.dirichlet_cg_dev(bhm.ptr, bhy.ptr, bxx.ptr, cols)
+    xh = bxx.download((N, cols), dtype)[:, 0].astype(np.float64)
+    rhs = -(L @ np.where(hmask, Yh[:, 0].astype(np.float64), 0.0))[~hmask]
+    res["dirichlet_cg"] = {"columns": cols, "measured": float(hmask.mean()), "ms": ms,
+                           "rtol": 1e-10 if dtype == np.float64 else 1e-5, "iterations": [int(i) for i in iters],
+                           "ms_per_iteration": ms / max(int(iters.max()), 1),
+                           "measured_rows_equal_y": bool(np.array_equal(xh[hmask], Yh[hmask, 0].astype(np.float64))),
+                           "true_rel_residual_col0": float(np.linalg.norm(rhs - (L @ np.where(hmask, 0.0, xh))[~hmask])
+                                                           / np.linalg.norm(rhs))}
+    for b in (bm, byy, bxx, bx, by, bhm, bhy):
         b.free()
     dev.destroy()
     out[tag] = res

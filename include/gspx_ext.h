@@ -281,6 +281,24 @@ int gspx_graph_components_dev(gspx_graph* g, int32_t* labels_dev, int64_t* n_com
 int gspx_graph_components(gspx_graph* g, int32_t* labels_host, int64_t* n_components, int* rounds, double* kernel_ms);
 int gspx_components_round_cap(int64_t N, int* cap);
 
+/* Spring layout (Fruchterman-Reingold; Graph.set_coordinates('spring'), pygsp/graphs/_layout.py:169-219) iterated on
+ * the device.  A_ij = 1 where the graph's Laplacian stores an off-diagonal entry (i, j) - only the pattern is read, so
+ * fp32 and fp64 graphs both work, and the caller has ruled out what the pattern does not show (a directed W, negative
+ * weights).  dim 2 or 3; pos_dev: N x dim fp64 (DEVICE, caller's vertex order), start positions in, result out;
+ * fixed_dev: N uint8 (DEVICE, caller's order; nonzero = the vertex never moves, bit for bit) or NULL.  Iteration it =
+ * 0 .. iterations - 1 runs at temperature t_it, t_0 = t0 and t_{it+1} = t_it - dt in fp64 (the reference: t0 = 0.1, dt =
+ * t0 / (iterations + 1)): for every vertex i that is not fixed disp_i = sum over ALL j of (pos_i - pos_j) (k^2 / d^2 -
+ * A_ij d / k), d = max(||pos_i - pos_j||, 0.01); then pos_i += disp_i t / len_i, len_i = ||disp_i|| replaced by 0.1
+ * where < 0.01, every position after all displacements.  One step at a given temperature (iterations = 1) and the
+ * continuation of a longer run are the same call.  The all-pairs sum is exact (no grid, no tree) and every sum has a
+ * fixed order: the same inputs give the same bits on every call for a given split count - gspx_layout_splits: what the
+ * call uses for this graph, derived from N and the CU count unless the context option "layout_splits" (> 0) forces it.
+ * iterations = 0 and N = 0 leave pos untouched; dim outside {2, 3}, k <= 0, iterations < 0, a non-finite k / t0 / dt:
+ * GSPX_ERR_INVALID.  kernel_ms (nullable): device time of the whole call. */
+int gspx_layout_spring_dev(gspx_graph* g, int dim, double k, const void* fixed_dev, int64_t iterations, double t0,
+                           double dt, void* pos_dev, double* kernel_ms);
+int gspx_layout_splits(gspx_graph* g, int64_t* splits);
+
 /* Columns [j0, j0 + w) of the N x N identity as a row-major N x w panel in device memory (dtype GSPX_F32 /
  * GSPX_F64), queued on the context's stream: the input of Filter.compute_frame (filter.py:593-600 filters
  * np.identity(N)) produced where it is consumed. */

@@ -124,6 +124,10 @@ SIGNATURES = {
     "gspx_graph_components": (_c.c_int, [_P, _P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int),
                                          _c.POINTER(_c.c_double)]),
     "gspx_components_round_cap": (_c.c_int, [_c.c_int64, _c.POINTER(_c.c_int)]),
+    # spring layout (Graph.set_coordinates('spring'), pygsp_amd/layout.py)
+    "gspx_layout_spring_dev": (_c.c_int, [_P, _c.c_int, _c.c_double, _P, _c.c_int64, _c.c_double, _c.c_double, _P,
+                                          _c.POINTER(_c.c_double)]),
+    "gspx_layout_splits": (_c.c_int, [_P, _c.POINTER(_c.c_int64)]),
     "gspx_sbm_build": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_uint64, _P]),
     "gspx_sbm_build_ex": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_uint64, _c.c_int, _P]),
     "gspx_radius_build": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_double, _c.c_double, _c.c_int, _P]),

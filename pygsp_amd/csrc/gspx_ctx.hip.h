@@ -51,6 +51,8 @@ struct Options {
   int64_t streamed_alloc = 1;   // 1: the two streamed workspaces are assembled from scrambled 2 MB chunks (HIP
                                 // virtual-memory API; +2..8 % bandwidth); 0: plain hipMalloc (the safe mode on an
                                 // untested ROCm: no address range is ever reserved or retired)
+  int64_t layout_splits = 0;    // gspx_layout_spring_dev: ways the all-pairs j range is split over grid.y (0: from N and
+                                // the CU count, gspx_layout.hip.h)
 };
 
 struct gspx_ctx {
@@ -336,6 +338,8 @@ static const OptionDef OPTION_TABLE[] = {
     {"host_edge", &Options::host_edge, nullptr, nullptr},
     {"host_threads", &Options::host_threads, nullptr, nullptr},
     {"streamed_alloc", &Options::streamed_alloc, nullptr, nullptr},
+    {"layout_splits", &Options::layout_splits, [](int64_t v) { return v >= 0 && v <= 65535; },
+     "layout_splits must be in [0, 65535] (0 = automatic)"},
 };
 
 static const OptionDef* find_option(const char* key) {

@@ -1266,6 +1266,66 @@ class DeviceGraph:
             z = bz.download(x2.shape, np.float64)
         return (z[:, 0] if one_d else z), info
 
+    # ---- layout (Graph.set_coordinates('spring')) ---------------------------------------------------
+    def layout_splits(self):
+        """Ways gspx_layout_spring_dev splits the all-pairs sum for this graph (from N and the CU count, or the
+        context option 'layout_splits')."""
+        return self._i64(_capi.load().gspx_layout_splits)
+
+    def layout_spring_dev(self, pos_ptr, dim, k, fixed_ptr=None, iterations=50, t0=0.1, dt=None):
+        """gspx_layout_spring_dev on device pointers (N x dim float64 positions, in place; N uint8 fixed flags or
+        None), caller's vertex order; returns the report of layout_spring."""
+        iterations = int(iterations)
+        if dt is None:  # (a negative count is the library's to refuse)
+            dt = float(t0) / float(iterations + 1) if iterations >= 0 else 0.0
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_layout_spring_dev,
+            self._h, int(dim), float(k), ctypes.c_void_p(fixed_ptr), iterations, float(t0), dt,
+            ctypes.c_void_p(pos_ptr), ctypes.byref(ms))
+        return {"kernel_ms": ms.value, "splits": self.layout_splits(), "iterations": iterations}
+
+    def layout_spring(self, pos, k, fixed=None, iterations=50, t0=0.1, dt=None):
+        """`iterations` Fruchterman-Reingold steps (pygsp/graphs/_layout.py:169-219) from the positions `pos` (N x 2
+        or N x 3), on the pattern of this graph's Laplacian (fp32 and fp64 graphs alike; positions are float64):
+        step it runs at temperature t0 - it * dt, formed by repeated subtraction as the reference does; dt None:
+        t0 / (iterations + 1), the reference's cooling.  fixed: indices (or a boolean indicator of length N) of the
+        vertices that never move.  One step at a given temperature (iterations=1, t0=t) and the continuation of a
+        longer run (t0 where it stopped, the same dt) are ordinary calls.  pos: a numpy array or a float64
+        DeviceArray of this context (left unchanged); the result comes back as the same kind.  Returns (pos, report)
+        with report = {'kernel_ms', 'splits' (ways the all-pairs sum was split), 'iterations'}."""
+        mask = None
+        if fixed is not None and np.size(fixed):
+            fixed = np.asarray(fixed)
+            if fixed.dtype == np.bool_ and fixed.shape == (self.N,):
+                mask = fixed.astype(np.uint8)
+            else:
+                mask = np.zeros(self.N, dtype=np.uint8)
+                mask[fixed.astype(np.int64)] = 1
+            if not mask.any():
+                mask = None
+        if isinstance(pos, DeviceArray):
+            if pos.dtype != np.float64 or pos.ctx is not self.ctx or pos.cube[0] != self.N or pos.cube[2] != 1:
+                raise ValueError("layout_spring: device positions must be (N, dim) float64 on the graph's context")
+            dim = pos.cube[1]
+            out = DeviceArray.empty(self.ctx, pos.cube, np.float64)
+            out.shape = pos.shape
+            if self.N:
+                from . import fourier
+                fourier.panel_copy(self.ctx, self.N, pos.ptr, dim, dim, out.ptr, dim)
+            with self.ctx._temporaries() as t:
+                bm = None if mask is None else t.upload(mask)
+                report = self.layout_spring_dev(out.ptr, dim, k, None if bm is None else bm.ptr, iterations, t0, dt)
+            return out, report
+        p = np.ascontiguousarray(pos, dtype=np.float64)
+        if p.ndim != 2 or p.shape[0] != self.N:
+            raise ValueError("layout_spring: positions must be (N, dim), got {}".format(np.shape(pos)))
+        with self.ctx._temporaries() as t:
+            bp = t.upload(p) if p.size else t.alloc(16)
+            bm = None if mask is None else t.upload(mask)
+            report = self.layout_spring_dev(bp.ptr, p.shape[1], k, None if bm is None else bm.ptr, iterations, t0, dt)
+            out = bp.download(p.shape, np.float64) if p.size else p.copy()
+        return out, report
+
     # ---- edges: the differential operator D, grad = D^T x, div = D y ---------------------------------
     def n_edges(self):
         return self._i64(_capi.load().gspx_graph_n_edges)

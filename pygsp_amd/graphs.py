@@ -12,6 +12,7 @@ Mirrors (same names, argument meaning and exceptions) the parts of
 * ``Graph.is_connected``          graph.py:294-366  -> component labels ON DEVICE (gspx_graph_components)
 * ``Graph.extract_components``    graph.py:444-508  -> the same labels, one ``subgraph`` per component
 * ``Graph.subgraph / is_weighted / has_loops``      graph.py:218-292, 407-442
+* ``Graph.set_coordinates``       _layout.py:5-233  -> 'spring' iterated ON DEVICE (gspx_layout_spring_dev)
 
 Everything else of the reference's Graph (plotting, I/O, ...) is out of scope; use
 the real pygsp together with ``pygsp_amd.plugin.install()`` for those.
@@ -315,6 +316,35 @@ class Graph:
             part.info = {"orig_idx": members.tolist()}
             parts.append(part)
         return parts
+
+    # ---- coordinates (pygsp/graphs/_layout.py; pygsp_amd/layout.py) ---------------------------------
+    def set_coordinates(self, kind="spring", seed=None, **kwargs):
+        """_layout.py:5-119: set ``G.coords`` from an array (N, N x 2 or N x 3) or by a named layout: 'line1D',
+        'line2D', 'ring2D', 'random2D', 'random3D' (host; the reference's ``default_rng(seed)`` draws, the same bits),
+        'spring' (default; ``_fruchterman_reingold(seed=seed, **kwargs)``, iterated on the device),
+        'laplacian_eigenmap2D' / '3D' (``compute_fourier_basis`` of 3 / 4 vectors, then U[:, 1:3] / U[:, 1:4]).
+        'community2D' raises NotImplementedError (no Community graphs here), any other string the reference's
+        ValueError.  Coordinates set on a graph that is already set up do NOT re-derive the engine's internal vertex
+        order: that order was chosen when the device graph was built and stays."""
+        from . import layout
+        layout.set_coordinates(self, kind, seed, **kwargs)
+
+    def _fruchterman_reingold(self, dim=2, k=None, pos=None, fixed=[], iterations=50, scale=1.0, center=None,
+                              seed=None):
+        """_layout.py:121-219, Fruchterman-Reingold positions (N x dim): start positions from
+        ``default_rng(seed).uniform`` (or `pos`, with `fixed` vertices kept where they are), optimal distance k
+        (default sqrt(1 / N)), `iterations` steps cooling linearly from t = 0.1, then - when nothing is fixed - centred,
+        rescaled to `scale` and moved to `center`.  The iterations are ONE device call (engine.DeviceGraph.layout_spring,
+        report in ``G.layout_report``); the bookkeeping around them is host numpy (pygsp_amd.layout).
+        A directed graph, a negative weight or dim outside {2, 3} raise NotImplementedError (pygsp_amd.layout).  The
+        engine's internal vertex order is not touched."""
+        from . import layout
+        why = layout.device_route(self, dim)
+        if why is not None:
+            raise NotImplementedError(why + " (pygsp_amd.layout); use the real pygsp for this graph")
+        out, self.layout_report = layout.fruchterman_reingold(self, layout.device_iterate(self.device_graph()), dim, k,
+                                                              pos, fixed, iterations, scale, center, seed)
+        return out
 
     def _symmetric_w(self):
         """W itself if undirected, else (W + W.T)/2 (utils.symmetrize 'average', graph.py:613-616)."""

@@ -314,9 +314,27 @@ def _extract_components_on_device(self):
     return parts
 
 
+_LAYOUT = ("_fruchterman_reingold",)
+
+
+def _fruchterman_reingold_on_device(self, dim=2, k=None, pos=None, fixed=[], iterations=50, scale=1.0, center=None,
+                                    seed=None):
+    """``Graph._fruchterman_reingold`` of the reference (_layout.py:121-219: the spring layout behind
+    ``set_coordinates('spring')``, an O(N^2) Python loop per iteration) with the iterations in one device call
+    (gspx_layout_spring_dev) and the host bookkeeping of pygsp_amd.layout around them; the call's report is left in
+    ``G.layout_report``.  A directed graph, a negative weight and dim outside {2, 3} run the reference's code."""
+    from . import layout
+    if self.N == 0 or layout.device_route(self, dim) is not None:
+        return _saved_on(type(self))["_fruchterman_reingold"](self, dim, k, pos, fixed, iterations, scale, center, seed)
+    out, self.layout_report = layout.fruchterman_reingold(self, layout.device_iterate(device_graph_for(self)), dim, k,
+                                                          pos, fixed, iterations, scale, center, seed)
+    return out
+
+
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
-            lanczos=False, features=False, learning=False, topology=False, optimization=False, harmonic=False):
+            lanczos=False, features=False, learning=False, topology=False, optimization=False, harmonic=False,
+            layout=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -348,7 +366,11 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     `topology` (default False): also replace ``Graph.is_connected`` and ``Graph.extract_components`` so that undirected
     graphs are labelled on the device (gspx_graph_components); directed graphs keep the reference's code.
     `optimization` (default False): also replace ``pygsp.optimization.prox_tv`` with pygsp_amd.optimization.prox_tv (the
-    graph total-variation proximal operator on the device, without pyunlocbox)."""
+    graph total-variation proximal operator on the device, without pyunlocbox).
+    `layout` (default False): also replace ``Graph._fruchterman_reingold``, the spring layout behind
+    ``Graph.set_coordinates('spring')``, so that undirected graphs without negative weights are laid out on the device
+    in 2 or 3 dimensions (gspx_layout_spring_dev); other graphs keep the reference's code.  The eigenmap kinds follow
+    ``fourier=True``."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -377,8 +399,9 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     if on["Filter"] is not None:
         wrap = wrap_filter and hasattr(on["approximations"], "compute_cheby_coeff")
         _apply(on["Filter"], {"filter": _filter_on_device, "compute_frame": _compute_frame_on_device} if wrap else {})
-    if topology and on["Graph"] is None:
-        raise ValueError("topology=True: {} has no graphs.Graph".format(pygsp_module.__name__))
+    for name, asked in (("topology", topology), ("layout", layout)):
+        if asked and on["Graph"] is None:
+            raise ValueError("{}=True: {} has no graphs.Graph".format(name, pygsp_module.__name__))
     if on["Graph"] is not None:
         methods = {}
         if lmax == "device":
@@ -387,6 +410,8 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
             methods["compute_fourier_basis"] = _compute_fourier_basis_on_device
         if topology:
             methods.update(zip(_TOPOLOGY, (_is_connected_on_device, _extract_components_on_device)))
+        if layout:
+            methods.update(zip(_LAYOUT, (_fruchterman_reingold_on_device,)))
         _apply(on["Graph"], methods)
     for name, asked, names, replacements in (
             ("features", features, _FEATURES, lambda saved: _feature_functions(pygsp_module, saved)),

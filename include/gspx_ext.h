@@ -68,8 +68,8 @@ int gspx_laplacian_apply_dev(gspx_graph* g, int64_t Nsig, const void* x_dev, voi
 int gspx_dirichlet_energy_dev(gspx_graph* g, int64_t Nsig, const void* x_dev, double* gram_host,
                               double* kernel_ms);
 /* ---- dense fp64 panel primitives (partial Fourier basis, pygsp_amd/fourier.py) ---------------------------
- * Panels: fp64 DEVICE pointers, row-major, N rows, leading dimension ld* >= width (elements); widths 1..512; any
- * N >= 0.  Matrix-core (f64 MFMA) kernels; every reduction goes through per-workgroup partials and a fixed-order
+ * Panels: fp64 DEVICE pointers, row-major, N rows, leading dimension ld* >= width (elements); widths 1..512 unless
+ * an entry point says otherwise; any N >= 0.  Matrix-core (f64 MFMA) kernels; every reduction goes through per-workgroup partials and a fixed-order
  * second pass, so the same inputs give the same bits on every call.  Vertex order: whatever the caller's panels use.
  * C_host (na x nb, row-major, HOST) = A^T B. */
 int gspx_panel_gram_dev(gspx_ctx* ctx, int64_t N, const double* A, int64_t lda, int na, const double* B, int64_t ldb,
@@ -77,6 +77,20 @@ int gspx_panel_gram_dev(gspx_ctx* ctx, int64_t N, const double* A, int64_t lda, 
 /* Y = X Q, Q (p x q, row-major, HOST) staged in LDS tiles; Y must not overlap X (GSPX_ERR_INVALID). */
 int gspx_panel_combine_dev(gspx_ctx* ctx, int64_t N, const double* X, int64_t ldx, int p, const double* Q_host, int q,
                            double* Y, int64_t ldy, double* kernel_ms);
+/* C (na x nb, row-major, leading dimension ldc >= nb, DEVICE) = alpha A^T diag(rowscale) B for ANY widths na, nb >= 0
+ * (not capped at 512): the Gram whose result stays on the device.  rowscale: N doubles on the DEVICE, or NULL for the
+ * plain A^T B.  C must not overlap A, B or rowscale.  N == 0 or an empty width: nothing is written. */
+int gspx_panel_gram_to_dev(gspx_ctx* ctx, int64_t N, const double* A, int64_t lda, int na, const double* B, int64_t ldb,
+                           int nb, const double* rowscale, double alpha, double* C, int64_t ldc, double* kernel_ms);
+/* Exact Fourier filtering's product Y_g = U Q_g (filter.py:292-301), Q_g formed from the coefficients S and the
+ * multipliers H (all DEVICE) while its tiles are staged, never materialised.  U: N x n, leading dimension ldu; any
+ * contraction length n >= 1, any width w >= 0.  mode 0 (plain, igft): Y = U S, nf = 1, H unused.  mode 1 (analysis):
+ * S one n x w panel, H nf x n row-major, Y nf planes [filter][vertex][signal] (plane stride N ldy),
+ * Q_g[k][c] = H[g][k] S[k][c].  mode 2 (synthesis): S nf panels (plane stride n lds), one output plane,
+ * Q[k][c] = sum_f H[f][k] S_f[k][c] in filter order.  Y must not overlap U, S or H.  The contraction runs in one
+ * fixed order: the same bits on every call.  N == 0 or w == 0: nothing is written. */
+int gspx_spectral_apply_dev(gspx_ctx* ctx, int64_t N, const double* U, int64_t ldu, int n, const double* S, int64_t lds,
+                            int w, int mode, int nf, const double* H, double* Y, int64_t ldy, double* kernel_ms);
 /* out_host[i] (HOST) = || LX[:, i] - theta_host[i] X[:, i] ||_2, both panels read once (no ||LX||^2 - theta^2). */
 int gspx_panel_residual_norms_dev(gspx_ctx* ctx, int64_t N, const double* X, const double* LX, int64_t ld, int p,
                                   const double* theta_host, double* out_host, double* kernel_ms);

@@ -83,6 +83,10 @@ SIGNATURES = {
     # dense fp64 panel primitives of the partial Fourier basis (pygsp_amd/fourier.py)
     "gspx_panel_gram_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int64, _c.c_int, _P, _P]),
     "gspx_panel_combine_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int, _P, _c.c_int64, _P]),
+    "gspx_panel_gram_to_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int64, _c.c_int, _P,
+                                          _c.c_double, _P, _c.c_int64, _P]),
+    "gspx_spectral_apply_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int64, _c.c_int, _c.c_int,
+                                           _c.c_int, _P, _P, _c.c_int64, _P]),
     "gspx_panel_residual_norms_dev": (_c.c_int, [_P, _c.c_int64, _P, _P, _c.c_int64, _c.c_int, _P, _P, _P]),
     "gspx_panel_copy_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int64, _P]),
     # Lanczos filtering (pygsp_amd/lanczos.py)

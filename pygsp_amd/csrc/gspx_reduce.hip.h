@@ -88,13 +88,16 @@ __global__ __launch_bounds__(256) void k_panel_sum_parts(const double* __restric
 // the tile, row l / 16 of the group) and B-operand = B (the same lane map): coalesced row segments, no LDS.  fp32
 // panels are converted on load: the sums are double either way.
 // D layout of the f64 instruction: lane l holds rows (l / 16) + 4 e, column l % 16.
+// ROWSCALE: C = A^T diag(rs) B, the A element scaled by rs[row] on load (rs: N doubles); without it rs is not read
+// and the arithmetic is the unscaled kernel's.
 // The four waves' tiles are summed in LDS in a fixed order (((w0 + w1) + w2) + w3) and wave 0 writes the workgroup's
 // partial[chunk * na * nb + a * nb + c]: every entry of every chunk's slot is written (zeros where the slice has no
 // rows), so the second pass needs no initialisation.
-template <typename T>
+template <typename T, bool ROWSCALE>
 __global__ __launch_bounds__(256) void k_panel_gram(const T* __restrict__ A, int64_t lda, int na,
                                                     const T* __restrict__ B, int64_t ldb, int nb, int64_t N,
-                                                    int64_t rpc, double* __restrict__ partial) {
+                                                    int64_t rpc, const double* __restrict__ rs,
+                                                    double* __restrict__ partial) {
   typedef double d4 __attribute__((ext_vector_type(4)));
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int kq = lane >> 4, cq = lane & 15;
@@ -117,6 +120,11 @@ __global__ __launch_bounds__(256) void k_panel_gram(const T* __restrict__ A, int
       const int ca = a0 + t * 16 + cq, cb = b0 + t * 16 + cq;
       xa[t] = (rok && ca < na) ? (double)A[row * lda + ca] : 0.0;
       yb[t] = (rok && cb < nb) ? (double)B[row * ldb + cb] : 0.0;
+    }
+    if constexpr (ROWSCALE) {
+      const double sc = rok ? rs[row] : 0.0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) xa[t] *= sc;
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -177,10 +185,11 @@ static void sum_parts(const double* partial, int nparts, int64_t count, double* 
 }
 
 // C = A^T B (na x nb, row-major doubles) of two N-row device panels, N > 0, left on the device in ctx->ws_spec
-// (*out_dev, valid until the next use of that workspace): records no events, copies nothing to the host
+// (*out_dev, valid until the next use of that workspace): records no events, copies nothing to the host.
+// rs (N doubles on the device, or null): C = A^T diag(rs) B.
 template <typename T>
 static int launch_panel_gram(gspx_ctx* ctx, const T* A, int64_t lda, int na, const T* B, int64_t ldb, int nb, int64_t N,
-                             double** out_dev) {
+                             double** out_dev, const double* rs = nullptr) {
   const size_t count = (size_t)na * nb;
   const int ntiles = ((na + 63) / 64) * ((nb + 63) / 64);
   // about eight workgroups per CU in all; at least 16 rows per wave; at most 256 MiB of partials
@@ -194,8 +203,12 @@ static int launch_panel_gram(gspx_ctx* ctx, const T* A, int64_t lda, int na, con
   CHK(ctx->ws_spec.ensure((nparts + 1) * count * sizeof(double)));
   double* partial = ctx->ws_spec.as<double>();
   *out_dev = partial + nparts * count;
-  hipLaunchKernelGGL((gspx::k_panel_gram<T>), dim3(ntiles, (unsigned)nchunk), dim3(256), 0, ctx->stream, A, lda, na, B,
-                     ldb, nb, N, rpc, partial);
+  if (rs)
+    hipLaunchKernelGGL((gspx::k_panel_gram<T, true>), dim3(ntiles, (unsigned)nchunk), dim3(256), 0, ctx->stream, A, lda,
+                       na, B, ldb, nb, N, rpc, rs, partial);
+  else
+    hipLaunchKernelGGL((gspx::k_panel_gram<T, false>), dim3(ntiles, (unsigned)nchunk), dim3(256), 0, ctx->stream, A, lda,
+                       na, B, ldb, nb, N, rpc, rs, partial);
   sum_parts(partial, (int)nparts, (int64_t)count, *out_dev, ctx->stream);
   return GSPX_OK;
 }

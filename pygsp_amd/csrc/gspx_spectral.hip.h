@@ -1,12 +1,17 @@
-// gspx_spectral.hip.h - dense primitives on tall-skinny fp64 panels for the partial Fourier basis
-// (pygsp_amd/fourier.py: Chebyshev-filtered subspace iteration).  The polynomial of L is the existing program
-// path (gspx_poly_program_dev); these are the three dense pieces around it:
-//   C = A^T B                 gspx_panel_gram_dev            (na x nb, to the host)
-//   Y = X Q                   gspx_panel_combine_dev         (Q p x q from the host, staged in LDS)
-//   r_i = ||LX_i - th_i X_i|| gspx_panel_residual_norms_dev  (one read of both panels)
-//   Y = X (strided)           gspx_panel_copy_dev            (a column block out of / into a wider panel)
-// Panels are row-major device arrays with an explicit leading dimension (elements), any N >= 0, widths 1..512.
-// Gram and combine run on the matrix cores (v_mfma_f64_16x16x4f64).  The Gram kernel and the second pass of every
+// gspx_spectral.hip.h - dense primitives on fp64 panels for the Fourier basis: the partial basis
+// (pygsp_amd/fourier.py: Chebyshev-filtered subspace iteration) and exact Fourier filtering against a full one
+// (filters.filter_signals(method='exact'), Graph.gft / igft of device arrays, filters.Modulation).  The polynomial of
+// L is the existing program path (gspx_poly_program_dev); these are the dense pieces around it:
+//   C = A^T B                       gspx_panel_gram_dev            (na x nb <= 512, to the host)
+//   C = alpha A^T diag(r) B         gspx_panel_gram_to_dev         (any na x nb, to a device buffer; r optional)
+//   Y = X Q                         gspx_panel_combine_dev         (Q p x q <= 512 from the host, staged in LDS)
+//   Y_g = U (diag(h_g) S)           gspx_spectral_apply_dev        (S, h on the device; analysis, synthesis or plain;
+//                                                                   any contraction length, any width)
+//   r_i = ||LX_i - th_i X_i||       gspx_panel_residual_norms_dev  (one read of both panels)
+//   Y = X (strided)                 gspx_panel_copy_dev            (a column block out of / into a wider panel)
+// Panels are row-major device arrays with an explicit leading dimension (elements), any N >= 0.
+// Gram and the X Q products run on the matrix cores (v_mfma_f64_16x16x4f64); combine and spectral apply are one
+// kernel (k_spectral_apply) that differs only in how the Q tile is staged.  The Gram kernel and the second pass of every
 // reduction are gspx_reduce.hip.h's (launch_panel_gram, sum_parts): no atomics, the same bits on every call.
 // After gspx_ops.hip.h (which brings gspx_reduce.hip.h).
 #pragma once
@@ -16,25 +21,35 @@ namespace gspx {
 typedef double spec_d4 __attribute__((ext_vector_type(4)));
 
 // ---- Y = X Q: a workgroup owns 64 rows x 64 columns of Y ---------------------------------------------------
-// The contraction runs in chunks of SPEC_KC columns of X: the X chunk (64 rows) and the matching SPEC_KC x 64 tile of
-// Q are staged in LDS (33.8 KiB per workgroup, four workgroups per CU within 160 KiB), then wave w forms rows
-// 16 w .. 16 w + 15 against the four 16-column sub-tiles: A-operand X[row l % 16][k l / 16], B-operand Q[k l / 16]
-// [column l % 16].  Row stride SPEC_KC + 1 (X) and 64 + 4 (Q) doubles keep the fragment reads off one bank.
-// Tiles are numbered column tile fastest, so the column tiles of one row block run side by side and share X in L2.
+// The contraction runs in chunks of SPEC_KC columns of X, in order, for any length p: the X chunk (64 rows) and the
+// matching SPEC_KC x 64 tile of Q are staged in LDS (33.8 KiB per workgroup, four workgroups per CU within 160 KiB),
+// then wave w forms rows 16 w .. 16 w + 15 against the four 16-column sub-tiles: A-operand X[row l % 16][k l / 16],
+// B-operand Q[k l / 16][column l % 16].  Row stride SPEC_KC + 1 (X) and 64 + 4 (Q) doubles keep the fragment reads off
+// one bank.  STAGE says what the Q tile is, formed while it is staged and never written to memory:
+//   SPEC_PLAIN      Q[k][c]                                 (one plane: combine, igft)
+//   SPEC_ANALYSIS   H[g][k] Q[k][c] for output plane g      (nf output planes N x q, plane stride N ldy)
+//   SPEC_SYNTHESIS  sum_f H[f][k] Q_f[k][c], f in order     (nf input planes p x q, plane stride p ldq; one output)
+// H is nf x p, row-major.  Tiles are numbered column tile fastest, then output plane, then row block, so the tiles
+// that read one row block of X run side by side and share it in L2.
 constexpr int SPEC_KC = 32;
 constexpr int SPEC_XS = SPEC_KC + 1;
 constexpr int SPEC_QS = 64 + 4;
-__global__ __launch_bounds__(256) void k_panel_combine(const double* __restrict__ X, int64_t ldx, int p,
-                                                       const double* __restrict__ Q, int q, double* __restrict__ Y,
-                                                       int64_t ldy, int64_t N) {
+enum { SPEC_PLAIN = 0, SPEC_ANALYSIS = 1, SPEC_SYNTHESIS = 2 };
+template <int STAGE>
+__global__ __launch_bounds__(256) void k_spectral_apply(const double* __restrict__ X, int64_t ldx, int p,
+                                                        const double* __restrict__ Q, int64_t ldq, int q,
+                                                        const double* __restrict__ H, int nf, double* __restrict__ Y,
+                                                        int64_t ldy, int64_t N) {
   __shared__ double xs[64 * SPEC_XS];
   __shared__ double qs[SPEC_KC * SPEC_QS];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kq = lane >> 4, cq = lane & 15;
   const int nct = (q + 63) / 64;
-  const int64_t ntiles = (N + 63) / 64 * nct;
+  const int nplanes = STAGE == SPEC_ANALYSIS ? nf : 1;
+  const int64_t ntiles = (N + 63) / 64 * nplanes * nct;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t r0 = tile / nct * 64;
+    const int64_t r0 = tile / ((int64_t)nct * nplanes) * 64;
+    const int g = (int)(tile / nct % nplanes);
     const int c0 = (int)(tile % nct) * 64;
     const int ntc = min(4, (q - c0 + 15) / 16);
     spec_d4 acc[4];
@@ -49,7 +64,15 @@ __global__ __launch_bounds__(256) void k_panel_combine(const double* __restrict_
       }
       for (int idx = tid; idx < SPEC_KC * 64; idx += 256) {
         const int k = idx / 64, c = idx % 64;
-        qs[k * SPEC_QS + c] = (k0 + k < p && c0 + c < q) ? Q[(size_t)(k0 + k) * q + c0 + c] : 0.0;
+        double v = 0.0;
+        if (k0 + k < p && c0 + c < q) {
+          const size_t at = (size_t)(k0 + k) * ldq + c0 + c;
+          if constexpr (STAGE == SPEC_PLAIN) v = Q[at];
+          if constexpr (STAGE == SPEC_ANALYSIS) v = H[(size_t)g * p + k0 + k] * Q[at];
+          if constexpr (STAGE == SPEC_SYNTHESIS)
+            for (int f = 0; f < nf; ++f) v += H[(size_t)f * p + k0 + k] * Q[(size_t)f * p * ldq + at];
+        }
+        qs[k * SPEC_QS + c] = v;
       }
       __syncthreads();
       const int kend = min(SPEC_KC, p - k0);
@@ -61,15 +84,24 @@ __global__ __launch_bounds__(256) void k_panel_combine(const double* __restrict_
             acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, qs[(kk + kq) * SPEC_QS + j * 16 + cq], acc[j], 0, 0, 0);
       }
     }
+    double* Yg = Y + (size_t)g * (size_t)N * ldy;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int64_t row = r0 + w * 16 + kq + 4 * e;
         const int col = c0 + j * 16 + cq;
-        if (row < N && col < q) Y[row * ldy + col] = acc[j][e];
+        if (row < N && col < q) Yg[row * ldy + col] = acc[j][e];
       }
   }
+}
+
+// ---- C[a][c] = alpha * sum[a][c]: the Gram's summed tile into the caller's (strided) device matrix -----------
+__global__ __launch_bounds__(256) void k_gram_store(const double* __restrict__ sum, int na, int nb, double alpha,
+                                                    double* __restrict__ C, int64_t ldc) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)na * nb) return;
+  C[i / nb * ldc + i % nb] = alpha * sum[i];
 }
 
 // ---- residual norms: partial[b][c] = sum over the block's rows of (LX[i][c] - theta[c] X[i][c])^2 ----------
@@ -170,8 +202,95 @@ extern "C" int gspx_panel_combine_dev(gspx_ctx* ctx, int64_t N, const double* X,
   HIPCHK(hipEventRecord(ctx->ev[0], st));
   const int64_t ntiles = (N + 63) / 64 * ((q + 63) / 64);
   const unsigned grid = (unsigned)std::min<int64_t>(ntiles, (int64_t)1 << 20);
-  hipLaunchKernelGGL(gspx::k_panel_combine, dim3(grid), dim3(256), 0, st, X, ldx, p, ctx->ws_spec.as<double>(), q, Y,
-                     ldy, N);
+  hipLaunchKernelGGL(gspx::k_spectral_apply<gspx::SPEC_PLAIN>, dim3(grid), dim3(256), 0, st, X, ldx, p,
+                     ctx->ws_spec.as<double>(), (int64_t)q, q, (const double*)nullptr, 1, Y, ldy, N);
+  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  return finish_timed(ctx, kernel_ms);
+}
+
+// C (na x nb, leading dimension ldc, DEVICE) = alpha A^T diag(r) B for any widths: the output is formed in blocks of at
+// most SPEC_GRAM_BLOCK x SPEC_GRAM_BLOCK entries (32 MiB, so that launch_panel_gram keeps several row chunks within its
+// 256 MiB of partials), each block summed by sum_parts and scaled into C by k_gram_store.  N == 0 or an empty width:
+// nothing is launched and C is left as it is.  (A later block may grow the workspace after earlier blocks were written;
+// if that allocation fails the call can be repeated as it is: the inputs are untouched and every entry of C is rewritten.)
+static constexpr int SPEC_GRAM_BLOCK = 2048;
+extern "C" int gspx_panel_gram_to_dev(gspx_ctx* ctx, int64_t N, const double* A, int64_t lda, int na, const double* B,
+                                      int64_t ldb, int nb, const double* rowscale, double alpha, double* C, int64_t ldc,
+                                      double* kernel_ms) {
+  if (N < 0) return set_err(GSPX_ERR_INVALID, "panel_gram_to: negative number of rows");
+  if (na < 0 || nb < 0) return set_err(GSPX_ERR_INVALID, "panel_gram_to: negative width (got %d, %d)", na, nb);
+  if (lda < na || ldb < nb || ldc < nb)
+    return set_err(GSPX_ERR_INVALID, "panel_gram_to: leading dimension below the width");
+  const bool work = N > 0 && na > 0 && nb > 0;
+  if (work && (!A || !B || !C)) return set_err(GSPX_ERR_INVALID, "panel_gram_to: null panel");
+  if (work) {
+    const size_t cbytes = spec_span(na, ldc, nb);
+    if (spec_overlap(C, cbytes, A, spec_span(N, lda, na)) || spec_overlap(C, cbytes, B, spec_span(N, ldb, nb)) ||
+        (rowscale && spec_overlap(C, cbytes, rowscale, (size_t)N * sizeof(double))))
+      return set_err(GSPX_ERR_INVALID, "panel_gram_to: C must not alias A, B or the row scale");
+  }
+  if (!ctx) return set_err(GSPX_ERR_INVALID, "null context");
+  replay_reset(ctx);
+  if (kernel_ms) *kernel_ms = 0;
+  if (!work) return GSPX_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipEventRecord(ctx->ev[0], st));
+  for (int a0 = 0; a0 < na; a0 += SPEC_GRAM_BLOCK)
+    for (int b0 = 0; b0 < nb; b0 += SPEC_GRAM_BLOCK) {
+      const int aw = std::min(SPEC_GRAM_BLOCK, na - a0), bw = std::min(SPEC_GRAM_BLOCK, nb - b0);
+      double* csum = nullptr;
+      CHK(launch_panel_gram<double>(ctx, A + a0, lda, aw, B + b0, ldb, bw, N, &csum, rowscale));
+      const int64_t count = (int64_t)aw * bw;
+      hipLaunchKernelGGL(gspx::k_gram_store, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, csum, aw, bw, alpha,
+                         C + (size_t)a0 * ldc + b0, ldc);
+    }
+  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  return finish_timed(ctx, kernel_ms);
+}
+
+// Y_g = U Q_g with Q_g formed from S (and H) while it is staged (k_spectral_apply): mode 0 plain (Y = U S, H unused,
+// nf = 1), 1 analysis (S one n x w panel, nf output planes), 2 synthesis (nf panels of S, plane stride n lds, one
+// output plane).  N == 0 or w == 0: nothing is launched.
+extern "C" int gspx_spectral_apply_dev(gspx_ctx* ctx, int64_t N, const double* U, int64_t ldu, int n, const double* S,
+                                       int64_t lds, int w, int mode, int nf, const double* H, double* Y, int64_t ldy,
+                                       double* kernel_ms) {
+  if (N < 0) return set_err(GSPX_ERR_INVALID, "spectral_apply: negative number of rows");
+  if (n < 1) return set_err(GSPX_ERR_INVALID, "spectral_apply: the contraction length must be at least 1 (got %d)", n);
+  if (w < 0) return set_err(GSPX_ERR_INVALID, "spectral_apply: negative width (got %d)", w);
+  if (mode < gspx::SPEC_PLAIN || mode > gspx::SPEC_SYNTHESIS)
+    return set_err(GSPX_ERR_INVALID, "spectral_apply: mode must be 0 (plain), 1 (analysis) or 2 (synthesis), got %d", mode);
+  if (nf < 1 || (mode == gspx::SPEC_PLAIN && nf != 1))
+    return set_err(GSPX_ERR_INVALID, "spectral_apply: the number of filters must be at least 1 (1 in plain mode), got %d", nf);
+  if (ldu < n || lds < w || ldy < w) return set_err(GSPX_ERR_INVALID, "spectral_apply: leading dimension below the width");
+  const bool work = N > 0 && w > 0;
+  if (work && (!U || !S || !Y || (mode != gspx::SPEC_PLAIN && !H)))
+    return set_err(GSPX_ERR_INVALID, "spectral_apply: null panel");
+  if (work) {
+    const int planes_in = mode == gspx::SPEC_SYNTHESIS ? nf : 1, planes_out = mode == gspx::SPEC_ANALYSIS ? nf : 1;
+    const size_t ybytes = (size_t)(planes_out - 1) * (size_t)N * ldy * sizeof(double) + spec_span(N, ldy, w);
+    const size_t sbytes = (size_t)(planes_in - 1) * (size_t)n * lds * sizeof(double) + spec_span(n, lds, w);
+    if (spec_overlap(Y, ybytes, U, spec_span(N, ldu, n)) || spec_overlap(Y, ybytes, S, sbytes) ||
+        (H && spec_overlap(Y, ybytes, H, (size_t)nf * n * sizeof(double))))
+      return set_err(GSPX_ERR_INVALID, "spectral_apply: Y must not alias U, the coefficients or the multipliers");
+  }
+  if (!ctx) return set_err(GSPX_ERR_INVALID, "null context");
+  replay_reset(ctx);
+  if (kernel_ms) *kernel_ms = 0;
+  if (!work) return GSPX_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipEventRecord(ctx->ev[0], st));
+  const int64_t ntiles = (N + 63) / 64 * ((w + 63) / 64) * (mode == gspx::SPEC_ANALYSIS ? nf : 1);
+  const dim3 grid((unsigned)std::min<int64_t>(ntiles, (int64_t)1 << 20)), block(256);
+  if (mode == gspx::SPEC_PLAIN)
+    hipLaunchKernelGGL(gspx::k_spectral_apply<gspx::SPEC_PLAIN>, grid, block, 0, st, U, ldu, n, S, lds, w, H, nf, Y, ldy, N);
+  else if (mode == gspx::SPEC_ANALYSIS)
+    hipLaunchKernelGGL(gspx::k_spectral_apply<gspx::SPEC_ANALYSIS>, grid, block, 0, st, U, ldu, n, S, lds, w, H, nf, Y, ldy,
+                       N);
+  else
+    hipLaunchKernelGGL(gspx::k_spectral_apply<gspx::SPEC_SYNTHESIS>, grid, block, 0, st, U, ldu, n, S, lds, w, H, nf, Y,
+                       ldy, N);
   HIPCHK(hipEventRecord(ctx->ev[1], st));
   return finish_timed(ctx, kernel_ms);
 }

@@ -8,9 +8,12 @@ Mirrors (names, argument meaning, shapes, exceptions):
 * ``Filter.filter`` & co    pygsp/filters/filter.py:146-391, 506-600
 * ``Heat``                  pygsp/filters/heat.py:102-119
 * ``MexicanHat``            pygsp/filters/mexicanhat.py:55-84 (+ utils.compute_log_scales)
+* ``Modulation``            pygsp/filters/modulation.py:126-177
+* ``Gabor``                 pygsp/filters/gabor.py:72-92
 
-Only ``method='chebyshev'`` is implemented: it is the accelerated path.  The exact (Fourier)
-method is a different algorithm (dense eigendecomposition) and stays with the reference.
+``method='chebyshev'`` is the accelerated path for large graphs.  ``method='exact'`` (filter.py:292-301) filters in the
+Fourier domain against the full basis: the basis itself comes from the host's eigh, the transforms and the spectral
+multiply run on the device (gspx_panel_gram_to_dev, gspx_spectral_apply_dev).
 """
 import functools
 
@@ -757,9 +760,7 @@ def filter_signals(bank, s, method="chebyshev", order=30, devices=None, coeffici
         cube_shape = _cube_shape(bank.G, bank.Nf, s.shape)
     synthesis = cube_shape[2] != 1
     if method == "exact":
-        raise NotImplementedError(
-            "method='exact' (dense Fourier filtering, filter.py:292-301) is outside the "
-            "accelerated path; use the reference implementation for it.")
+        return _filter_exact(bank, s, cube_shape)
     if method != "chebyshev":
         raise ValueError("Unknown method {}.".format(method))
     coeffs = coefficients(bank, m=order)
@@ -785,6 +786,98 @@ def filter_signals(bank, s, method="chebyshev", order=30, devices=None, coeffici
         _record_timing(bank.G, ms)
         out = np.asarray(y, dtype=np.float64)
     return np.squeeze(out)
+
+
+# ---- method='exact': dense Fourier filtering against the full basis (filter.py:292-301) -----------------------------
+def _exact_basis(G):
+    """(float64 DeviceGraph, DevicePanel of U) of `G`: the mirror Graph's own copy, or the one plugin mode keeps on a
+    reference graph."""
+    if hasattr(G, "_basis_on_device"):
+        return G._basis_on_device()
+    from . import plugin
+    return plugin.basis_on_device_for(G)
+
+
+def _exact_upload(G, cube):
+    """A host cube (N, Nsig, Nfeat) as a float64 DeviceArray on the context of G's device basis."""
+    from . import engine
+    return engine.DeviceArray.from_host(_exact_basis(G)[0].ctx, cube, np.float64)
+
+
+def _exact_gft(G, a, S, F):
+    """Device call 1: the coefficients U^T s of the DeviceArray `a` read as F planes of (N, S), as a DeviceArray of
+    cube (N, S, F) (the basis is full: N coefficients per signal).  One gspx_panel_gram_to_dev per plane, written
+    where the result lives."""
+    from . import engine, fourier
+    dev, U = _exact_basis(G)
+    if a.ctx is not dev.ctx:
+        raise ValueError("the DeviceArray does not live on the context of this graph's Fourier basis")
+    N = a.cube[0]
+    x_ptr, keep = a.planes(S, F)
+    hat = engine.DeviceArray.empty(dev.ctx, (N, S, F), np.float64)
+    ms = 0.0
+    for f in range(F):
+        ms += fourier.panel_gram_to(dev.ctx, N, U.ptr, U.ld, U.width, x_ptr + 8 * f * N * S, S, S,
+                                    hat.ptr + 8 * f * N * S, S)
+    del keep
+    return hat, ms
+
+
+def _exact_apply(G, hat, H, synthesis):
+    """Device call 2: U (H-weighted coefficients), the multiplier fused into the product (gspx_spectral_apply_dev).
+    `hat`: DeviceArray of coefficients, cube (N, Nsig, 1) for analysis or (N, Nsig, Nf) for synthesis; `H`: host
+    (Nf, N) multipliers, the only data that crosses PCIe.  Returns the DeviceArray (N, Nsig, Nf) or (N, Nsig, 1)."""
+    from . import engine, fourier
+    dev, U = _exact_basis(G)
+    ctx = dev.ctx
+    N, S, _ = hat.cube
+    Nf = H.shape[0]
+    out = engine.DeviceArray.empty(ctx, (N, S, 1 if synthesis else Nf), np.float64)
+    ms = 0.0
+    if N * S:
+        with ctx._temporaries() as tmp:
+            h = tmp.upload(np.ascontiguousarray(H, dtype=np.float64))
+            ms = fourier.spectral_apply(ctx, N, U.ptr, U.ld, U.width, hat.ptr, S, S, out.ptr, S,
+                                        fourier.SPECTRAL_SYNTHESIS if synthesis else fourier.SPECTRAL_ANALYSIS,
+                                        Nf, h.ptr)
+    return out, ms
+
+
+def _filter_exact(bank, s, cube_shape):
+    """filter_signals(method='exact'): s_out = U diag(h) U^T s per filter (filter.py:292-301), as one Gram (the
+    transform of the signals) and one spectral apply (multiplier and inverse transform in one product) on the float64
+    device graph's context, against the device copy of U.  numpy in gives numpy out; a float64 DeviceArray in gives a
+    DeviceArray out, and then only the Nf x N multipliers ``bank.evaluate(G.e)`` cross PCIe.  The full basis is needed:
+    it comes from the host's eigh (Graph.compute_fourier_basis), which bounds this path to graphs of a few ten
+    thousand vertices."""
+    from . import engine
+    G = bank.G
+    if not (hasattr(G, "gft") and hasattr(G, "igft")):
+        raise NotImplementedError(
+            "method='exact' (dense Fourier filtering, filter.py:292-301) is outside the "
+            "accelerated path; use the reference implementation for it.")
+    on_device = isinstance(s, engine.DeviceArray)
+    dtype = s.dtype if on_device else np.asarray(s).dtype
+    if np.issubdtype(dtype, np.complexfloating):
+        raise TypeError("complex signals are not supported by the exact path")
+    if (on_device or np.issubdtype(dtype, np.floating)) and dtype != np.float64:
+        raise TypeError("gft / igft of a device array need float64 signals (got {}); fp32 is not "
+                        "supported".format(dtype))
+    e = G.e
+    if len(e) < G.N:
+        raise ValueError("method='exact' needs the full Fourier basis, but the cached basis has {} of {} vectors; "
+                         "call compute_fourier_basis() for the full one".format(len(e), G.N))
+    H = np.asarray(bank.evaluate(e), dtype=np.float64).reshape(bank.Nf, G.N)
+    N, nsig, nfeat = cube_shape
+    synthesis = nfeat != 1
+    a = s if on_device else _exact_upload(G, np.asarray(s, dtype=np.float64).reshape(cube_shape))
+    hat, ms_gram = _exact_gft(G, a, nsig, nfeat)
+    out, ms_apply = _exact_apply(G, hat, H, synthesis)
+    hat.free()
+    if not on_device:
+        a.free()
+    _record_timing(G, ms_gram + ms_apply, "exact")
+    return out if on_device else out.numpy()
 
 
 def _filter_device_array(bank, s, cube_shape, coeffs, devices, evaluation=None):
@@ -1078,3 +1171,113 @@ class MexicanHat(Filter):
         bank = [_MexicanLowPass(lmin)]
         bank.extend(_MexicanBandPass(t, normalize) for t in self.scales)
         super().__init__(G, bank)
+
+
+# ---- banks defined through the exact path: one kernel moved to every graph frequency -----------------------------
+def _check_mother_kernel(graph, kernel):
+    if kernel.n_filters != 1:
+        raise ValueError("A kernel must be one filter. The passed "
+                         "filter bank {} has {}.".format(kernel, kernel.n_filters))
+    if kernel.G is not graph:
+        raise ValueError("The graph passed to this filter bank must "
+                         "be the one used to build the mother kernel.")
+
+
+def modulation_localized(bank, s, panel=1024, coefficients=None):
+    """``Modulation.filter`` with localisation first (modulation.py:170-177), the windowed graph Fourier transform:
+    row i of the result is sqrt(N) gft(s * kernel.localize(i)).  The reference loops over the vertices (N Chebyshev
+    localisations and N transforms); as matrices it is Y = sqrt(N) (diag(s) T)^T U with T[:, i] = kernel.localize(i)
+    = sqrt(N) p(L) delta_i, p the order-30 Chebyshev polynomial ``localize`` uses by default.  Here p(L) of identity
+    panels of `panel` columns comes from the Chebyshev path on the float64 device graph (as frame_panels), and each
+    panel goes through one Gram against the device copy of U with row scale s (gspx_panel_gram_to_dev), both
+    factors sqrt(N) folded into its alpha.  `bank`: the mirror Modulation or the real pygsp one (plugin.install(
+    exact=True)), `coefficients` its compute_cheby_coeff.  Returns the (N, N) array, row i = vertex i."""
+    from . import fourier
+    G, kernel = bank.G, bank._kernels
+    s = np.asarray(G._check_signal(s))
+    if s.shape != (G.N,):
+        raise ValueError("Modulation.filter with localisation first takes one signal of shape ({},), got {}."
+                         .format(G.N, s.shape))
+    if np.iscomplexobj(s):
+        raise TypeError("complex signals are not supported by the exact path")
+    if len(G.e) < G.N:
+        raise ValueError("Modulation needs the full Fourier basis, but the cached basis has {} of {} vectors; "
+                         "call compute_fourier_basis() for the full one".format(len(G.e), G.N))
+    coeffs = _as_coeff_matrix((coefficients or compute_cheby_coeff)(kernel, m=30))
+    dev, U = _exact_basis(G)
+    ctx, N = dev.ctx, G.N
+    root = float(np.sqrt(N))
+    width = max(1, min(int(panel), N))
+    ms = 0.0
+    with ctx._temporaries() as tmp:
+        deltas, atoms = tmp.alloc(N * width * 8), tmp.alloc(N * width * 8)
+        out, scale = tmp.alloc(N * N * 8), tmp.upload(np.ascontiguousarray(s, dtype=np.float64))
+        for j0 in range(0, N, width):
+            w = min(width, N - j0)
+            ctx.identity_panel(deltas, N, j0, w, np.float64)
+            ms += dev.cheby_filter_dev(coeffs, deltas.ptr, atoms.ptr, w, G.lmax)
+            ms += fourier.panel_gram_to(ctx, N, atoms.ptr, w, w, U.ptr, U.ld, N, out.ptr + 8 * j0 * N, N,
+                                        rowscale_ptr=scale.ptr, alpha=root * root)
+        y = out.download((N, N), np.float64)
+    _record_timing(G, ms, "exact")
+    return y
+
+
+class Modulation(Filter):
+    """One mother kernel modulated to every graph frequency (modulation.py:7-177): filter k is the kernel multiplied,
+    in the vertex domain, by eigenvector u_k.  Filtering a signal gives its vertex-frequency picture S[i, k]:
+    with ``modulation_first=False`` (default) the windowed graph Fourier transform - localise the kernel at vertex i,
+    window the signal with it, transform - computed by modulation_localized on the device; with
+    ``modulation_first=True`` the N-filter bank ``evaluate`` describes, applied by the exact path.  ``evaluate``
+    always describes the modulated (not localised) bank and is defined at the eigenvalues only: NaN elsewhere.
+    Needs the full Fourier basis, so graphs up to a few ten thousand vertices."""
+
+    def __init__(self, graph, kernel, modulation_first=False):
+        _check_mother_kernel(graph, kernel)
+        self.G, self._kernels, self._modulation_first = graph, kernel, modulation_first
+
+    @property
+    def n_features_out(self):
+        return self.G.n_vertices
+
+    def _response(self):
+        """(N, N): row k holds the response of every filter at eigenvalue e[k] (host arithmetic, as the reference's:
+        the kernel's inverse transform, times sqrt(N) u_f, transformed back)."""
+        if not hasattr(self, "_coefficients"):
+            G = self.G
+            atom = G.igft(np.squeeze(self._kernels.evaluate(G.e)))
+            self._coefficients = G.gft(np.sqrt(G.n_vertices) * G.U * atom[:, np.newaxis])
+        return self._coefficients
+
+    def evaluate(self, x):
+        table = self._response()
+        first = {}
+        for k, lam in enumerate(self.G.e):
+            first.setdefault(lam, k)
+        at = np.asanyarray(x)
+        y = np.full((self.n_features_out, at.size), np.nan)
+        for i, lam in enumerate(at.ravel()):
+            k = first.get(lam)
+            if k is not None:
+                y[:, i] = table[k]
+        return y.reshape((self.n_features_out,) + at.shape)
+
+    def filter(self, s, method="exact", order=None):
+        """The vertex-frequency transform of `s` (method and order are accepted and ignored, as in the reference:
+        this bank is only defined through the exact path)."""
+        if self._modulation_first:
+            return super().filter(s, method="exact")
+        return modulation_localized(self, s)
+
+
+class Gabor(Filter):
+    """One mother kernel centred at every graph frequency (gabor.py:6-92): filter k is x -> kernel(x - e[k]).  A bank
+    of N filters applied by the exact path (whatever `method` says, as in the reference); needs the full Fourier
+    basis."""
+
+    def __init__(self, graph, kernel):
+        _check_mother_kernel(graph, kernel)
+        super().__init__(graph, [lambda x, k=k: kernel.evaluate(x - graph.e[k])[0] for k in range(graph.n_vertices)])
+
+    def filter(self, s, method="exact", order=None):
+        return super().filter(s, method="exact")

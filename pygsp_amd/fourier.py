@@ -24,7 +24,7 @@ from scipy import linalg as sla
 # a partial request goes to the device when the graph is this large and the block is this narrow against it
 AUTO_MIN_VERTICES = 2048
 AUTO_MAX_BLOCK_FRACTION = 0.25
-MAX_BLOCK = 512          # widest panel of the primitives
+MAX_BLOCK = 512          # widest panel of the solver's primitives (gram to the host, combine, residuals, copy)
 BLOCK_QUANTUM = 16       # the block is rounded up to a multiple of this (why not 32)
 AMPLIFICATION_LIMIT = 1e6  # largest ratio one filter may put between the first and the slowest active vector
 
@@ -352,6 +352,36 @@ def panel_combine(ctx, N, x_ptr, ldx, p, Q, y_ptr, ldy):
     ms = ctypes.c_double(0)
     ctx.call(_capi.load().gspx_panel_combine_dev, ctx._h, int(N), ctypes.c_void_p(x_ptr), int(ldx), int(p),
              _capi.ptr(Q), int(Q.shape[1]), ctypes.c_void_p(y_ptr), int(ldy), ctypes.byref(ms))
+    return ms.value
+
+
+def panel_gram_to(ctx, N, a_ptr, lda, na, b_ptr, ldb, nb, c_ptr, ldc, rowscale_ptr=None, alpha=1.0):
+    """C = alpha A^T diag(r) B written to the device matrix at `c_ptr` (leading dimension ldc), any widths
+    (gspx_panel_gram_to_dev); `rowscale_ptr`: N doubles on the device, or None.  Returns the kernel ms."""
+    import ctypes
+
+    from . import _capi
+    ms = ctypes.c_double(0)
+    ctx.call(_capi.load().gspx_panel_gram_to_dev, ctx._h, int(N), ctypes.c_void_p(a_ptr), int(lda), int(na),
+             ctypes.c_void_p(b_ptr), int(ldb), int(nb), ctypes.c_void_p(rowscale_ptr), float(alpha),
+             ctypes.c_void_p(c_ptr), int(ldc), ctypes.byref(ms))
+    return ms.value
+
+
+SPECTRAL_PLAIN, SPECTRAL_ANALYSIS, SPECTRAL_SYNTHESIS = 0, 1, 2
+
+
+def spectral_apply(ctx, N, u_ptr, ldu, n, s_ptr, lds, w, y_ptr, ldy, mode=SPECTRAL_PLAIN, nf=1, h_ptr=None):
+    """Y_g = U (diag(h_g) S) on the device (gspx_spectral_apply_dev): plain (Y = U S), analysis (nf output planes) or
+    synthesis (nf coefficient planes summed into one); U, S, the nf x n multipliers and Y are device pointers.
+    Returns the kernel ms."""
+    import ctypes
+
+    from . import _capi
+    ms = ctypes.c_double(0)
+    ctx.call(_capi.load().gspx_spectral_apply_dev, ctx._h, int(N), ctypes.c_void_p(u_ptr), int(ldu), int(n),
+             ctypes.c_void_p(s_ptr), int(lds), int(w), int(mode), int(nf), ctypes.c_void_p(h_ptr),
+             ctypes.c_void_p(y_ptr), int(ldy), ctypes.byref(ms))
     return ms.value
 
 

@@ -629,9 +629,11 @@ class Graph:
 
     def gft(self, s):
         """Graph Fourier transform U^T s (fourier.py:197-230): numpy input on the host, exactly the reference's
-        arithmetic.  A float64 engine.DeviceArray is read on the device (gspx_panel_gram_dev against the device copy
-        of U) and the result is a DeviceArray of shape (n, ...) for a basis of n vectors; the n x Nsig coefficients
-        themselves make a host round trip (the Gram entry point returns them to the host, they are uploaded again)."""
+        arithmetic.  A float64 engine.DeviceArray is read on the device against the device copy of U, for a basis of
+        any width n, and the result is a DeviceArray of shape (n, ...) whose coefficients never leave the device
+        (gspx_panel_gram_to_dev: the Gram kernel, written into the result's planes).  Bases of at most 512 vectors
+        take this same call rather than the older Gram-to-the-host: it is the same kernel with the same row chunks,
+        so up to 512 signal columns give the bits they gave before, and one path serves every width."""
         if isinstance(s, engine.DeviceArray):
             return self._transform_device(s, inverse=False)
         s = self._check_signal(s)
@@ -640,9 +642,10 @@ class Graph:
 
     def igft(self, s_hat):
         """Inverse transform U s_hat (fourier.py:232-264).  The first axis of s_hat runs over the basis vectors
-        (N of them for a full basis, as in the reference).  A float64 DeviceArray gives a DeviceArray: the small
-        n x Nsig coefficients are downloaded (they are the Q of gspx_panel_combine_dev, a host matrix) and the
-        N x Nsig product is formed on the device."""
+        (N of them for a full basis, as in the reference).  A float64 DeviceArray gives a DeviceArray: the n x Nsig
+        coefficients are read where they lie (gspx_spectral_apply_dev in plain mode) and the N x Nsig product is
+        formed on the device, for a basis of any width.  The product kernel is the one gspx_panel_combine_dev
+        launches, tile for tile, so narrow bases keep their bits here too."""
         if isinstance(s_hat, engine.DeviceArray):
             return self._transform_device(s_hat, inverse=True)
         n = self.U.shape[1]
@@ -658,9 +661,6 @@ class Graph:
             raise TypeError("gft / igft of a device array need float64 signals (got {}); fp32 is not "
                             "supported".format(a.dtype))
         n = self.U.shape[1]
-        if n > fourier.MAX_BLOCK:
-            raise ValueError("gft / igft on the device take bases of at most {} vectors, this one has {}"
-                             .format(fourier.MAX_BLOCK, n))
         rows_in, rows_out = (n, self.N) if inverse else (self.N, n)
         if a.cube[0] != rows_in:
             raise ValueError("First dimension must be {}, got {}.".format(rows_in, a.shape))
@@ -670,25 +670,24 @@ class Graph:
             raise ValueError("the device array lives on another context than the graph's Fourier basis")
         _, S, F = a.cube
         shape = (rows_out,) + tuple(a.shape[1:])
-        if inverse:
-            hat = a.numpy().reshape(n, S, F)  # n x S x F coefficients: small, they travel to the host as Q
-            out = engine.DeviceArray.empty(ctx, (rows_out, S, F), np.float64)
-            for f in range(F):
-                for j0 in range(0, S, fourier.MAX_BLOCK):
-                    j1 = min(S, j0 + fourier.MAX_BLOCK)
-                    if self.N:
-                        fourier.panel_combine(ctx, self.N, U.ptr, U.ld, n, hat[:, j0:j1, f],
-                                              out.ptr + 8 * (f * self.N * S + j0), S)
-        else:
-            res = np.zeros((n, S, F))
-            for f in range(F):
-                for j0 in range(0, S, fourier.MAX_BLOCK):
-                    j1 = min(S, j0 + fourier.MAX_BLOCK)
-                    res[:, j0:j1, f] = fourier.panel_gram(ctx, self.N, U.ptr, U.ld, n, a.ptr + 8 * (f * self.N * S + j0),
-                                                          S, j1 - j0)[0]
-            out = engine.DeviceArray.from_host(ctx, res)
+        out = engine.DeviceArray.empty(ctx, (rows_out, S, F), np.float64)
+        for f in range(F):  # planes [feature][row][signal] on both sides
+            src, dst = a.ptr + 8 * f * rows_in * S, out.ptr + 8 * f * rows_out * S
+            if inverse:
+                fourier.spectral_apply(ctx, self.N, U.ptr, U.ld, n, src, S, S, dst, S)
+            else:
+                fourier.panel_gram_to(ctx, self.N, U.ptr, U.ld, n, src, S, S, dst, S)
         out.shape = shape
         return out
+
+    @property
+    def coherence(self):
+        """max |U_ik| over the full Fourier basis (fourier.py:38-95): between 1 / sqrt(N) (every eigenvector spread
+        over all vertices) and 1 (one of them is a delta).  Computed on the host from ``G.U``; a cached partial basis
+        is replaced by the full one first, as the definition runs over all N vectors."""
+        if self.U.shape[1] < self.N:
+            self.compute_fourier_basis()
+        return float(np.abs(self.U).max())
 
     @property
     def e(self):

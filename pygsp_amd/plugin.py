@@ -147,6 +147,41 @@ def _reference_coefficients(bank, m):
     raise RuntimeError("pygsp_amd.plugin: {} is not a patched class".format(type(bank).__name__))
 
 
+def basis_on_device_for(G):
+    """(float64 DeviceGraph, fourier.DevicePanel of U) attached to a reference ``pygsp.graphs.Graph``: U uploaded once
+    and cached on the object next to the very ``G.U`` it was copied from (compared with ``is``, as device_graph_for
+    does for L), so a recomputed basis is uploaded again."""
+    from . import fourier
+    dev = device_graph_for(G, dtype=np.float64)
+    with _cache_lock:
+        held = G.__dict__.get("_gspx_basis")
+        if held is not None and held[0] is G.U and held[1] is dev and held[2].buf is not None:
+            return dev, held[2]
+        if held is not None and held[2].buf is not None:
+            held[2].buf.free()
+        panel = fourier.DeviceBackend(dev, 1.0).from_host(np.ascontiguousarray(G.U, dtype=np.float64))
+        G.__dict__["_gspx_basis"] = (G.U, dev, panel)
+        return dev, panel
+
+
+def _filter_exact_on_device(self, s, method="chebyshev", order=30):
+    """What install(exact=True) puts in place of ``Filter.filter``: _filter_on_device whose method='exact' branch
+    (filter.py:292-301) also runs on the device (filters.filter_signals: one Gram, one spectral apply against the
+    device copy of ``G.U``).  ``Gabor.filter`` calls this through ``super()`` and follows."""
+    if method == "exact":
+        return _filters.filter_signals(self, s, method, order, None, _reference_coefficients)
+    return _filter_on_device(self, s, method, order)
+
+
+def _modulation_on_device(self, s, method="exact", order=None):
+    """``Modulation.filter`` (modulation.py:164-177) on the device: modulation first is the exact path of the wrapped
+    ``Filter.filter``; localisation first, the reference's loop over the vertices, is filters.modulation_localized
+    (identity-panel Chebyshev filter, then one Gram per panel)."""
+    if self._modulation_first:
+        return _filters.filter_signals(self, s, "exact", order, None, _reference_coefficients)
+    return _filters.modulation_localized(self, s, coefficients=_reference_coefficients)
+
+
 def _filter_on_device(self, s, method="chebyshev", order=30):
     """``pygsp.filters.Filter.filter`` (filter.py:146-328) with its Chebyshev branch in one device call: the shape
     rules are the reference's (filters._cube_shape restates filter.py:267-290), analysis is the call the
@@ -334,7 +369,7 @@ def _fruchterman_reingold_on_device(self, dim=2, k=None, pos=None, fixed=[], ite
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
             lanczos=False, features=False, learning=False, topology=False, optimization=False, harmonic=False,
-            layout=False):
+            layout=False, exact=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -370,7 +405,11 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     `layout` (default False): also replace ``Graph._fruchterman_reingold``, the spring layout behind
     ``Graph.set_coordinates('spring')``, so that undirected graphs without negative weights are laid out on the device
     in 2 or 3 dimensions (gspx_layout_spring_dev); other graphs keep the reference's code.  The eigenmap kinds follow
-    ``fourier=True``."""
+    ``fourier=True``.
+    `exact` (default False; needs ``wrap_filter=True``): ``Filter.filter(method='exact')`` and ``Modulation.filter``
+    also run on the device, against a device copy of the full ``G.U`` the reference computed (float64 signals; the
+    basis still comes from the host's eigh); ``Gabor`` follows through ``Filter.filter``.  Off, the package's own code
+    answers ``method='exact'``."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -379,6 +418,8 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         raise ValueError("lmax must be 'device' or 'reference'")
     if harmonic and not learning:
         raise ValueError("harmonic=True needs learning=True")
+    if exact and not wrap_filter:
+        raise ValueError("exact=True needs wrap_filter=True")
     if pygsp_module is None:
         import pygsp as pygsp_module
     if devices is not None:
@@ -398,7 +439,14 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     _apply(on["filters"], ops)  # (the aliases of pygsp/filters/__init__.py)
     if on["Filter"] is not None:
         wrap = wrap_filter and hasattr(on["approximations"], "compute_cheby_coeff")
-        _apply(on["Filter"], {"filter": _filter_on_device, "compute_frame": _compute_frame_on_device} if wrap else {})
+        if exact and not wrap:
+            raise ValueError("exact=True: {} has no compute_cheby_coeff to wrap Filter with".format(pygsp_module.__name__))
+        _apply(on["Filter"], {"filter": _filter_exact_on_device if exact else _filter_on_device,
+                              "compute_frame": _compute_frame_on_device} if wrap else {})
+    elif exact:
+        raise ValueError("exact=True: {} has no filters.Filter".format(pygsp_module.__name__))
+    if on["Modulation"] is not None:
+        _apply(on["Modulation"], {"filter": _modulation_on_device} if exact else {})
     for name, asked in (("topology", topology), ("layout", layout)):
         if asked and on["Graph"] is None:
             raise ValueError("{}=True: {} has no graphs.Graph".format(name, pygsp_module.__name__))
@@ -428,6 +476,7 @@ def _targets(pygsp_module):
     """The modules and classes of `pygsp_module` that install() patches, by role; None where the package has none."""
     filters = pygsp_module.filters
     return {"approximations": filters.approximations, "filters": filters, "Filter": getattr(filters, "Filter", None),
+            "Modulation": getattr(filters, "Modulation", None),
             "Graph": getattr(getattr(pygsp_module, "graphs", None), "Graph", None),
             "features": getattr(pygsp_module, "features", None), "learning": getattr(pygsp_module, "learning", None),
             "optimization": getattr(pygsp_module, "optimization", None)}

@@ -313,6 +313,34 @@ int gspx_layout_spring_dev(gspx_graph* g, int dim, double k, const void* fixed_d
                            double dt, void* pos_dev, double* kernel_ms);
 int gspx_layout_splits(gspx_graph* g, int64_t* splits);
 
+/* The full Fourier basis on the device: every eigenpair of a dense symmetric fp64 matrix by two-sided cyclic block
+ * Jacobi (blocks of 32, 64 x 64 subproblems solved in LDS by scalar rotations, updates on the matrix cores).
+ * A: n x n (DEVICE, row-major, leading dimension lda), symmetric - the subproblems read (S + S^T) / 2 -; only read.
+ * V (DEVICE out, n x n, leading dimension ldv): orthonormal eigenvectors in columns, ascending eigenvalue; entries
+ * beyond column n of a row are left alone.  e_host (HOST out): the n eigenvalues, ascending, Rayleigh quotients of the
+ * returned columns.  A sweep rotates every block pair once (gspx_sym_eig_schedule_describe); pairs whose 64 x 64 block
+ * is already diagonal to the tolerance are skipped.  Before each sweep: stop when off(A) <= tol ||A||_F and no row's
+ * off-diagonal norm exceeds tol max |a_ii| (off: the square root of the sum of the squared off-diagonal entries,
+ * summed directly).  After max_sweeps sweeps without that: GSPX_ERR_NOCONV, V and e_host unspecified, the library
+ * usable.  The finish orders the columns, takes one Newton-Schulz step V (3 I - V^T V) / 2 and forms the Rayleigh
+ * quotients.  No atomics: the same inputs give the same bits.  info (HOST, 12 doubles, nullable): [0] sweeps,
+ * [1] final off(A) / ||A||_F, [2] pairs rotated, [3] pairs skipped, [4..8] device ms of the subproblems, the column
+ * updates, the row updates, the off-norms and the finish, [9] wall ms of the call, [10] max_i ||A v_i - e_i v_i||_2,
+ * [11] the largest entry of a returned column outside the first n rows of the padded work matrix (0: the padding
+ * never mixed).  skipped_per_sweep (HOST, max_sweeps entries, nullable): pairs skipped in each sweep run.
+ * n = 0: nothing to do.  n < 0, n > 32768, lda < n, ldv < n, null pointers with n > 0, tol <= 0, max_sweeps < 1,
+ * V overlapping A, non-finite entries: GSPX_ERR_INVALID - all but the last before any device work. */
+#define GSPX_ERR_NOCONV 7 /* an iteration used up its sweeps -> ValueError */
+int gspx_sym_eig_dev(gspx_ctx* ctx, int n, const double* A, int64_t lda, double* V, int64_t ldv, double* e_host,
+                     double tol, int max_sweeps, double* info, int64_t* skipped_per_sweep);
+/* Host-only: the block pairs of one sweep over n_blocks blocks (1..1024), in the order the solver visits them.
+ * *n_rounds = ceil(n_blocks / 2) * 2 - 1 rounds of floor(n_blocks / 2) disjoint pairs each (an odd count leaves one
+ * block out per round); pairs_out (nullable): n_rounds * floor(n_blocks / 2) * 2 ints, (i, j) with i < j, round-major. */
+int gspx_sym_eig_schedule_describe(int n_blocks, int* pairs_out, int* n_rounds);
+/* X[:, c] *= s[c] for the w columns of an N-row fp64 panel (DEVICE, leading dimension ldx); s_host: w doubles (HOST).
+ * The sign rule of a Fourier basis applied to its device copy, for widths beyond gspx_panel_combine_dev's 512. */
+int gspx_panel_scale_cols_dev(gspx_ctx* ctx, int64_t N, double* X, int64_t ldx, int w, const double* s_host);
+
 /* Columns [j0, j0 + w) of the N x N identity as a row-major N x w panel in device memory (dtype GSPX_F32 /
  * GSPX_F64), queued on the context's stream: the input of Filter.compute_frame (filter.py:593-600 filters
  * np.identity(N)) produced where it is consumed. */

@@ -17,7 +17,7 @@ F32, F64 = 0, 1
 LAP_COMBINATORIAL, LAP_NORMALIZED = 0, 1
 ANALYSIS, SYNTHESIS = 0, 1
 
-OK, ERR_INVALID, ERR_COEFF, ERR_HIP, ERR_NODEVICE, ERR_OOM, ERR_INTERNAL = 0, 1, 2, 3, 4, 5, 6
+OK, ERR_INVALID, ERR_COEFF, ERR_HIP, ERR_NODEVICE, ERR_OOM, ERR_INTERNAL, ERR_NOCONV = 0, 1, 2, 3, 4, 5, 6, 7
 
 _lib = None
 
@@ -89,6 +89,10 @@ SIGNATURES = {
                                            _c.c_int, _P, _P, _c.c_int64, _P]),
     "gspx_panel_residual_norms_dev": (_c.c_int, [_P, _c.c_int64, _P, _P, _c.c_int64, _c.c_int, _P, _P, _P]),
     "gspx_panel_copy_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P, _c.c_int64, _P]),
+    # the full Fourier basis: dense symmetric eigensolver (pygsp_amd/fourier.py: sym_eig, device_full_basis)
+    "gspx_sym_eig_dev": (_c.c_int, [_P, _c.c_int, _P, _c.c_int64, _P, _c.c_int64, _P, _c.c_double, _c.c_int, _P, _P]),
+    "gspx_sym_eig_schedule_describe": (_c.c_int, [_c.c_int, _P, _c.POINTER(_c.c_int)]),
+    "gspx_panel_scale_cols_dev": (_c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _P]),
     # Lanczos filtering (pygsp_amd/lanczos.py)
     "gspx_lanczos_krylov_dev": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _c.c_int64, _c.c_double, _P, _P, _P, _P, _P,
                                            _P, _P]),
@@ -199,6 +203,8 @@ def check(rc):
     msg = last_error()
     if rc == ERR_INVALID:
         raise ValueError(msg)  # graph.py:635-639, filter.py:272-276
+    if rc == ERR_NOCONV:
+        raise ValueError(msg)  # (as the partial solver after maxiter)
     if rc == ERR_COEFF:
         raise TypeError(msg)  # approximations.py:83-84
     if rc == ERR_NODEVICE:

@@ -1,6 +1,8 @@
 """Partial graph Fourier bases: the k smallest eigenpairs of L by Chebyshev-filtered subspace iteration (ChFSI,
 Zhou & Saad 2007).  What ``Graph.compute_fourier_basis(n_eigenvectors=k)`` runs on the device (DESIGN.md section
 "Partial Fourier bases").
+The full basis (``method='jacobi'``: block Jacobi on the dense L, gspx_sym_eig_dev) is at the end of the file (DESIGN.md
+section "The full Fourier basis").
 
 The loop is host Python over a small backend: only p x p matrices reach the host (Cholesky and eigh on p <= 512).
 The backend does every N x p pass:
@@ -210,8 +212,12 @@ def sign_fix(U):
     """Signs s (one per column) that make each column's largest-magnitude entry positive (the lowest index on ties)."""
     if U.shape[0] == 0:
         return np.ones(U.shape[1])
-    idx = np.argmax(np.abs(U), axis=0)
-    s = np.sign(U[idx, np.arange(U.shape[1])])
+    # the largest entry against the smallest decides without an index (two contiguous reductions instead of a strided
+    # argmax: 0.03 s against 0.5 s on a 4096-wide basis); only an exact tie between them needs the lowest index
+    top, low = U.max(axis=0), -U.min(axis=0)
+    s = np.where(top > low, 1.0, -1.0)
+    for c in np.nonzero(top == low)[0]:
+        s[c] = np.sign(U[np.argmax(np.abs(U[:, c])), c])
     s[s == 0] = 1.0
     return s
 
@@ -428,4 +434,96 @@ def device_partial_basis(dev, k, b, *, tol=1e-10, maxiter=100, seed=0, degree=(1
     stats["ms"], stats["calls"] = dict(be.ms), dict(be.calls)
     stats["bytes"], stats["flops"] = dict(be.bytes), dict(be.flops)
     stats["p"] = block_width(k, dev.N)
+    return e, U, U_dev, stats
+
+
+# ---- the full basis: dense symmetric eigensolver on the device (gspx_eig.hip.h) --------------
+FULL_TOL = 1e-13        # stop when off(A) <= tol ||A||_F (and no row's off-diagonal norm exceeds tol max |a_ii|)
+FULL_MAX_SWEEPS = 30
+FULL_SLAB = 1024        # identity columns per L X call when the dense L is formed, as filters.frame_panels
+_EIG_INFO = ("sweeps", "off_rel", "pairs_rotated", "pairs_skipped", "ms_sub", "ms_cols", "ms_rows", "ms_off",
+             "ms_finish", "ms_wall", "residual", "pad_mass")
+
+
+def sym_eig(ctx, n, a_ptr, lda, v_ptr, ldv, tol=FULL_TOL, max_sweeps=FULL_MAX_SWEEPS):
+    """Every eigenpair of the symmetric n x n fp64 device matrix at `a_ptr` (leading dimension lda, only read) by block
+    Jacobi (gspx_sym_eig_dev): the eigenvectors go to the device matrix at `v_ptr` (leading dimension ldv), in columns,
+    ascending.  Returns (e host (n,), stats); ValueError when max_sweeps sweeps do not converge."""
+    import ctypes
+
+    from . import _capi
+    e = np.zeros(int(n), dtype=np.float64)
+    info = np.zeros(len(_EIG_INFO), dtype=np.float64)
+    per_sweep = np.zeros(max(int(max_sweeps), 1), dtype=np.int64)
+    ctx.call(_capi.load().gspx_sym_eig_dev, ctx._h, int(n), ctypes.c_void_p(a_ptr), int(lda), ctypes.c_void_p(v_ptr),
+             int(ldv), _capi.ptr(e), float(tol), int(max_sweeps), _capi.ptr(info), _capi.ptr(per_sweep))
+    stats = SolveStats(zip(_EIG_INFO, (float(v) for v in info)))
+    for key in ("sweeps", "pairs_rotated", "pairs_skipped"):
+        stats[key] = int(stats[key])
+    stats["skipped_per_sweep"] = [int(v) for v in per_sweep[:stats["sweeps"]]]
+    return e, stats
+
+
+def sym_eig_schedule(n_blocks):
+    """The block pairs of one sweep over n_blocks blocks, as a list of rounds of (i, j) pairs, i < j
+    (gspx_sym_eig_schedule_describe: host only, no device)."""
+    import ctypes
+
+    from . import _capi
+    lib, rounds = _capi.load(), ctypes.c_int(0)
+    _capi.check(lib.gspx_sym_eig_schedule_describe(int(n_blocks), None, ctypes.byref(rounds)))
+    per_round = int(n_blocks) // 2
+    pairs = np.zeros((rounds.value, per_round, 2), dtype=np.int32)
+    _capi.check(lib.gspx_sym_eig_schedule_describe(int(n_blocks), _capi.ptr(pairs), ctypes.byref(rounds)))
+    return [[(int(i), int(j)) for i, j in rnd] for rnd in pairs]
+
+
+def panel_scale_cols(ctx, N, x_ptr, ldx, w, s):
+    """X[:, c] *= s[c] on the device (gspx_panel_scale_cols_dev); s a host (w,) array."""
+    import ctypes
+
+    from . import _capi
+    s = np.ascontiguousarray(s, dtype=np.float64)
+    if s.shape != (int(w),):
+        raise ValueError("s must have {} entries".format(w))
+    ctx.call(_capi.load().gspx_panel_scale_cols_dev, ctx._h, int(N), ctypes.c_void_p(x_ptr), int(ldx), int(w),
+             _capi.ptr(s))
+
+
+def device_full_basis(dev, *, tol=FULL_TOL, max_sweeps=FULL_MAX_SWEEPS):
+    """All N eigenpairs of a float64 DeviceGraph on the device.  The dense L is formed there in the caller's vertex
+    order (identity slabs of at most FULL_SLAB columns through L X, copied into place), solved by sym_eig, and signed
+    by sign_fix on the host copy and the device copy alike.  Returns (e, U host (N, N), U_dev (DevicePanel N x N,
+    contiguous), stats); e[0] is set to 0 when |e[0]| < 1e-9, as the host eigh branch does."""
+    be = DeviceBackend(dev, 1.0)
+    ctx, N = dev.ctx, dev.N
+    A, U_dev = be.empty(N), be.empty(N)
+    try:
+        slab = min(FULL_SLAB, max(N, 1))
+        deltas, LX = ctx.take(max(N * slab * 8, 16)), ctx.take(max(N * slab * 8, 16))
+        try:
+            for j0 in range(0, N, slab):
+                w = min(slab, N - j0)
+                ctx.identity_panel(deltas, N, j0, w, np.float64)
+                be.ms["lap"] += dev.laplacian_apply_dev(deltas.ptr, LX.ptr, w)
+                for c0 in range(0, w, MAX_BLOCK):  # (panel_copy takes at most MAX_BLOCK columns)
+                    cw = min(MAX_BLOCK, w - c0)
+                    be.ms["copy"] += panel_copy(ctx, N, LX.ptr + 8 * c0, w, cw, A.ptr + 8 * (j0 + c0), N)
+        finally:
+            ctx.give(deltas)
+            ctx.give(LX)
+        e, stats = sym_eig(ctx, N, A.ptr, N, U_dev.ptr, N, tol=tol, max_sweeps=max_sweeps)
+    except BaseException:
+        be.free(U_dev)
+        raise
+    finally:
+        be.free(A)
+    U = be.to_host(U_dev)
+    s = sign_fix(U)
+    U *= s[None, :]
+    panel_scale_cols(ctx, N, U_dev.ptr, N, N, s)  # (a multiplication by +-1: exact, so the two copies stay equal)
+    stats["theta0"] = float(e[0]) if N else 0.0
+    if N and abs(e[0]) < 1e-9:
+        e[0] = 0
+    stats["ms_form"] = be.ms["lap"] + be.ms["copy"]
     return e, U, U_dev, stats

@@ -565,7 +565,7 @@ class Graph:
             candidates.append(np.max(deg + W.dot(deg) / deg))
         return min(candidates)
 
-    def compute_fourier_basis(self, n_eigenvectors=None, *, method="auto", tol=1e-10, maxiter=100, seed=0,
+    def compute_fourier_basis(self, n_eigenvectors=None, *, method="auto", tol=None, maxiter=None, seed=0,
                               degree=(10, 300)):
         """The (partial) Fourier basis of L (fourier.py:97-195), cached in ``G.e`` / ``G.U``.
 
@@ -575,10 +575,21 @@ class Graph:
         ||L u_i - e_i u_i|| <= tol * b with b the rigorous upper bound of lambda_max, ValueError after `maxiter`
         iterations, filter degree per iteration within `degree`, start block from `seed`; 'dense' - host eigh,
         sliced; 'auto' - 'device' when N >= 2048 and the block (k plus guard vectors) is at most N / 4.
+        `tol` and `maxiter` default to 1e-10 and 100 there.
         A partial basis leaves ``lmax`` alone; e[0] is checked to be within 1e-5 of zero and set to zero, and each
-        column's largest-magnitude entry is made positive."""
+        column's largest-magnitude entry is made positive.
+
+        ``method='jacobi'`` (opt-in, for the full basis and for partial requests alike): all N eigenpairs by block
+        Jacobi on the float64 device graph (fourier.device_full_basis; `tol` 1e-13 on off(L) / ||L||_F, ValueError
+        after `maxiter` sweeps, 30 by default).  The N x N panel stays on the device, so a following
+        ``filter(method='exact')``, ``gft`` or ``igft`` of a device array uploads no basis.  k < N keeps the first k
+        columns under the partial-result rules, as 'dense' does."""
         N = self.n_vertices
         k = N if n_eigenvectors is None else int(n_eigenvectors)
+        if method == "jacobi":
+            return self._fourier_basis_jacobi(k, n_eigenvectors, tol, maxiter)
+        tol = 1e-10 if tol is None else tol
+        maxiter = 100 if maxiter is None else maxiter
         if k == N:
             if self._U is None or self._U.shape[1] < N:
                 self._release_basis_dev()
@@ -591,7 +602,7 @@ class Graph:
         if not 1 <= k < N:
             raise ValueError("n_eigenvectors must be in 1..{}, got {}".format(N, n_eigenvectors))
         if method not in ("auto", "device", "dense"):
-            raise ValueError("method must be 'auto', 'device' or 'dense', got {!r}".format(method))
+            raise ValueError("method must be 'auto', 'device', 'dense' or 'jacobi', got {!r}".format(method))
         if self._U is not None and k <= len(self._e):
             return
         from . import fourier
@@ -607,6 +618,28 @@ class Graph:
         fourier.finish_partial(e, U)
         self._release_basis_dev()
         self._e, self._U, self.fourier_stats = e, U, None
+
+    def _fourier_basis_jacobi(self, k, asked, tol, maxiter):
+        from . import fourier
+        N = self.n_vertices
+        if not 1 <= k <= N:
+            raise ValueError("n_eigenvectors must be in 1..{}, got {}".format(N, asked))
+        if self._U is not None and k <= len(self._e):
+            return
+        dev = self.device_graph(np.float64)
+        e, U, U_dev, stats = fourier.device_full_basis(dev, tol=fourier.FULL_TOL if tol is None else tol,
+                                                       max_sweeps=fourier.FULL_MAX_SWEEPS if maxiter is None else maxiter)
+        self._release_basis_dev()
+        if k == N:
+            self._e, self._U, self._U_dev, self.fourier_stats = e, U, (dev, U_dev), stats
+            self._lmax, self._lmax_method = e[-1], "fourier"
+            return
+        if U_dev.buf is not None:  # (the N x N panel is not kept for a slice: U[:, :k] is uploaded when first needed)
+            dev.ctx.give(U_dev.buf)
+            U_dev.buf = None
+        e, U = np.array(e[:k]), np.array(U[:, :k])
+        fourier.finish_partial(e, U)  # (the signs are already the rule's: this checks e[0] and sets it to zero)
+        self._e, self._U, self.fourier_stats = e, U, stats
 
     def _release_basis_dev(self):
         """Drop the device copy of U: (float64 DeviceGraph, fourier.DevicePanel) or None."""

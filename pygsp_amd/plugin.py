@@ -211,6 +211,38 @@ def _filters_logger(bank):
     return logging.getLogger(type(bank).__module__)
 
 
+# install(full_basis=True): full requests of graphs this large go to the device.  The measured crossover against the
+# host's eigh (profiles/eigh.md: host / device 0.73 at 1024 vertices, 1.57 at 2048)
+FULL_BASIS_MIN_VERTICES = 2048
+
+
+def _compute_full_basis_on_device(self, n_eigenvectors=None):
+    """What install(fourier=True, full_basis=True) puts in place of ``Graph.compute_fourier_basis``: a request for
+    all N vectors of a graph of at least FULL_BASIS_MIN_VERTICES vertices runs block Jacobi on the float64 device
+    Laplacian (pygsp_amd.fourier.device_full_basis) instead of scipy's eigh, with the reference's bookkeeping
+    (fourier.py:156-195: a cached basis is kept, ``_e``, ``_U``, e[0] checked and set to zero, ``_lmax`` = e[-1]).  The
+    solver's N x N panel is cached where basis_on_device_for looks, so ``filter(method='exact')`` under
+    install(exact=True) uploads nothing.  Partial requests follow install(fourier=True); smaller graphs run the
+    package's own code."""
+    from . import fourier
+    n = self.n_vertices if n_eigenvectors is None else int(n_eigenvectors)
+    if n != self.n_vertices or n < FULL_BASIS_MIN_VERTICES:
+        return _compute_fourier_basis_on_device(self, n_eigenvectors)
+    if self._U is not None and n <= len(self._e):
+        return
+    dev = device_graph_for(self, dtype=np.float64)
+    e, U, U_dev, _ = fourier.device_full_basis(dev)
+    fourier.finish_partial(e, U)  # (e[0] within 1e-5 of zero, then zero; the signs are set already)
+    self._e, self._U = e, U
+    self._lmax, self._lmax_method = e[-1], "fourier"
+    self._coherence = np.max(np.abs(U))
+    with _cache_lock:
+        held = self.__dict__.get("_gspx_basis")
+        if held is not None and held[2].buf is not None:
+            held[2].buf.free()
+        self.__dict__["_gspx_basis"] = (U, dev, U_dev)
+
+
 def _compute_fourier_basis_on_device(self, n_eigenvectors=None):
     """``Graph.compute_fourier_basis`` of the reference (fourier.py:97-195) with its partial branch on the device: a
     request for k < N vectors that pygsp_amd.fourier.use_device sends there (N >= 2048, a block of at most N / 4) runs
@@ -369,7 +401,7 @@ def _fruchterman_reingold_on_device(self, dim=2, k=None, pos=None, fixed=[], ite
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
             lanczos=False, features=False, learning=False, topology=False, optimization=False, harmonic=False,
-            layout=False, exact=False):
+            layout=False, exact=False, full_basis=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -386,6 +418,9 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     which is 'recurrence' unless filters.set_evaluation() changed it.
     `fourier` (default False): also replace ``Graph.compute_fourier_basis`` so that partial requests on large graphs
     run on the device (pygsp_amd.fourier); full bases and small graphs keep the reference's code.
+    `full_basis` (default False; needs ``fourier=True``): requests for the full basis of graphs of at least
+    FULL_BASIS_MIN_VERTICES vertices also run on the device (block Jacobi, pygsp_amd.fourier.device_full_basis), and the
+    N x N panel stays there for ``exact=True``.
     `lanczos` (default False): also replace ``approximations.lanczos_op`` and the ``pygsp.filters.lanczos_op`` alias
     with pygsp_amd.filters.lanczos_op (Lanczos filtering on the device, pygsp_amd.lanczos).
     `features` (default False): also replace ``pygsp.features.compute_norm_tig`` and ``compute_spectrogram`` with
@@ -407,9 +442,9 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     in 2 or 3 dimensions (gspx_layout_spring_dev); other graphs keep the reference's code.  The eigenmap kinds follow
     ``fourier=True``.
     `exact` (default False; needs ``wrap_filter=True``): ``Filter.filter(method='exact')`` and ``Modulation.filter``
-    also run on the device, against a device copy of the full ``G.U`` the reference computed (float64 signals; the
-    basis still comes from the host's eigh); ``Gabor`` follows through ``Filter.filter``.  Off, the package's own code
-    answers ``method='exact'``."""
+    also run on the device, against a device copy of the full ``G.U`` (float64 signals; the basis is the reference's
+    own eigh, uploaded once, or the device's under ``full_basis=True``); ``Gabor`` follows through ``Filter.filter``.
+    Off, the package's own code answers ``method='exact'``."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -420,6 +455,8 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         raise ValueError("harmonic=True needs learning=True")
     if exact and not wrap_filter:
         raise ValueError("exact=True needs wrap_filter=True")
+    if full_basis and not fourier:
+        raise ValueError("full_basis=True needs fourier=True")
     if pygsp_module is None:
         import pygsp as pygsp_module
     if devices is not None:
@@ -455,7 +492,8 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         if lmax == "device":
             methods["estimate_lmax"] = _estimate_lmax_on_device
         if fourier:
-            methods["compute_fourier_basis"] = _compute_fourier_basis_on_device
+            methods["compute_fourier_basis"] = (_compute_full_basis_on_device if full_basis
+                                                else _compute_fourier_basis_on_device)
         if topology:
             methods.update(zip(_TOPOLOGY, (_is_connected_on_device, _extract_components_on_device)))
         if layout:

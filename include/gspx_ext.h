@@ -182,8 +182,10 @@ int gspx_grad_dev(gspx_graph* g, int64_t Nsig, const void* x_dev, void* y_dev, d
 int gspx_div_dev(gspx_graph* g, int64_t Nsig, const void* y_dev, void* z_dev, double* kernel_ms);
 
 /* ---- k-nearest-neighbour graph construction on the device ---------------
- * Replaces, for NNtype='knn' and 1..64 dimensions (a uniform grid in 1-3 dimensions; beyond that a tiled brute
- * force whose pair distances run on the matrix cores, candidates re-evaluated in the KD-tree's arithmetic),
+ * Replaces, for NNtype='knn' and 1..4096 dimensions (a uniform grid in 1-3 dimensions; beyond that a tiled brute
+ * force whose pair distances run on the matrix cores, candidates re-evaluated in the KD-tree's arithmetic; up to
+ * 64 dimensions with the queries in registers, beyond that with a run-time dimension loop and one wave per query
+ * in the exact stages - chosen by d > 64 alone, same plan, same statistics, same bits; 1 <= k <= 64),
  * the KD-tree query, the Gaussian weights and the symmetrisation of NNGraph
  * (pygsp/graphs/nngraphs/nngraph.py:213-226, 289-297):
  *   D, NN = KDTree(X).query(X, k + 1);  sigma = mean(D[:, 1:]);  w = exp(-D^2 / sigma);
@@ -212,7 +214,7 @@ int gspx_knn_download_neighbors(gspx_knn* h, int32_t* nn, double* dist);
 /* Radius graphs: NNtype='radius' of NNGraph (nngraph.py:228-287) - neighbours within epsilon (the
  * KD-tree's ball query, squared distance <= epsilon^2), weights exp(-d^2 / sigma), sigma == 0 selects
  * the mean neighbour distance ("No neighbors found" -> GSPX_ERR_INVALID, as the reference's ValueError).
- * 1 to 64 dimensions: a grid of epsilon-sized cells up to 3-D; beyond that the candidate pairs come from an MFMA
+ * 1 to 4096 dimensions: a grid of epsilon-sized cells up to 3-D; beyond that the candidate pairs come from an MFMA
  * distance sweep (a counting pass, then a filling pass into rows of exactly those lengths) and are tested in the
  * KD-tree's arithmetic.  Result read with gspx_knn_info / gspx_knn_download_w, freed with gspx_knn_destroy. */
 int gspx_radius_build(gspx_ctx* ctx, int64_t N, int d, const double* coords, double epsilon,
@@ -267,7 +269,10 @@ int gspx_graph_setup(gspx_ctx* ctx, int64_t N, int64_t nnz, const int32_t* indpt
  * gspx_sbm_build; the handle stays valid and still serves gspx_knn_download_w): the generator classes NNGraph /
  * Sensor / StochasticBlockModel / ErdosRenyi (nngraph.py:289-313, stochasticblockmodel.py:144-181 end in
  * Graph.__init__(W)) hand the builder's handle over - no download and re-upload of W; its host copy is made
- * when somebody reads G.W.  coords may be NULL (order_mode 0 or 4).  report / *out as gspx_graph_setup. */
+ * when somebody reads G.W.  coords may be NULL (order_mode 0 or 4).  report / *out as gspx_graph_setup.
+ * coords of both set-ups: 1 to 64 columns, of which a curve reads the first two (Hilbert) or three (Morton) - the
+ * builders take up to 4096, so for a wider cloud the caller hands over its leading columns only
+ * (engine.DeviceGraph._order_args does). */
 int gspx_graph_setup_from_knn(gspx_knn* h, int lap_type, int compute_dtype, const double* coords, int d,
                               int order_mode, const int32_t* perm_in, int64_t report[12], gspx_graph** out);
 /* The ingredients of Graph._get_upper_bound (graph.py:933-960: the smallest of four classical upper bounds of

@@ -448,8 +448,8 @@ extern "C" int gspx_knn_build(gspx_ctx* ctx, int64_t N, int d, const double* coo
   if (symmetrize < 0 || symmetrize > 3)
     return set_err(GSPX_ERR_INVALID, "symmetrize: 0 average, 1 maximum / fill, 2 tril, 3 triu");
   if (N < 2 || N >= ((int64_t)1 << 31) / 64) return set_err(GSPX_ERR_INVALID, "gspx_knn_build: bad N");
-  if (d < 1 || d > 64)
-    return set_err(GSPX_ERR_INVALID, "gspx_knn_build: the device k-NN search covers 1 to 64 dimensions (got %d)", d);
+  if (d < 1 || d > 4096)
+    return set_err(GSPX_ERR_INVALID, "gspx_knn_build: the device k-NN search covers 1 to 4096 dimensions (got %d)", d);
   if (k < 1 || k > 64) return set_err(GSPX_ERR_INVALID, "gspx_knn_build: 1 <= k <= 64 (got %d)", k);
   if (k >= N)  // nngraph.py:123-127
     return set_err(GSPX_ERR_INVALID, "The number of neighbors (k=%d) must be smaller than the number of nodes (%lld).",
@@ -969,8 +969,8 @@ extern "C" int gspx_radius_build(gspx_ctx* ctx, int64_t N, int d, const double* 
   *out = nullptr;
   if (metric < 0 || metric > 2) return set_err(GSPX_ERR_INVALID, "metric: 0 euclidean, 1 manhattan, 2 max_dist");
   if (N < 1 || N >= ((int64_t)1 << 31) / 64) return set_err(GSPX_ERR_INVALID, "gspx_radius_build: bad N");
-  if (d < 1 || d > 64)
-    return set_err(GSPX_ERR_INVALID, "gspx_radius_build: the device search covers 1 to 64 dimensions (got %d)", d);
+  if (d < 1 || d > 4096)
+    return set_err(GSPX_ERR_INVALID, "gspx_radius_build: the device search covers 1 to 4096 dimensions (got %d)", d);
   if (!coords) return set_err(GSPX_ERR_INVALID, "null coordinates");
   if (!(epsilon > 0) || !std::isfinite(epsilon)) return set_err(GSPX_ERR_INVALID, "epsilon must be positive");
   if (!(sigma >= 0) || !std::isfinite(sigma)) return set_err(GSPX_ERR_INVALID, "sigma must be >= 0 (0: mean distance)");

@@ -22,6 +22,12 @@
 //                     like the grid search in 1-3 dimensions.  A query whose list overflowed (heavy ties /
 //                     duplicates) scans all points exactly instead.
 // Other metrics (manhattan, max_dist) have no product form: every query takes the exact scan of stage 4.
+//
+// Up to 64 dimensions the query lives in registers (stages 2 and 4: q[4 DT] per thread; stage 3: the operands of a
+// wave's 64 queries), DT a template constant in {4, 8, 16}.  From 65 to 4096 dimensions (learned embeddings, 5 x 5 RGB
+// patches) the same plan runs on a second set of kernels, chosen by d > 64 alone: k_bf_collect_wide loops over the
+// dimension at run time with the accumulators in registers, k_bf_exact_wide / k_bf_radius_wide serve one query per
+// wave with its row in LDS.  No wide kernel holds a row in a per-thread array (see knn_sqdist_reg for why).
 #pragma once
 
 namespace gspx {
@@ -148,13 +154,123 @@ __device__ __forceinline__ void bf_append(const int* __restrict__ off, int cap, 
   }
 }
 
-// One wave = 64 queries (four 16-query tiles, their operands in registers), sweeping all point tiles: 4 x DT
-// MFMAs per point tile, then 16 (query, point) pairs per lane are tested against the query's bound.
+// ---- what the narrow (d <= 64) and the wide (d > 64) sweep share ---------------------------------------------------
 // F = double: v_mfma_f64_16x16x4f64.  F = float: v_mfma_f32_16x16x4f32 at twice the rate - the sweep only has to
 // admit a SUPERSET of the true neighbours (k_bf_select decides in the KD-tree's arithmetic), so single precision
 // does when its rounding margin, (4 DT + 8) 2^-24 (|x|^2 + |y|^2), is small against the bounds (the caller checks);
 // the bound is rounded up and the point's norm down, towards admitting.
 typedef float bf_f4 __attribute__((ext_vector_type(4)));
+template <typename F> struct bf_mfma {
+  static constexpr bool F32 = sizeof(F) == 4;
+  typedef typename std::conditional<F32, bf_f4, bf_d4>::type acc_t;
+  static __device__ __forceinline__ acc_t mac(F a, F b, acc_t c) {
+    if constexpr (F32) return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+  }
+};
+// the query behind element e of this lane's result of query tile qt: rows kq + 4 e of the tile in the fp64 product's
+// result layout, rows 4 kq + e in the fp32 one's
+template <typename F> __device__ __forceinline__ int bf_query_of(int q0, int kq, int qt, int e) {
+  return q0 + 16 * qt + (bf_mfma<F>::F32 ? 4 * kq + e : kq + 4 * e);
+}
+// this lane's 16 bounds: tau minus the query's own norm (what is compared is |y|^2 - 2 x.y), with the rounding
+// margin of the product form; queries beyond N admit nothing
+template <typename F>
+__device__ __forceinline__ void bf_limits(F (&lim)[4][4], const double* __restrict__ norm, const double* __restrict__ tau,
+                                          int N, int q0, int kq, double margin_scale, double norm_max) {
+  constexpr bool F32 = bf_mfma<F>::F32;
+#pragma unroll
+  for (int qt = 0; qt < 4; ++qt)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int q = bf_query_of<F>(q0, kq, qt, e);
+      if (q < N) {
+        const double nq = norm[q];
+        const double l = tau[q] - nq + margin_scale * (nq + norm_max);
+        if constexpr (F32) lim[qt][e] = __double2float_ru(l);
+        else lim[qt][e] = l;
+      } else {
+        lim[qt][e] = F32 ? F(-3e38) : F(-1e300);
+      }
+    }
+}
+// a point's norm as the sweep compares it (the padding points' 1e300 stays "infinitely far" in single precision)
+template <typename F> __device__ __forceinline__ F bf_norm_of(const double* __restrict__ norm, int i) {
+  const double v = norm[i];
+  if constexpr (bf_mfma<F>::F32) return v > 3e38 ? 3e38f : __double2float_rd(v);
+  else return v;
+}
+// the j-th point tile of a sweep: phase 0 takes every step-th tile (a strided subset of the cloud: a fair sample
+// whatever order the points come in), phase 1 the tiles in between
+__device__ __forceinline__ int bf_tile_of(int phase, int step, int j) {
+  return phase == 0 ? j * step : (j / (step - 1)) * step + 1 + j % (step - 1);
+}
+// The 16 (query, point) tests of a lane for one point tile (acc: the four query tiles' products with it, nc: the
+// point's norm), folded into one mask: a single wave-wide branch per tile guards the rare appends.  (The point itself
+// is not filtered here: k_bf_select skips it.)  Hits are parked in the wave's LDS queue ((query << 32) | point, 128
+// slots) and appended 64 at a time: an append is an atomic (whose return the wave must wait for) plus a scattered
+// store, and about 60 % of the tiles hit something - appending on the spot stalled the wave a memory round trip per
+// tile.  queued is wave-uniform.
+template <typename F>
+__device__ __forceinline__ void bf_test_tile(const typename bf_mfma<F>::acc_t (&acc)[4], F nc, const F (&lim)[4][4], int ct,
+                                             int q0, int lane, unsigned long long lt_mask,
+                                             volatile unsigned long long* queue, int& queued, const int* __restrict__ off, int cap, int* __restrict__ cnt,
+                                             int* __restrict__ buf) {
+  const int kq = lane >> 4, cq = lane & 15;
+  // D layout: lane (kq, cq) holds query rows kq + 4 e (fp64) / 4 kq + e (fp32), point column cq
+  // (the tests are folded with a scalar OR of the compare masks: two vector instructions per pair)
+  bool any = false;
+#pragma unroll
+  for (int qt = 0; qt < 4; ++qt)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) any |= nc - F(2) * acc[qt][e] <= lim[qt][e];
+  if (__builtin_amdgcn_ballot_w64(any) != 0) {
+    const int c = ct * 16 + cq;
+#pragma unroll
+    for (int qt = 0; qt < 4; ++qt)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool hit = nc - F(2) * acc[qt][e] <= lim[qt][e];
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+        if (m != 0) {
+          if (hit) {
+            const int pos = queued + __popcll(m & lt_mask);
+            queue[pos] = ((unsigned long long)(unsigned)bf_query_of<F>(q0, kq, qt, e) << 32) | (unsigned)c;
+          }
+          queued += __popcll(m);
+          if (queued >= 64) {  // at most 127 parked: room for one more round of 64
+            __builtin_amdgcn_wave_barrier();
+            const unsigned long long it = queue[lane];
+            const int iq = (int)(it >> 32), ic = (int)(unsigned)it;
+            const int slot = atomicAdd(&cnt[iq], 1);
+            bf_append(off, cap, iq, slot, ic, buf);
+            const int rest = queued - 64;
+            unsigned long long mv = 0;
+            if (lane < rest) mv = queue[64 + lane];
+            __builtin_amdgcn_wave_barrier();
+            if (lane < rest) queue[lane] = mv;
+            __builtin_amdgcn_wave_barrier();
+            queued = rest;
+          }
+        }
+      }
+  }
+}
+// what is still parked when the sweep ends
+__device__ __forceinline__ void bf_flush(int lane, volatile unsigned long long* queue, int queued,
+                                         const int* __restrict__ off, int cap, int* __restrict__ cnt,
+                                         int* __restrict__ buf) {
+  __builtin_amdgcn_wave_barrier();
+  if (lane < queued) {
+    const unsigned long long it = queue[lane];
+    const int iq = (int)(it >> 32), ic = (int)(unsigned)it;
+    const int slot = atomicAdd(&cnt[iq], 1);
+    bf_append(off, cap, iq, slot, ic, buf);
+  }
+}
+
+// One wave = 64 queries (four 16-query tiles, their operands in registers), sweeping all point tiles: 4 x DT
+// MFMAs per point tile, then 16 (query, point) pairs per lane are tested against the query's bound.
 template <int DT, typename F>
 __global__ __launch_bounds__(256) void k_bf_collect(const F* __restrict__ xop, const double* __restrict__ norm,
                                                     const double* __restrict__ tau, int N, int phase, int step,
@@ -165,8 +281,7 @@ __global__ __launch_bounds__(256) void k_bf_collect(const F* __restrict__ xop, c
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int q0 = wave * 64;
   if (q0 >= N) return;
-  constexpr bool F32 = sizeof(F) == 4;
-  typedef typename std::conditional<F32, bf_f4, bf_d4>::type acc_t;
+  typedef typename bf_mfma<F>::acc_t acc_t;
   const int ntiles = (N + 15) / 16;
   F a[4][DT];
 #pragma unroll
@@ -175,47 +290,20 @@ __global__ __launch_bounds__(256) void k_bf_collect(const F* __restrict__ xop, c
 #pragma unroll
     for (int t = 0; t < DT; ++t) a[qt][t] = tile < ntiles ? xop[(tile * DT + t) * 64 + lane] : F(0);
   }
-  // this lane's 16 queries - rows kq + 4 e of a query tile in the fp64 product's result layout, rows 4 kq + e in
-  // the fp32 one's -; bound minus the query's own norm (what is compared is |y|^2 - 2 x.y), with the rounding
-  // margin of the product form
-  auto query_of = [&](int qt, int e) { return q0 + 16 * qt + (F32 ? 4 * kq + e : kq + 4 * e); };
   F lim[4][4];
-#pragma unroll
-  for (int qt = 0; qt < 4; ++qt)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int q = query_of(qt, e);
-      if (q < N) {
-        const double nq = norm[q];
-        const double l = tau[q] - nq + margin_scale * (nq + norm_max);
-        if constexpr (F32) lim[qt][e] = __double2float_ru(l);
-        else lim[qt][e] = l;
-      } else {
-        lim[qt][e] = F32 ? F(-3e38) : F(-1e300);
-      }
-    }
+  bf_limits<F>(lim, norm, tau, N, q0, kq, margin_scale, norm_max);
   // Software pipeline: a tile's operands AND its norms are loaded one tile ahead, so no load issued in an
   // iteration is waited for in that iteration (the first version loaded the norm at the top of the tile and
   // paid an L2 round trip per tile: the matrix cores idled two thirds of the time).  The four query tiles'
-  // product chains are interleaved (four independent accumulators in flight, no stall on a chain's own result),
-  // and the 16 (query, point) tests of a lane are folded into one mask: a single wave-wide branch per tile
-  // guards the rare appends.  (The point itself is not filtered here: k_bf_select skips it.)
-  __shared__ unsigned long long queue_all[4][128];  // (query << 32) | point
+  // product chains are interleaved (four independent accumulators in flight, no stall on a chain's own result).
+  __shared__ unsigned long long queue_all[4][128];
   volatile unsigned long long* queue = queue_all[threadIdx.x >> 6];
-  const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));  // the lanes before this one
   int queued = 0;  // wave-uniform
   F b[DT], b_next[DT], n_next;
-  auto norm_of = [&](int i) {  // (the padding points' 1e300 stays "infinitely far" in single precision)
-    const double v = norm[i];
-    if constexpr (F32) return v > 3e38 ? 3e38f : __double2float_rd(v);
-    else return v;
-  };
-  // the j-th point tile of this sweep: phase 0 takes every step-th tile (a strided subset of the cloud: a fair
-  // sample whatever order the points come in), phase 1 the tiles in between
-  auto tile_of = [&](int j) { return phase == 0 ? j * step : (j / (step - 1)) * step + 1 + j % (step - 1); };
-  int ct_next = tile_of(0);
+  int ct_next = bf_tile_of(phase, step, 0);
   {
-    n_next = norm_of(ct_next * 16 + cq);
+    n_next = bf_norm_of<F>(norm, ct_next * 16 + cq);
 #pragma unroll
     for (int t = 0; t < DT; ++t) b_next[t] = xop[((long long)ct_next * DT + t) * 64 + lane];
   }
@@ -225,8 +313,8 @@ __global__ __launch_bounds__(256) void k_bf_collect(const F* __restrict__ xop, c
 #pragma unroll
     for (int t = 0; t < DT; ++t) b[t] = b_next[t];
     if (j + 1 < count) {
-      ct_next = tile_of(j + 1);
-      n_next = norm_of(ct_next * 16 + cq);  // (padded: no bounds test between the load and its use a tile later)
+      ct_next = bf_tile_of(phase, step, j + 1);
+      n_next = bf_norm_of<F>(norm, ct_next * 16 + cq);  // (padded: no bounds test between the load and its use a tile later)
 #pragma unroll
       for (int t = 0; t < DT; ++t) b_next[t] = xop[((long long)ct_next * DT + t) * 64 + lane];
     }
@@ -236,59 +324,101 @@ __global__ __launch_bounds__(256) void k_bf_collect(const F* __restrict__ xop, c
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
-      for (int qt = 0; qt < 4; ++qt) {
-        if constexpr (F32) acc[qt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[qt][t], b[t], acc[qt], 0, 0, 0);
-        else acc[qt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[qt][t], b[t], acc[qt], 0, 0, 0);
-      }
-    // D layout: lane (kq, cq) holds query rows kq + 4 e (fp64) / 4 kq + e (fp32), point column cq
-    // (the tests are folded with a scalar OR of the compare masks: two vector instructions per pair)
-    bool any = false;
+      for (int qt = 0; qt < 4; ++qt) acc[qt] = bf_mfma<F>::mac(a[qt][t], b[t], acc[qt]);
+    bf_test_tile<F>(acc, nc, lim, ct, q0, lane, lt_mask, queue, queued, off, cap, cnt, buf);
+  }
+  bf_flush(lane, queue, queued, off, cap, cnt, buf);
+}
+
+// The sweep in more than 64 dimensions: the dimension is a run-time loop over 4-column MFMA steps (DT = ceil(d / 4)
+// of them), so neither the 64 queries' operands nor a point tile's fit in registers.  A wave keeps the ACCUMULATORS
+// there instead - 4 query tiles x 4 point tiles, 16 independent product chains across the whole dimension loop -, so
+// every operand it reads feeds four MFMAs.  The four waves of a workgroup (256 queries) sweep the same four point tiles:
+// their operands go through LDS, BF_WS steps at a time (each wave loads one tile's share, double buffered: one
+// barrier per 16 BF_WS MFMAs of a wave); the queries' operands stream from xop for every group (already in operand
+// order: one coalesced line per load; from the L2 while the array fits it, profiles/knn_wide.md).  Bounds, tests, hit
+// queue, norm pipelining (a group ahead) and tile order are the narrow kernel's.
+constexpr int BF_WS = 4;
+template <typename F>
+__global__ __launch_bounds__(256) void k_bf_collect_wide(const F* __restrict__ xop, const double* __restrict__ norm,
+                                                         const double* __restrict__ tau, int N, int DT, int phase,
+                                                         int step, int count, double margin_scale, double norm_max,
+                                                         int cap, const int* __restrict__ off, int* __restrict__ cnt,
+                                                         int* __restrict__ buf) {
+  if (count <= 0) return;
+  const int lane = threadIdx.x & 63, kq = lane >> 4, cq = lane & 15, w = threadIdx.x >> 6;
+  const int q0 = (blockIdx.x * 4 + w) * 64;  // (a wave beyond N stays for the barriers: its bounds admit nothing)
+  typedef typename bf_mfma<F>::acc_t acc_t;
+  const int ntiles = (N + 15) / 16;
+  const F* ap[4];
 #pragma unroll
-    for (int qt = 0; qt < 4; ++qt)
+  for (int qt = 0; qt < 4; ++qt) ap[qt] = xop + (long long)min(q0 / 16 + qt, ntiles - 1) * DT * 64 + lane;
+  F lim[4][4];
+  bf_limits<F>(lim, norm, tau, N, q0, kq, margin_scale, norm_max);
+  __shared__ unsigned long long queue_all[4][128];
+  __shared__ F bs[2][4][BF_WS][64];
+  volatile unsigned long long* queue = queue_all[w];
+  const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  int queued = 0;  // wave-uniform
+  const int nchunks = (DT + BF_WS - 1) / BF_WS, ngroups = (count + 3) / 4;
+  // this wave's share of a chunk's point operands: tile 4 g + w of the sweep (the last group repeats the last
+  // tile: finite operands, and a norm that admits nothing), steps BF_WS c .. + BF_WS (zero beyond DT)
+  auto stage = [&](int g, int c, F (&r)[BF_WS]) {
+    const F* bp = xop + (long long)bf_tile_of(phase, step, min(4 * g + w, count - 1)) * DT * 64 + lane;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) any |= nc - F(2) * acc[qt][e] <= lim[qt][e];
-    if (__builtin_amdgcn_ballot_w64(any) != 0) {
-      // Hits are parked in the wave's LDS queue and appended 64 at a time: an append is an atomic (whose return the
-      // wave must wait for) plus a scattered store, and about 60 % of the tiles hit something - appending on the
-      // spot stalled the wave a memory round trip per tile.
-      const int c = ct * 16 + cq;
+    for (int s = 0; s < BF_WS; ++s) r[s] = BF_WS * c + s < DT ? bp[(long long)(BF_WS * c + s) * 64] : F(0);
+  };
+  auto norms = [&](int g, F (&n)[4]) {
 #pragma unroll
-      for (int qt = 0; qt < 4; ++qt)
+    for (int p = 0; p < 4; ++p)
+      n[p] = 4 * g + p < count ? bf_norm_of<F>(norm, bf_tile_of(phase, step, 4 * g + p) * 16 + cq)
+                               : (bf_mfma<F>::F32 ? F(3e38) : F(1e300));
+  };
+  F r[BF_WS], nc[4], n_next[4];
+  stage(0, 0, r);
+  norms(0, n_next);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool hit = nc - F(2) * acc[qt][e] <= lim[qt][e];
-          const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-          if (m != 0) {
-            if (hit) {
-              const int pos = queued + __popcll(m & lt_mask);
-              queue[pos] = ((unsigned long long)(unsigned)query_of(qt, e) << 32) | (unsigned)c;
-            }
-            queued += __popcll(m);
-            if (queued >= 64) {  // at most 127 parked: room for one more round of 64
-              __builtin_amdgcn_wave_barrier();
-              const unsigned long long it = queue[lane];
-              const int iq = (int)(it >> 32), ic = (int)(unsigned)it;
-              const int slot = atomicAdd(&cnt[iq], 1);
-              bf_append(off, cap, iq, slot, ic, buf);
-              const int rest = queued - 64;
-              unsigned long long mv = 0;
-              if (lane < rest) mv = queue[64 + lane];
-              __builtin_amdgcn_wave_barrier();
-              if (lane < rest) queue[lane] = mv;
-              __builtin_amdgcn_wave_barrier();
-              queued = rest;
-            }
-          }
-        }
+  for (int s = 0; s < BF_WS; ++s) bs[0][w][s][lane] = r[s];
+  __syncthreads();
+  acc_t acc[4][4];  // [point tile][query tile]
+  int it = 0;
+  for (int g = 0; g < ngroups; ++g) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      nc[p] = n_next[p];
+#pragma unroll
+      for (int qt = 0; qt < 4; ++qt) acc[p][qt] = acc_t{0, 0, 0, 0};
     }
+    if (g + 1 < ngroups) norms(g + 1, n_next);  // a group ahead: not waited for in this group
+    for (int c = 0; c < nchunks; ++c, ++it) {
+      const bool more = c + 1 < nchunks || g + 1 < ngroups;
+      if (more) stage(c + 1 < nchunks ? g : g + 1, c + 1 < nchunks ? c + 1 : 0, r);
+      const int cur = it & 1;
+#pragma unroll
+      for (int s = 0; s < BF_WS; ++s) {
+        const long long t = min(BF_WS * c + s, DT - 1);  // (beyond DT the point operands are zero)
+        F a[4], b[4];
+#pragma unroll
+        for (int qt = 0; qt < 4; ++qt) a[qt] = ap[qt][t * 64];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) b[p] = bs[cur][p][s][lane];
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+          for (int qt = 0; qt < 4; ++qt) acc[p][qt] = bf_mfma<F>::mac(a[qt], b[p], acc[p][qt]);
+      }
+      if (more) {
+#pragma unroll
+        for (int s = 0; s < BF_WS; ++s) bs[cur ^ 1][w][s][lane] = r[s];
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      bf_test_tile<F>(acc[p], nc[p], lim, bf_tile_of(phase, step, min(4 * g + p, count - 1)), q0, lane, lt_mask, queue, queued,
+                      off, cap, cnt, buf);
   }
-  __builtin_amdgcn_wave_barrier();
-  if (lane < queued) {  // what is still parked
-    const unsigned long long it = queue[lane];
-    const int iq = (int)(it >> 32), ic = (int)(unsigned)it;
-    const int slot = atomicAdd(&cnt[iq], 1);
-    bf_append(off, cap, iq, slot, ic, buf);
-  }
+  bf_flush(lane, queue, queued, off, cap, cnt, buf);
 }
 
 // Between the two sweeps: the exact k-th smallest key among a query's candidates so far (all from the first
@@ -374,6 +504,84 @@ __global__ __launch_bounds__(128) void k_bf_select(const double* __restrict__ x,
     }
 }
 
+// ---- exact evaluation in more than 64 dimensions --------------------------------------------------------------
+// A query row of that width in a per-thread array would live in scratch memory (see knn_sqdist_reg), so here ONE WAVE
+// serves a query: the row is staged once in LDS (d doubles; every lane reads the same word: a broadcast), the lanes take
+// different candidates - each key is still computed by one thread, in the KD-tree's order (knn_key) - and the best 64
+// by (key, index) are kept sorted ACROSS the wave, lane t holding the t-th: no per-thread list either, and one build
+// for every k <= 64.
+struct bf_best {
+  double d;
+  int i;
+};
+// the wave's candidates of one round (cd / ci per lane, live: this lane has one) merged into the sorted list: only
+// those below the k-th entry (rare once the list has settled) are inserted, one at a time, by a shift across lanes
+__device__ __forceinline__ void bf_wave_merge(bf_best& best, double cd, int ci, bool live, int k, int lane) {
+  const double td = __shfl(best.d, k - 1);
+  const int ti = __shfl(best.i, k - 1);
+  unsigned long long m = __builtin_amdgcn_ballot_w64(live && (cd < td || (cd == td && ci < ti)));
+  while (m != 0) {  // wave-uniform
+    const int src = __builtin_ctzll(m);
+    m &= m - 1;
+    const double vd = __shfl(cd, src);
+    const int vi = __shfl(ci, src);
+    const unsigned long long after = __builtin_amdgcn_ballot_w64(vd < best.d || (vd == best.d && vi < best.i));
+    const double pd = __shfl_up(best.d, 1);
+    const int pi = __shfl_up(best.i, 1);
+    if (after != 0) {  // the entries from the first larger one on move up a lane (the 64th drops out)
+      const int pos = __builtin_ctzll(after);
+      if (lane > pos) best.d = pd, best.i = pi;
+      else if (lane == pos) best.d = vd, best.i = vi;
+    }
+  }
+}
+__device__ __forceinline__ void bf_stage_query(double* qs, const double* __restrict__ row, int d, int lane) {
+  for (int j = lane; j < d; j += 64) qs[j] = row[j];
+  __syncthreads();  // (a one-wave workgroup)
+}
+// WHAT 0: k_bf_tau (candidates: the strided sample), 1: k_bf_refine (the candidates so far), 2: k_bf_select (the
+// candidates, or every point).  One 64-thread workgroup per query; dynamic LDS: d doubles.
+template <int WHAT>
+__global__ __launch_bounds__(64) void k_bf_exact_wide(const double* __restrict__ x, int N, int d, int k, int metric,
+                                                      int stride, int cap, const int* __restrict__ cnt,
+                                                      const int* __restrict__ buf, double* __restrict__ tau,
+                                                      int* __restrict__ nn, double* __restrict__ dist,
+                                                      int* __restrict__ n_scans) {
+  extern __shared__ double bf_qs[];
+  const int i = blockIdx.x, lane = threadIdx.x;
+  bf_stage_query(bf_qs, x + (size_t)i * d, d, lane);
+  bf_best best{1e300, 0x7fffffff};
+  bool scan = false;
+  int n;
+  if (WHAT == 0) {
+    n = (N + stride - 1) / stride;
+  } else if (WHAT == 1) {
+    n = min(cnt[i], cap);
+  } else {
+    const int have = cnt ? cnt[i] : -1;
+    scan = have < 0 || have > cap || have < k;
+    n = scan ? N : have;
+    if (scan && cnt && lane == 0) atomicAdd(n_scans, 1);
+  }
+  for (int base = 0; base < n; base += 64) {
+    const int a = base + lane;
+    int idx = 0x7fffffff;
+    if (a < n) idx = WHAT == 0 ? a * stride : (scan ? a : buf[(size_t)i * cap + a]);
+    const bool live = a < n && idx != i;
+    double cd = 1e300;
+    if (live) cd = knn_key(bf_qs, x + (size_t)idx * d, d, WHAT == 2 ? metric : 0);
+    bf_wave_merge(best, cd, idx, live, k, lane);
+  }
+  if (WHAT == 2) {
+    if (lane < k) {
+      nn[(size_t)i * k + lane] = best.i;
+      dist[(size_t)i * k + lane] = metric == 0 ? knn_sqrt(best.d) : best.d;
+    }
+  } else if (lane == k - 1) {
+    if (WHAT == 0 || best.d < tau[i]) tau[i] = best.d;
+  }
+}
+
 }  // namespace gspx
 
 template <int KMAX, int DT>
@@ -398,11 +606,28 @@ static void launch_bf_k(gspx_ctx* ctx, const double* x, int N, int d, int k, int
 // what: 0 the sample bounds (k_bf_tau), 1 their refinement between the sweeps (k_bf_refine), 2 the selection
 static void launch_bf(gspx_ctx* ctx, const double* x, int N, int d, int k, int metric, int stride, double* tau, int cap,
                       const int* cnt, const int* buf, int* nn, double* dist, int* n_scans, int what) {
+  if (d > 64) {  // one wave per query, one build for every k (k_bf_exact_wide)
+    const dim3 grid((unsigned)N), block(64);
+    const size_t lds = (size_t)d * sizeof(double);
+    if (what == 0)
+      hipLaunchKernelGGL((gspx::k_bf_exact_wide<0>), grid, block, lds, ctx->stream, x, N, d, k, metric, stride, cap, cnt, buf,
+                         tau, nn, dist, n_scans);
+    else if (what == 1)
+      hipLaunchKernelGGL((gspx::k_bf_exact_wide<1>), grid, block, lds, ctx->stream, x, N, d, k, metric, stride, cap, cnt, buf,
+                         tau, nn, dist, n_scans);
+    else
+      hipLaunchKernelGGL((gspx::k_bf_exact_wide<2>), grid, block, lds, ctx->stream, x, N, d, k, metric, stride, cap, cnt, buf,
+                         tau, nn, dist, n_scans);
+    return;
+  }
   if (k <= 8) launch_bf_k<8>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
   else if (k <= 16) launch_bf_k<16>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
   else if (k <= 32) launch_bf_k<32>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
   else launch_bf_k<64>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
 }
+
+// 4-column MFMA steps of the sweep: the narrow builds' template constant up to 64 dimensions, ceil(d / 4) beyond
+static int bf_steps(int d) { return d <= 16 ? 4 : (d <= 32 ? 8 : (d <= 64 ? 16 : (d + 3) / 4)); }
 
 // x: N x d doubles on the device; nn / dist: N x k outputs (nearest first, the point itself excluded).
 // stats (nullable, 4 values): sample size, candidate capacity per query, mean candidates per query, queries that
@@ -420,7 +645,7 @@ static int knn_bruteforce(gspx_ctx* ctx, const double* x, int N, int d, int k, i
     if (stats) stats[0] = 0, stats[1] = 0, stats[2] = (double)N, stats[3] = (double)N;
     return GSPX_OK;
   }
-  const int DT = d <= 16 ? 4 : (d <= 32 ? 8 : 16);
+  const int DT = bf_steps(d);
   const int ntiles = (N + 15) / 16;
   // sample: about max(2048, N / 128) points (at least 4 k + 1), strided through the cloud
   const int want = std::max(std::max(2048, N / 128), 4 * k + 1);
@@ -458,6 +683,7 @@ static int knn_bruteforce(gspx_ctx* ctx, const double* x, int N, int d, int k, i
   double nmax = 0;
   for (double v : hn) nmax = std::max(nmax, v);
   // |fl(|y|^2 - 2 x.y) + |x|^2 - |x - y|^2| <= (4 DT + 8) u (|x|^2 + |y|^2) with u = 2^-53; ten times that
+  // (DT = ceil(d / 4) steps beyond 64 dimensions: the bound grows with the length of the dot product)
   const double margin64 = 10.0 * (4.0 * DT + 8.0) * 1.1102230246251565e-16;
   // The same bound with u = 2^-24 for the single-precision sweep: used when it widens a typical bound (the
   // median over a sample of the queries) by at most half a percent - clouds far from the origin (|x|^2 >> the
@@ -485,7 +711,16 @@ static int knn_bruteforce(gspx_ctx* ctx, const double* x, int N, int d, int k, i
                          buf.as<int>());                                                                                 \
   } while (0)
   auto sweep = [&](int phase, int count) {
-    if (DT == 4) GSPX_BF(4, phase, count);
+    if (d > 64) {
+      if (use32)
+        hipLaunchKernelGGL((gspx::k_bf_collect_wide<float>), grid, dim3(256), 0, st, xop32.as<float>(), norm.as<double>(),
+                           tau.as<double>(), N, DT, phase, step, count, margin, nmax, cap, (const int*)nullptr,
+                           cnt.as<int>(), buf.as<int>());
+      else
+        hipLaunchKernelGGL((gspx::k_bf_collect_wide<double>), grid, dim3(256), 0, st, xop.as<double>(), norm.as<double>(),
+                           tau.as<double>(), N, DT, phase, step, count, margin, nmax, cap, (const int*)nullptr,
+                           cnt.as<int>(), buf.as<int>());
+    } else if (DT == 4) GSPX_BF(4, phase, count);
     else if (DT == 8) GSPX_BF(8, phase, count);
     else GSPX_BF(16, phase, count);
   };
@@ -548,6 +783,37 @@ __global__ __launch_bounds__(128) void k_bf_radius(const double* __restrict__ x,
   if (!PASS) cnt[i] = m;
 }
 
+// the same two passes in more than 64 dimensions: one wave per query, its row in LDS, the lanes on different
+// candidates (k_bf_exact_wide); a round's members keep their candidate order (k_knn_row_sort orders the row later)
+template <int PASS>
+__global__ __launch_bounds__(64) void k_bf_radius_wide(const double* __restrict__ x, int N, int d, int metric, double eps2,
+                                                       const int* __restrict__ off, const int* __restrict__ buf,
+                                                       int* __restrict__ cnt, const int* __restrict__ rowptr,
+                                                       int* __restrict__ col, double* __restrict__ dist) {
+  extern __shared__ double bf_qs[];
+  const int i = blockIdx.x, lane = threadIdx.x;
+  bf_stage_query(bf_qs, x + (size_t)i * d, d, lane);
+  const int lo = off ? off[i] : 0, n = off ? off[i + 1] - lo : N;
+  const int o = PASS ? rowptr[i] : 0;
+  const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  int m = 0;  // wave-uniform
+  for (int base = 0; base < n; base += 64) {
+    const int a = base + lane;
+    const int idx = a < n ? (off ? buf[(size_t)lo + a] : a) : i;
+    double key = 1e300;
+    if (idx != i) key = knn_key(bf_qs, x + (size_t)idx * d, d, metric);
+    const bool in = idx != i && key <= eps2;
+    const unsigned long long hits = __builtin_amdgcn_ballot_w64(in);
+    if (PASS && in) {
+      const int at = o + m + __popcll(hits & lt_mask);
+      col[at] = idx;
+      dist[at] = metric == 0 ? knn_sqrt(key) : key;
+    }
+    m += __popcll(hits);
+  }
+  if (!PASS && lane == 0) cnt[i] = m;
+}
+
 }  // namespace gspx
 
 template <int PASS>
@@ -557,7 +823,10 @@ static void launch_bf_radius(gspx_ctx* ctx, const double* x, int N, int d, int m
 #define GSPX_BR(D_)                                                                                                   \
   hipLaunchKernelGGL((gspx::k_bf_radius<PASS, D_>), grid, dim3(128), 0, ctx->stream, x, N, d, metric, eps2, off, buf, cnt, \
                      rowptr, col, dist)
-  if (d <= 16) GSPX_BR(4);
+  if (d > 64)
+    hipLaunchKernelGGL((gspx::k_bf_radius_wide<PASS>), dim3((unsigned)N), dim3(64), (size_t)d * sizeof(double), ctx->stream,
+                       x, N, d, metric, eps2, off, buf, cnt, rowptr, col, dist);
+  else if (d <= 16) GSPX_BR(4);
   else if (d <= 32) GSPX_BR(8);
   else GSPX_BR(16);
 #undef GSPX_BR
@@ -568,7 +837,7 @@ static void launch_bf_radius(gspx_ctx* ctx, const double* x, int N, int d, int m
 // Leaves off (N + 1) and buf; euclidean only (the other metrics scan every point in k_bf_radius).
 static int radius_candidates(gspx_ctx* ctx, const double* x, int N, int d, double eps2, DevMem& off, DevMem& buf) {
   hipStream_t st = ctx->stream;
-  const int DT = d <= 16 ? 4 : (d <= 32 ? 8 : 16);
+  const int DT = bf_steps(d);
   const int ntiles = (N + 15) / 16;
   DevMem xop, norm, tau, cnt;
   CHK(xop.alloc((size_t)ntiles * DT * 64 * sizeof(double)));
@@ -592,7 +861,10 @@ static int radius_candidates(gspx_ctx* ctx, const double* x, int N, int d, doubl
 #define GSPX_BF(D_)                                                                                                  \
   hipLaunchKernelGGL((gspx::k_bf_collect<D_, double>), grid, dim3(256), 0, st, xop.as<double>(), norm.as<double>(),  \
                      tau.as<double>(), N, 0, 1, ntiles, margin, nmax, 0, offp, cnt.as<int>(), bufp)
-    if (DT == 4) GSPX_BF(4);
+    if (d > 64)
+      hipLaunchKernelGGL((gspx::k_bf_collect_wide<double>), grid, dim3(256), 0, st, xop.as<double>(), norm.as<double>(),
+                         tau.as<double>(), N, DT, 0, 1, ntiles, margin, nmax, 0, offp, cnt.as<int>(), bufp);
+    else if (DT == 4) GSPX_BF(4);
     else if (DT == 8) GSPX_BF(8);
     else GSPX_BF(16);
 #undef GSPX_BF

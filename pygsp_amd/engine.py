@@ -806,7 +806,10 @@ class DeviceGraph:
             mode = cls.ORDER_MODES[order]
         if mode in (1, 2, 3):
             if _curve_coords(coords, N) and N >= 4096:
-                xy = np.ascontiguousarray(coords, dtype=np.float64)
+                xy = np.asarray(coords)
+                if xy.shape[1] > 64:  # the set-up takes up to 64 columns; a curve reads the first two or three
+                    xy = xy[:, :3]
+                xy = np.ascontiguousarray(xy, dtype=np.float64)
                 d = xy.shape[1]
             else:
                 mode = 0
@@ -1445,8 +1448,9 @@ def _adjacency(h, ctx, N, keep_on_device, weights=np.float64, neighbors=None):
 def knn_graph(coords, k, sigma=None, ctx=None, neighbors=False, metric="euclidean", symmetrize="average",
               keep_on_device=False):
     """k-nearest-neighbour weights on the device (gspx_knn_build): the KD-tree query, Gaussian weights
-    and symmetrisation of NNGraph (nngraph.py:213-226, 289-297) in 1 to 64 dimensions (a uniform grid in 1-3-D;
-    beyond that a tiled brute force whose pair distances run on the matrix cores).  coords: (N, d), already centred / rescaled.  Returns (W csr float64, sigma, info)
+    and symmetrisation of NNGraph (nngraph.py:213-226, 289-297) in 1 to 4096 dimensions, 1 <= k <= 64 (a uniform grid
+    in 1-3-D; beyond that a tiled brute force whose pair distances run on the matrix cores - from 65 dimensions on with
+    a run-time dimension loop, same results).  coords: (N, d), already centred / rescaled.  Returns (W csr float64, sigma, info)
     where info = {"build_ms": ...} plus "NN", "D" (N x k, nearest first) when neighbors=True.  keep_on_device: W is
     returned as a DeviceAdjacency (not downloaded)."""
     ctx = ctx or default_context()
@@ -1467,7 +1471,7 @@ def knn_graph(coords, k, sigma=None, ctx=None, neighbors=False, metric="euclidea
 
 def radius_graph(coords, epsilon, sigma=None, ctx=None, metric="euclidean", keep_on_device=False):
     """Radius-graph weights on the device (gspx_radius_build): NNtype='radius' of NNGraph
-    (nngraph.py:228-287) in 1 to 64 dimensions (a grid of epsilon-sized cells up to 3-D; beyond that the candidates of
+    (nngraph.py:228-287) in 1 to 4096 dimensions (a grid of epsilon-sized cells up to 3-D; beyond that the candidates of
     an MFMA distance sweep, tested in the KD-tree's arithmetic).  Returns (W csr float64, sigma, info)."""
     ctx = ctx or default_context()
     X = np.ascontiguousarray(coords, dtype=np.float64)

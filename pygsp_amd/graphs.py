@@ -17,6 +17,9 @@ Mirrors (same names, argument meaning and exceptions) the parts of
 Everything else of the reference's Graph (plotting, I/O, ...) is out of scope; use
 the real pygsp together with ``pygsp_amd.plugin.install()`` for those.
 
+NNGraph / ImgPatches / Grid2d / Grid2dImgPatches (nngraphs/, grid2d.py) build their W here: the neighbour search on
+the device (1 to 4096 dimensions), patches and grid on the host.
+
 The synthetic generators at the bottom (Sensor, ErdosRenyi, StochasticBlockModel) are vectorised
 samplers of the same distributions as the reference's constructors (the reference's ER/SBM
 constructors are O(N^2) Python loops, stochasticblockmodel.py:125-139, unusable at N >= 1e5).
@@ -777,7 +780,7 @@ _MINKOWSKI = {1: "manhattan", 2: "euclidean", np.inf: "max_dist"}
 
 class NNGraph(Graph):
     """Nearest-neighbour graph from a point cloud (nngraphs/nngraph.py:13-313), built on the device
-    (NNtype='knn', the KD-tree query, and NNtype='radius', the ball query: 1 to 64 dimensions), dist_type
+    (NNtype='knn', the KD-tree query, and NNtype='radius', the ball query: 1 to 4096 dimensions, k up to 64), dist_type
     'euclidean' / 'manhattan' / 'max_dist', every symmetrize_type of utils.symmetrize.  Other settings
     raise NotImplementedError (no host fallback)."""
 
@@ -817,6 +820,70 @@ class NNGraph(Graph):
                                                       keep_on_device=True)
         self.knn_build_ms = info["build_ms"]
         Graph.__init__(self, W, plotting=plotting, coords=points, **kwargs)
+
+
+def image_patches(img, patch_shape):
+    """Feature matrix of ``graphs.ImgPatches`` (nngraphs/imgpatches.py:52-99), on the host and without scikit-image:
+    one row per pixel (raster order), holding the r x c window around it - all channels of a colour image, channel
+    fastest - cut from the image padded symmetrically by ((r - 1) // 2, r // 2) rows and ((c - 1) // 2, c // 2)
+    columns.  patch_shape: (r, c), or (r,) for a square window.  Returns (h * w, r * c * channels)."""
+    pixels = np.asanyarray(img)
+    if pixels.ndim not in (2, 3):
+        raise ValueError("Image should be at least a 2D array.")
+    window = tuple(patch_shape) if len(patch_shape) == 2 else (patch_shape[0], patch_shape[0])
+    margins = [((side - 1) // 2, side // 2) for side in window]
+    if pixels.ndim == 3:  # the window spans every channel
+        margins.append((0, 0))
+        window += (pixels.shape[2],)
+    padded = np.pad(pixels, margins, mode="symmetric")
+    views = np.lib.stride_tricks.sliding_window_view(padded, window)
+    return views.reshape(pixels.shape[0] * pixels.shape[1], -1)
+
+
+class ImgPatches(NNGraph):
+    """Nearest-neighbour graph between the patches of an image (nngraphs/imgpatches.py:8-105): one vertex per pixel,
+    its feature vector (``Xin``) the patch around it (``image_patches``); the neighbour search runs on the device -
+    5 x 5 patches of an RGB image are a 75-dimensional cloud.  kwargs go to NNGraph."""
+
+    def __init__(self, img, patch_shape=(3, 3), **kwargs):
+        self.img, self.patch_shape = img, patch_shape
+        NNGraph.__init__(self, image_patches(img, patch_shape), **kwargs)
+
+
+def grid2d_weights(N1, N2=None, diagonal=0.0):
+    """W and coordinates of ``graphs.Grid2d`` (grid2d.py:37-86), on the host: vertex a * N2 + b sits in row a, column
+    b of an N1 x N2 grid; unit edges to the right and downward neighbour, edges of weight `diagonal` to the two
+    downward diagonal ones (when there are two rows and columns at least); coordinates (b / N2, (N1 - 1 - a) / N1)."""
+    N2 = N1 if N2 is None else N2
+    a, b = np.divmod(np.arange(N1 * N2), N2)
+    steps = [(b < N2 - 1, 1, 1.0), (a < N1 - 1, N2, 1.0)]
+    if diagonal != 0.0 and N1 > 1 and N2 > 1:
+        steps += [((a < N1 - 1) & (b < N2 - 1), N2 + 1, diagonal), ((a < N1 - 1) & (b > 0), N2 - 1, diagonal)]
+    src = np.concatenate([np.flatnonzero(ok) for ok, _, _ in steps])
+    dst = np.concatenate([np.flatnonzero(ok) + jump for ok, jump, _ in steps])
+    wgt = np.concatenate([np.full(np.count_nonzero(ok), value) for ok, _, value in steps])
+    half = sparse.coo_matrix((wgt, (src, dst)), shape=(N1 * N2, N1 * N2))
+    coords = np.column_stack((b / float(N2), (N1 - 1 - a) / float(N1)))
+    return sparse.csr_matrix(half + half.T), coords
+
+
+class Grid2d(Graph):
+    """2-D grid graph (grid2d.py:9-89); ``grid2d_weights`` builds W and the coordinates."""
+
+    def __init__(self, N1=16, N2=None, diagonal=0.0, **kwargs):
+        self.N1, self.N2 = N1, N1 if N2 is None else N2
+        W, coords = grid2d_weights(self.N1, self.N2, diagonal)
+        limits = np.array([-1.0 / self.N2, 1 + 1.0 / self.N2, 1.0 / self.N1, 1 + 1.0 / self.N1])
+        Graph.__init__(self, W, coords=coords, plotting={"limits": limits}, **kwargs)
+
+
+class Grid2dImgPatches(Graph):
+    """Union of the patch graph of an image with the grid graph of its pixels (nngraphs/grid2dimgpatches.py:9-51):
+    W = aggregate(Wp, Wg), the grid's coordinates.  kwargs go to ImgPatches."""
+
+    def __init__(self, img, aggregate=lambda Wp, Wg: Wp + Wg, **kwargs):
+        self.Gg, self.Gp = Grid2d(*np.shape(img)[:2]), ImgPatches(img, **kwargs)
+        Graph.__init__(self, aggregate(self.Gp.W, self.Gg.W), coords=self.Gg.coords, plotting=self.Gg.plotting)
 
 
 class Sensor(NNGraph):

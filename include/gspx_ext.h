@@ -392,6 +392,14 @@ int gspx_host_pipeline_describe(int mode, int64_t host_batch, int64_t host_edge,
  * kernels (sum of device times), out[4] device-to-host DMA, out[5] unpacking (busiest host thread), out[6]
  * batches (0: the call was not pipelined), out[7] signals per batch, out[8] host threads per direction. */
 int gspx_last_host_timing(gspx_ctx* ctx, double out[9]);
+/* Which step kernels the LAST gspx_cheby_filter*, gspx_newton_filter* or gspx_poly_program* call on this context
+ * launched: out[0] launches of the LDS-staged tile kernel (k_step_tile), out[1] launches of the plain step kernels.
+ * Counted on the host where the launches are issued (no kernel takes part, no device traffic); zeroed where the
+ * call's timings are; summed over the column batches of a call, pipelined host-array calls included.  A replayed
+ * recurrence call (option "graph_launch") issues no launch: it reports the counts stored with its recording.  Other
+ * entry points that use a step kernel (gspx_laplacian_apply_dev, gspx_lanczos_lmax, ...) add to the counts without
+ * zeroing them: read the counts right after the call they are about. */
+int gspx_last_step_kinds(gspx_ctx* ctx, int64_t out[2]);
 /* Host clock of the last pipelined gspx_cheby_filter, per batch, in ms since the call began: [6 b + 0] packed,
  * [+1] H2D issued, [+2] kernels begun, [+3] kernels done, [+4] D2H done, [+5] unpacked.  *batches: how many there
  * were; out (capacity doubles) may be NULL. */

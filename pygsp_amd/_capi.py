@@ -141,6 +141,7 @@ SIGNATURES = {
     "gspx_radius_build": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_double, _c.c_double, _c.c_int, _P]),
     "gspx_last_timing": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
     "gspx_last_host_timing": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
+    "gspx_last_step_kinds": (_c.c_int, [_P, _c.POINTER(_c.c_int64)]),
     "gspx_last_host_timeline": (_c.c_int, [_P, _P, _c.c_int, _P]),
     "gspx_host_pipeline_describe": (_c.c_int, [_c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64,
                                                _c.c_int64, _c.c_int, _P, _c.c_int, _P, _P]),

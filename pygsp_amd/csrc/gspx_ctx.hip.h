@@ -76,6 +76,9 @@ struct gspx_ctx {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   std::vector<hipEvent_t> ev_pool;
   double timing[5] = {0, 0, 0, 0, 0};  // what gspx_last_timing reports (run_batches fills it)
+  // step launches of the last filter / Newton / program call (gspx_last_step_kinds): k_step_tile | the plain step
+  // kernels.  Counted on the host where they are issued (launch_step_tile, launch_step), zeroed with `timing`.
+  int64_t step_kinds[2] = {0, 0};
   // hipGraph replay of a repeated identical filter call (launch-bound small graphs)
   bool capturing = false;     // run_batch is being recorded: no copies, syncs or events inside
   // identity of a call = the full tuple of everything the recorded launches depend on, compared
@@ -83,6 +86,7 @@ struct gspx_ctx {
   std::vector<unsigned char> seen_key;   // key of the last eager call (empty: none)
   std::vector<unsigned char> graph_key;  // key the instantiated graph was captured for
   hipGraphExec_t graph_exec = nullptr;
+  int64_t graph_kinds[2] = {0, 0};  // step_kinds of the recorded launches: what a replay reports
 };
 
 static std::atomic<int> g_live_ctx[64];  // live contexts per device (zero-initialised)
@@ -553,5 +557,12 @@ extern "C" int gspx_last_host_timeline(gspx_ctx* ctx, double* out, int capacity,
 extern "C" int gspx_last_timing(gspx_ctx* ctx, double out[5]) {
   if (!ctx || !out) return set_err(GSPX_ERR_INVALID, "null argument");
   for (int i = 0; i < 5; ++i) out[i] = ctx->timing[i];
+  return GSPX_OK;
+}
+
+extern "C" int gspx_last_step_kinds(gspx_ctx* ctx, int64_t out[2]) {
+  if (!ctx || !out) return set_err(GSPX_ERR_INVALID, "null argument");
+  out[0] = ctx->step_kinds[0];
+  out[1] = ctx->step_kinds[1];
   return GSPX_OK;
 }

@@ -225,6 +225,7 @@ static int filter_host_pipelined(gspx_graph* g, int64_t Nsig, int in_planes, int
 
   // this thread: the kernels, batch by batch
   double k_ms = 0, tm[5] = {0, 0, 0, 0, 0};
+  int64_t kinds[2] = {0, 0};
   for (int b = 0; b < nb; ++b) {
     const int s = b % NIN, so = b & 1;
     if (!wait_for([&] { return issued >= b + 1 && shipped >= b - 1; })) break;
@@ -238,6 +239,7 @@ static int filter_host_pipelined(gspx_graph* g, int64_t Nsig, int in_planes, int
     stamp(b, 3);
     k_ms += ctx->timing[0];
     for (int i = 0; i < 5; ++i) tm[i] += ctx->timing[i];
+    for (int i = 0; i < 2; ++i) kinds[i] += ctx->step_kinds[i];
     std::lock_guard<std::mutex> lock(mu);
     computed = b + 1;
     cv.notify_all();
@@ -257,6 +259,7 @@ static int filter_host_pipelined(gspx_graph* g, int64_t Nsig, int in_planes, int
   }
   (void)hipGetLastError();
   for (int i = 0; i < 5; ++i) ctx->timing[i] = tm[i];
+  for (int i = 0; i < 2; ++i) ctx->step_kinds[i] = kinds[i];
   hp.timing[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
   hp.timing[1] = *std::max_element(pack_ms.begin(), pack_ms.end());
   hp.timing[2] = h2d_ms;

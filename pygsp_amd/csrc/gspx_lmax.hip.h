@@ -144,7 +144,7 @@ static int lanczos_t(gspx_graph* g, int max_iter, double tol, double* out, int* 
     a.cur = v[cur];
     a.old = v[cur];
     a.out = v[nxt];
-    launch_step<T>(a, shape, opt, st, nullptr);  // w = L v_j
+    launch_step<T>(g->ctx, a, shape, opt, st, nullptr);  // w = L v_j
     if (j > 0)
       hipLaunchKernelGGL((k_axpby<T>), dim3(nb), dim3(256), 0, st, (T)(-beta_prev), v[prev], T(1),
                          v[nxt], (size_t)N);

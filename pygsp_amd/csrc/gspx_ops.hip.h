@@ -49,7 +49,7 @@ static int spmm_internal(gspx_graph* g, const T* vals, T scale, T beta, const T*
   a.y = y;
   a.ldy = ldy;
   a.perm = g->has_perm ? g->perm.as<int>() : nullptr;
-  launch_step<T>(a, shape, opt, ctx->stream, g->coff.as<unsigned>());
+  launch_step<T>(ctx, a, shape, opt, ctx->stream, g->coff.as<unsigned>());
   return GSPX_OK;
 }
 

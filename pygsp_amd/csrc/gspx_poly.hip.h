@@ -189,8 +189,9 @@ static void launch_lds(const StepArgs<T>& a, const unsigned* coff, const Shape& 
 }
 
 template <typename T>
-static void launch_step(StepArgs<T> a, const Shape& s, const Options& opt, hipStream_t st,
+static void launch_step(gspx_ctx* ctx, StepArgs<T> a, const Shape& s, const Options& opt, hipStream_t st,
                         const unsigned* coff) {
+  ++ctx->step_kinds[1];
   int rpw = (int)opt.rows_per_wave;
   if (rpw <= 0)
     rpw = (s.kernel == 5) ? (sizeof(T) == 4 ? 16 : 8) : (s.kernel == 2 ? 1 : 4);
@@ -458,6 +459,7 @@ static int launch_step_tile(gspx_graph* g, const Options& opt, TileArgs<T> t, un
     nwg = (unsigned)std::max<int64_t>(8, std::min<int64_t>(opt.tile_workgroups, 1 << 20) / 8 * 8);
   nwg = std::min(nwg, 8u * (unsigned)std::max(t.per_xcd, 1));  // (workgroups beyond an XCD's blocks would exit at once)
   t.nt = opt.tile_nt >= 0 ? (int)opt.tile_nt : ((size_t)g->N * ld * sizeof(T) >= ((size_t)192 << 20) ? 5 : 0);
+  ++g->ctx->step_kinds[0];
   hipLaunchKernelGGL(kern, dim3(nwg), dim3(threads), lds, st, t);
   return GSPX_OK;
 }
@@ -717,7 +719,7 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
     a.final = ps.final;
     a.reverse = (opt.alternate_sweep && (k & 1)) ? 1 : 0;
     a.wts = ctx->ws_w.as<T>() + (size_t)(k - 1) * nf * 3;
-    launch_step<T>(a, shape, opt, st, g->coff.as<unsigned>());
+    launch_step<T>(ctx, a, shape, opt, st, g->coff.as<unsigned>());
   }
   if (!cap) HIPCHK(hipEventRecord(ev[2], st));
   if (deferred && sq) {  // the squared column norms in place of the outputs (rows in any order: no perm)
@@ -835,7 +837,7 @@ static int run_synthesis_batch(gspx_graph* g, int nf, int M, const std::vector<d
       a.scale = (k == 0) ? T(0.5) : T(1);
     }
     a.reverse = (opt.alternate_sweep && (k & 1)) ? 1 : 0;
-    launch_step<T>(a, shape, opt, st, g->coff.as<unsigned>());
+    launch_step<T>(ctx, a, shape, opt, st, g->coff.as<unsigned>());
   }
   HIPCHK(hipEventRecord(ev[2], st));
   if (padded) {
@@ -928,7 +930,7 @@ static int run_program_batch(gspx_graph* g, int S, const double* sc, const doubl
     a.flush = last ? 1 : 0;
     a.final = last ? 1 : 0;
     a.reverse = (opt.alternate_sweep && (s & 1)) ? 1 : 0;
-    launch_step<T>(a, shape, opt, st, g->coff.as<unsigned>());
+    launch_step<T>(ctx, a, shape, opt, st, g->coff.as<unsigned>());
   }
   HIPCHK(hipEventRecord(ev[2], st));
   HIPCHK(hipEventRecord(ev[3], st));
@@ -943,6 +945,7 @@ static int filter_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double*
   const Options& opt = ctx->opt;
   const int64_t N = g->N;
   for (int i = 0; i < 5; ++i) ctx->timing[i] = 0;
+  ctx->step_kinds[0] = ctx->step_kinds[1] = 0;
   if (N == 0 || Nsig == 0) return GSPX_OK;
   CHK(ensure_factor<T>(g, lmax));
   std::vector<double> cp;
@@ -995,6 +998,8 @@ static int filter_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double*
       ctx->timing[0] = gms;
       ctx->timing[1] = gms;  // one graph: no per-phase split
       ctx->timing[2] = (double)K;
+      ctx->step_kinds[0] = ctx->graph_kinds[0];  // no launch is issued: the counts of the recording
+      ctx->step_kinds[1] = ctx->graph_kinds[1];
       return GSPX_OK;
     }
     if (!key.empty() && ctx->seen_key == key) {  // second identical call: record it
@@ -1019,6 +1024,8 @@ static int filter_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double*
         (void)hipGraphDestroy(graph);
         if (ie == hipSuccess) {
           ctx->graph_key = key;
+          ctx->graph_kinds[0] = ctx->step_kinds[0];
+          ctx->graph_kinds[1] = ctx->step_kinds[1];
           return filter_dev_t<T>(g, lmax, Nf, M, coeffs, Nsig, x, y, mode);  // replays
         }
         ctx->graph_exec = nullptr;
@@ -1054,6 +1061,7 @@ static int program_dev_t(gspx_graph* g, double lmax, int S, const double* sc, co
   gspx_ctx* ctx = g->ctx;
   replay_reset(ctx);  // (a program rewrites the weights and panels a recorded filter call replays from)
   for (int i = 0; i < 5; ++i) ctx->timing[i] = 0;
+  ctx->step_kinds[0] = ctx->step_kinds[1] = 0;
   if (g->N == 0 || Nsig == 0) return GSPX_OK;
   CHK(ensure_factor<T>(g, lmax));
   int64_t max_ld = 0;
@@ -1269,6 +1277,7 @@ static int sqnorms_dev_t(gspx_graph* g, double lmax, int Nf, int M, const double
   gspx_ctx* ctx = g->ctx;
   const int64_t N = g->N;
   for (int i = 0; i < 5; ++i) ctx->timing[i] = 0;
+  ctx->step_kinds[0] = ctx->step_kinds[1] = 0;
   if (Nsig == 0) return GSPX_OK;
   if (N == 0) {
     std::fill(out, out + (size_t)Nf * Nsig, 0.0);

@@ -57,6 +57,13 @@ class Context:
         return {"total_ms": out[0], "steps_ms": out[1], "step_launches": int(out[2]),
                 "permute_ms": out[3], "combine_ms": out[4]}
 
+    def last_step_kinds(self):
+        """{"tile": launches of the LDS-staged tile kernel, "plain": launches of the plain step kernels} of the last
+        filter, Newton or program call on this context (gspx_last_step_kinds; counted on the host)."""
+        out = (ctypes.c_int64 * 2)()
+        _capi.check(_capi.load().gspx_last_step_kinds(self._h, out))
+        return {"tile": int(out[0]), "plain": int(out[1])}
+
     def last_host_timing(self):
         """Stage times (ms) of the last host-array filter call on this context (gspx_last_host_timing); None
         when that call was not pipelined."""

@@ -107,6 +107,8 @@ def test_argument_errors_need_no_device():
     with pytest.raises(ValueError):
         _capi.check(lib.gspx_last_host_timing(None, d9))
     with pytest.raises(ValueError):
+        _capi.check(lib.gspx_last_step_kinds(None, (ctypes.c_int64 * 2)()))
+    with pytest.raises(ValueError):
         _capi.check(lib.gspx_knn_search_stats(None, _capi.ptr(d4)))
     assert lib.gspx_comm_destroy(None) == 0
 

@@ -1,7 +1,7 @@
 """Randomised differential test of the device path against the oracle: random graphs (ragged, hubs,
 isolated vertices, sensor graphs), Laplacian types, dtypes, internal orders (none / curve / random
 permutation), gather tiles (host- or device-built), engine options, panel widths, orders, filterbanks,
-synthesis, repeated calls (hipGraph replay) and the Newton form.  Needs a real MI355X: `-m gpu`."""
+synthesis, repeated calls (hipGraph replay), the Newton form and the product form.  Needs a real MI355X: `-m gpu`."""
 import numpy as np
 import pytest
 
@@ -18,7 +18,9 @@ def test_fuzz_against_oracle(seed):
     rng = np.random.default_rng(seed)
     ctx = engine.default_context(0)
     try:
-        _run(cases, rng, ctx)
+        # (a second generator decides on the product-form call and draws its input: the first one's stream of cases
+        # is what it was before that call existed)
+        _run(cases, rng, ctx, np.random.default_rng(seed + 1000))
     finally:
         for k, v in (("kernel", 0), ("tile_gather", 1), ("graph_launch", 2), ("xcd_remap", 1), ("alternate_sweep", 1),
                      ("combine", 0), ("synthesis", 0), ("max_batch", 0), ("host_pipeline", 1), ("host_batch", 0),
@@ -26,7 +28,7 @@ def test_fuzz_against_oracle(seed):
             ctx.set_option(k, v)
 
 
-def _run(cases, rng, ctx):
+def _run(cases, rng, ctx, rng2):
     for case in range(cases):
         dtype = [np.float64, np.float32][rng.integers(2)]
         kind = rng.integers(3)
@@ -89,6 +91,15 @@ def _run(cases, rng, ctx):
             err = float(np.max(np.abs(yn - ref)) / (np.max(np.abs(ref)) or 1.0))
             if not err < tol * 100:
                 raise AssertionError(("newton", case, dict(N=N, lap=lap, nsig=nsig, order=order, tiles=tiles, opts=opts, err=err)))
+        if nf == 1 and filters.product_guard(c[0], dtype)[0] and rng2.integers(2):
+            x = rng2.standard_normal((N, nsig))
+            yp, _ = dev.program_filter(filters.cheb_to_product(c[0], dtype), x, lmax)
+            kinds = ctx.last_step_kinds()
+            ref = orc.cheby_op(L, lmax, c[0], x.astype(dtype).astype(np.float64)).reshape(N, nsig)
+            err = float(np.max(np.abs(yp - ref)) / (np.max(np.abs(ref)) or 1.0))
+            if not err < tol * 100:
+                raise AssertionError(("product", case, dict(N=N, lap=lap, dtype=np.dtype(dtype).name, nsig=nsig, order=order,
+                                                            tiles=tiles, opts=opts, step_kinds=kinds, err=err)))
         dev.destroy()
 
 

@@ -17,127 +17,33 @@ run's output is profiles/programs_on_tiles_pytest_gpu.log), float64 / float32:
     C  default options 1.5e-14 / 1.9e-6 (every other setting: the same bits), other builds 1.6e-14 / 1.7e-6
     D  repeats 6.9e-14 / 1.1e-6, without tiles 1.5e-15;  E  filter API 3.3e-14
 The module takes 10 s (331 tests, 0.3 s the slowest)."""
-import contextlib
-
 import numpy as np
 import pytest
-from scipy import sparse
 
-from conftest import rel_err
-from gpu_helpers import DEFAULT_OPTIONS, TOL, ctx, upper_lmax  # noqa: F401 (ctx is a fixture)
+import tile_helpers
+from gpu_helpers import ctx  # noqa: F401 (ctx is a fixture)
 from oracle import cheby_oracle as orc
-from program_helpers import POLYNOMIALS, random_case, shapes_for
+from program_helpers import POLYNOMIALS, shapes_for
 from pygsp_amd import engine, filters, graphs
+from tile_helpers import DTYPES, F64, GRAPHS, OFF_PIECE, ROW_BYTES, columns, expected_kinds, hold, options
 
 pytestmark = pytest.mark.gpu
 
-F64, F32 = np.dtype(np.float64), np.dtype(np.float32)
-DTYPES = [np.float64, np.float32]
-# one row size (bytes) per tile build: 1-lane, 2-lane, 4-lane regrouped to 3 pieces, 4-lane, 8-lane regrouped to 5,
-# 8-lane, 16-lane regrouped to 10, NCOL = 1, NCOL = 2 twice, NCOL = 0 twice: float64 widths 2 ... 96, float32 4 ... 192
-ROW_BYTES = [16, 32, 48, 64, 80, 128, 160, 256, 272, 512, 528, 768]
-OFF_PIECE = {F64: [1, 3, 5, 33], F32: [1, 2, 6, 66]}
-# (sensor4097+hub: the sensor graph with a hub of 300 neighbours added - staged blocks and the hub's plain-gather block
-# in one launch; the random graphs have no locality, so nearly all of their blocks gather from global memory)
-GRAPHS = ["sensor4097", "sensor4097+hub", "hub3001", "hub3001-normalized", "rand577", "rand65"]
-BLOCKS = {"sensor4097": 65, "sensor4097+hub": 65, "hub3001": 47, "hub3001-normalized": 47, "rand577": 10, "rand65": 2}
-MAXW = 192
-OPTIONS = dict(DEFAULT_OPTIONS, tile_regroup=1, tile_lg=0, tile_pad=1, tile_min_row=16)
-
-_CASES, _DEVS, _WORST = {}, {}, {}
-
 
 def case(name):
-    """The graph, its Laplacian, an upper bound of its spectrum, 192 signals whose values are exact in both compute
-    dtypes (one oracle call per polynomial serves every test) and the oracle's result for every polynomial."""
-    if name in _CASES:
-        return _CASES[name]
-    if name.startswith("sensor4097"):
-        W, coords = graphs.sensor_weights(4097, k=8, seed=31)
-        if name.endswith("+hub"):
-            rng = np.random.default_rng(32)
-            to = rng.choice(4096, size=300, replace=False) + 1
-            A = sparse.coo_matrix((rng.uniform(0.1, 1.0, 300), (np.zeros(300, dtype=np.int64), to)), shape=W.shape)
-            W = sparse.csr_matrix(W + A + A.T)
-            W.sum_duplicates()
-            W.sort_indices()
-        lap = "combinatorial"
-        L, lmax = orc.laplacian(W), upper_lmax(W)
-        perm = engine.locality_order(W, coords)
-    else:
-        lap = "normalized" if name.endswith("-normalized") else "combinatorial"
-        W, L, lmax = random_case(name.split("-")[0], lap)
-        perm = engine.locality_order(W, None)
-    n = W.shape[0]
-    x = np.random.default_rng(GRAPHS.index(name)).standard_normal((n, MAXW)).astype(np.float32).astype(np.float64)
-    polys = POLYNOMIALS(lmax)
-    ref = {k: orc.cheby_op(L, lmax, c, x) for k, c in polys.items()}
-    for r in ref.values():
-        r.setflags(write=False)
-    _CASES[name] = dict(W=W, lap=lap, L=L, lmax=lmax, perm=perm, n=n, x=x, polys=polys, ref=ref)
-    return _CASES[name]
+    """tile_helpers.case with the polynomials of the program tests."""
+    return tile_helpers.case(name, POLYNOMIALS)
 
 
 def device_graph(ctx, name, dtype, builder):
-    """The case's graph on the device in its locality order with gather tiles: built in numpy and uploaded
-    (enable_gather_tiles) and built on the device (build_gather_tiles) - the two must agree -, `builder`'s left on."""
-    key = (name, np.dtype(dtype), builder)
-    if key in _DEVS:
-        return _DEVS[key]
-    c = case(name)
-    dev = engine.DeviceGraph.from_w(c["W"], c["lap"], dtype=dtype, perm=c["perm"], ctx=ctx)
-    host = dev.enable_gather_tiles()
-    device = dev.build_gather_tiles()
-    assert host["nb"] == device["nb"] == BLOCKS[name], (host, device)
-    assert host["slow_blocks"] == device["slow_blocks"] and host["lds_bytes"] == device["lds_bytes"], (host, device)
-    if host["slow_blocks"] == 0:  # (the device build sums the gather sets of the staged blocks only)
-        assert abs(host["mean_n1"] - device["mean_n1"]) < 1e-9, (host, device)
-    if name.startswith("sensor4097"):
-        assert host["slow_blocks"] * 20 < host["nb"], host
-    if "hub" in name:  # the hub's block takes the plain-gather branch inside the tile kernel
-        assert host["slow_blocks"] >= 1, host
-    if builder == "host":
-        dev.enable_gather_tiles()
-    print("{} {} tiles: {}".format(name, np.dtype(dtype).name, host))
-    _DEVS[key] = dev
-    return dev
+    return tile_helpers.device_graph(ctx, name, dtype, builder, POLYNOMIALS)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def report():
     """After the module: the device's worst deviation per test and dtype; the device graphs go."""
     yield
-    for (test, dt), (err, where) in sorted(_WORST.items()):
-        print("\nworst {:<34s} {:<8s} {:.2e} of max |ref| at {}".format(test, dt, err, where), end="")
-    print()
-    while _DEVS:
-        _DEVS.popitem()[1].destroy()
-    _CASES.clear()
-
-
-@contextlib.contextmanager
-def options(ctx, **kw):
-    try:
-        for k, v in kw.items():
-            ctx.set_option(k, v)
-        yield
-    finally:
-        for k in kw:
-            ctx.set_option(k, OPTIONS[k])
-
-
-def columns(c, w):
-    return np.ascontiguousarray(c["x"][:, :w])
-
-
-def hold(test, dtype, y, ref, where):
-    """y against the oracle, every column, at the bar; keeps the worst figure for the report."""
-    assert y.shape == ref.shape and np.all(np.isfinite(y)), where
-    err = rel_err(y.astype(np.float64), ref)
-    key = (test, np.dtype(dtype).name)
-    if err >= _WORST.get(key, (-1.0, None))[0]:
-        _WORST[key] = (err, where)
-    assert err < TOL[np.dtype(dtype)] * 10, (where, err)
+    tile_helpers.finish()
 
 
 def product_program(name, c, dtype):
@@ -189,22 +95,6 @@ def test_off_piece_widths_run_on_the_plain_kernels(ctx, graph, dtype):
             y, _ = dev.program_filter(prog, columns(c, w), c["lmax"])
             assert ctx.last_step_kinds() == {"tile": 0, "plain": prog.shape[0]}, (graph, w, name)
             hold("B off-piece widths", dtype, y, c["ref"][name][:, :w], (graph, w, name))
-
-
-def expected_kinds(nsig, elt, max_batch, S, tile_min_row=16):
-    """The rule of gspx_poly.hip.h restated: column batches of max_batch signals (a multiple of 4 when there are
-    several and max_batch >= 4); a batch of ld columns starting at column c0 takes the tile kernel iff its rows and the
-    rows of y are whole 16-byte pieces, its rows have at least tile_min_row bytes and y + c0 is 16-byte aligned (the
-    buffers themselves are)."""
-    width = nsig if max_batch <= 0 else min(max_batch, nsig)
-    if width < nsig and width >= 4:
-        width &= ~3
-    kinds = {"tile": 0, "plain": 0}
-    for c0 in range(0, nsig, width):
-        ld = min(width, nsig - c0)
-        tile = ((ld * elt) % 16 == 0 and (nsig * elt) % 16 == 0 and ld * elt >= tile_min_row and (c0 * elt) % 16 == 0)
-        kinds["tile" if tile else "plain"] += S
-    return kinds
 
 
 def test_the_restated_rule():

@@ -237,6 +237,22 @@ int gspx_sbm_build(gspx_ctx* ctx, int64_t N, int k, const int32_t* order, const 
 int gspx_sbm_build_ex(gspx_ctx* ctx, int64_t N, int k, const int32_t* order, const int64_t* bounds,
                       const double* M, uint64_t seed, int flags, gspx_knn** out);
 
+/* The line graph of an undirected graph without self-loops (pygsp/graphs/linegraph.py), built on the device from the
+ * edge tables of grad / div.  g: a graph created from W, either compute dtype and lap_type - only the pattern of its
+ * Laplacian is read; a graph created from L is refused with the differential operator's error, a graph that carries
+ * a caller's edge list (a directed graph, self-loops) with GSPX_ERR_INVALID - the host layer forms those.
+ * Line-graph vertex e is edge e of Graph.get_edge_list: the upper triangle of W, row-major, caller's vertex order.
+ * size: the vertex count (= n_edges) and the stored entries of the adjacency, sum over edges (s, t) of
+ * deg(s) + deg(t) - 2, from a 64-bit reduction - it may exceed 32 bits, and nothing is allocated for it.
+ * build: the adjacency as a handle read with the k-NN handle's info / download calls, handed to the set-up from a
+ * handle and freed with its destroy call: canonical CSR with sorted columns, every value exactly 1.0, no diagonal,
+ * no stored zero (its neighbour / distance members stay empty).  GSPX_ERR_INVALID with both counts in the message,
+ * before any allocation of the output, when either exceeds 2^31 - 1.  A graph without edges gives an empty handle
+ * (N = 0, nnz = 0).  kernel_ms (may be NULL): length pass, scan and fill on the context's stream.  The result is
+ * fully determined by the input: identical calls give identical bits. */
+int gspx_linegraph_size(gspx_graph* g, int64_t* n_vertices, int64_t* nnz);
+int gspx_linegraph_build(gspx_graph* g, gspx_knn** out, double* kernel_ms);
+
 /* Space-filling-curve keys of N points (coords: N x d doubles on the HOST, d >= 2; the first two /
  * three axes are used): curve 0 = Morton, 1 = Hilbert (2-D).  The engine's internal vertex order
  * for graphs with coordinates is the stable argsort of these keys (pygsp_amd.engine.locality_order). */

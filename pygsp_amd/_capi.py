@@ -138,6 +138,9 @@ SIGNATURES = {
     "gspx_layout_splits": (_c.c_int, [_P, _c.POINTER(_c.c_int64)]),
     "gspx_sbm_build": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_uint64, _P]),
     "gspx_sbm_build_ex": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _P, _c.c_uint64, _c.c_int, _P]),
+    # line graphs (graphs.LineGraph, engine.line_graph)
+    "gspx_linegraph_size": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    "gspx_linegraph_build": (_c.c_int, [_P, _c.POINTER(_P), _c.POINTER(_c.c_double)]),
     "gspx_radius_build": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_double, _c.c_double, _c.c_int, _P]),
     "gspx_last_timing": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
     "gspx_last_host_timing": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),

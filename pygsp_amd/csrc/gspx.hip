@@ -80,6 +80,7 @@ extern "C" const char* gspx_version(void) { return "gspx 0.1 (gfx950)"; }
                                   // gspx_reduce.hip.h and gspx_ops_kernels.hip.h                     (on poly)
 #include "gspx_knn.hip.h"         // k-NN / radius / SBM graphs on the device; brings gspx_knn_bf.hip.h (on graph)
 #include "gspx_setup.hip.h"       // graph set-up in one call, curve orders                           (on graph, knn)
+#include "gspx_linegraph.hip.h"   // line graphs from the edge tables of grad / div                   (on ops, knn)
 #include "gspx_components.hip.h"  // connected components                                             (on graph)
 #include "gspx_spectral.hip.h"    // panel Gram / combine / residual norms of the Fourier basis       (on ops)
 #include "gspx_eig.hip.h"         // the full Fourier basis: dense symmetric eigensolver by block Jacobi   (on spectral)

@@ -153,6 +153,7 @@ struct gspx_graph {
   // differential operator (built on first use; gspx_ops.hip.h)
   int lap_type = GSPX_LAP_COMBINATORIAL;
   bool edges_built = false;
+  bool edges_custom = false;  // the edge list is a caller's (gspx_graph_set_edge_list), not the Laplacian's own
   int64_t n_edges = 0;
   DevMem e_off, e_toff, e_src, e_dst, e_tedge, e_cs, e_ct, e_w;
 };

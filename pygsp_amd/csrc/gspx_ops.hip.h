@@ -464,6 +464,7 @@ static int set_edge_list_t(gspx_graph* g, int64_t E, const int32_t* src, const i
   // has NO edge list, so that a failure half-way leaves grad / div to rebuild the default one instead of running on
   // freed or mismatched buffers
   g->edges_built = false;
+  g->edges_custom = false;
   g->n_edges = 0;
   CHK(g->e_off.alloc(((size_t)N + 1) * sizeof(int)));
   CHK(g->e_toff.alloc(((size_t)N + 1) * sizeof(int)));
@@ -488,6 +489,7 @@ static int set_edge_list_t(gspx_graph* g, int64_t E, const int32_t* src, const i
   HIPCHK(hipStreamSynchronize(st));  // the host vectors above are read by the copies until here
   g->n_edges = E;
   g->edges_built = true;
+  g->edges_custom = true;
   return GSPX_OK;
 }
 

@@ -1518,6 +1518,26 @@ def sbm_graph(z, M, seed=None, ctx=None, keep_on_device=False, directed=False, s
     return W, ms
 
 
+def line_graph_size(dev):
+    """(vertices, stored entries) of the line graph of the DeviceGraph `dev` (gspx_linegraph_size): its edge count
+    and a 64-bit sum of the row lengths, which may exceed what the builder's 32-bit indices hold."""
+    n, nnz = ctypes.c_int64(0), ctypes.c_int64(0)
+    _capi.check(_capi.load().gspx_linegraph_size(dev._h, ctypes.byref(n), ctypes.byref(nnz)))
+    return n.value, nnz.value
+
+
+def line_graph(dev, keep_on_device=True):
+    """Adjacency of the line graph of the DeviceGraph `dev` (gspx_linegraph_build; linegraph.py:34-46): one vertex per
+    edge of Graph.get_edge_list, two of them joined when the edges share an endpoint, unit weights.  `dev` is an
+    undirected graph without self-loops that was built from W.  Returns (W, info): W a DeviceAdjacency (or the
+    scipy CSR matrix, float64, with keep_on_device=False), info = {"kernel_ms", "build_ms"}.  ValueError when the
+    vertex or entry count exceeds 32-bit indices - nothing is allocated by then."""
+    h, kernel_ms = ctypes.c_void_p(), ctypes.c_double(0)
+    dev.ctx.call(_capi.load().gspx_linegraph_build, dev._h, ctypes.byref(h), ctypes.byref(kernel_ms))
+    W, _, build_ms = _adjacency(h, dev.ctx, dev.n_edges(), keep_on_device)
+    return W, {"kernel_ms": kernel_ms.value, "build_ms": build_ms}
+
+
 def plan_describe(coeffs, ctx=None):
     """The engine's step schedule for these coefficients (host-only; for schedule tests)."""
     c = _coeff_matrix(coeffs)

@@ -76,7 +76,7 @@ class Graph:
         self._perm, self._perm_done = None, False
         self._dev = {}     # compute dtype -> engine.DeviceGraph
         self._adj_host = self._adj_dev = None  # W: the scipy matrix / a builder's result still on the device
-        self._L = self._dw = None
+        self._L = self._dw = self._A = self._d = None
         self._flags = {}   # lazily computed facts about W ("directed")
         self._forget_spectrum()
         if lap_type not in ("combinatorial", "normalized"):
@@ -202,6 +202,7 @@ class Graph:
     @_adjacency.setter
     def _adjacency(self, W):
         self._adj_host, self._adj_dev = W, None
+        self._A = self._d = None  # (the unweighted view follows W)
 
     def _forget_spectrum(self):
         """Everything derived from the Laplacian's spectrum (graph.py:602-609)."""
@@ -213,6 +214,24 @@ class Graph:
     @property
     def W(self):
         return self._adjacency
+
+    @property
+    def A(self):
+        """graph.py:717-727: the binary adjacency matrix ``W > 0`` (host; computed once)."""
+        if self._A is None:
+            self._A = self.W > 0
+        return self._A
+
+    @property
+    def d(self):
+        """graph.py:729-781: the number of neighbours of every vertex - the stored entries per row of W, or the mean
+        of in- and out-degree for a directed graph (host; computed once)."""
+        if self._d is None:
+            if not self.is_directed():
+                self._d = self.W.getnnz(axis=1)
+            else:
+                self._d = (self.W.getnnz(axis=0) + self.W.getnnz(axis=1)) / 2
+        return self._d
 
     def is_directed(self):
         """True when W differs from its transpose (graph.py:357-405); computed once."""
@@ -895,6 +914,69 @@ class Sensor(NNGraph):
         self.distributed, self.seed = distributed, seed
         NNGraph.__init__(self, Xin=_sensor_points(N, seed, distributed), k=k, rescale=False, center=False,
                          plotting={"limits": np.array([0, 1, 0, 1])}, **kwargs)
+
+
+def line_graph_host(sources, targets, n_vertices):
+    """Adjacency of the line graph from an edge list, on the host with scipy - what linegraph.py:41-46 computes through
+    the differential operator.  An edges x vertices indicator marks the endpoints of every edge; a self-loop marks
+    none, because its column of D is empty (its two values cancel, difference.py:166).  Two edges are joined when
+    their rows meet - the product is a boolean one, so an antiparallel pair of a directed graph, which shares both
+    endpoints, still gets the value 1 - and the identity is subtracted: 0 on the diagonal of an ordinary edge
+    (dropped), -1 on that of a self-loop.  Returns (adjacency csr int64, indicator csr float64)."""
+    sources, targets = np.asarray(sources), np.asarray(targets)
+    n_edges = sources.size
+    ordinary = np.flatnonzero(sources != targets)
+    touches = sparse.csr_matrix((np.ones(2 * ordinary.size), (np.concatenate([ordinary, ordinary]),
+                                 np.concatenate([sources[ordinary], targets[ordinary]]))), shape=(n_edges, n_vertices))
+    meet = sparse.csr_matrix(touches.dot(touches.T))
+    meet.data = np.ones(meet.nnz, dtype=np.int64)
+    adjacency = sparse.csr_matrix(meet - sparse.identity(n_edges, dtype=np.int64, format="csr"))
+    adjacency.eliminate_zeros()
+    adjacency.sort_indices()
+    return adjacency, touches
+
+
+class LineGraph(Graph):
+    """Line graph of a graph (linegraph.py:11-53): one vertex per edge of ``graph.get_edge_list()``, two of them joined
+    when the edges share an endpoint; unit weights (a weighted graph is read as unweighted, with the reference's
+    warning), coordinates at the edges' midpoints when the graph has coordinates, the graph's plotting settings.
+    kwargs go to Graph (lap_type and the engine's keyword-only arguments).
+
+    An undirected graph without self-loops or negative weights is served on the device: the adjacency is built from
+    the edge tables of its device graph (engine.line_graph) and stays there - checks, vertex order, Laplacian and
+    gather tiles run on it where it lies, ``LG.W`` is downloaded when somebody reads it.  Every other graph takes the
+    host route (``line_graph_host``), which keeps the reference's results for directed graphs and self-loops."""
+
+    def __init__(self, graph, **kwargs):
+        if graph.is_weighted():
+            _logger.warning("Your graph is weighted, and is considered "
+                            "unweighted to build a binary line graph.")
+        points = getattr(graph, "coords", None)
+        self.line_graph_info = None
+        if self._on_device(graph):
+            adjacency, self.line_graph_info = engine.line_graph(graph.device_graph())
+            coords = None
+            if points is not None:
+                sources, targets, _ = graph.device_graph().edge_list()
+                coords = (points[sources] + points[targets]) / 2
+        else:
+            sources, targets, _ = graph.get_edge_list()
+            adjacency, touches = line_graph_host(sources, targets, graph.n_vertices)
+            coords = None if points is None else touches.dot(points) / 2
+        Graph.__init__(self, adjacency, coords=coords, plotting=graph.plotting, **kwargs)
+
+    @staticmethod
+    def _on_device(graph):
+        """The device builder reads the pattern of the device Laplacian as the graph's simple undirected edge set:
+        that holds for an undirected graph with edges, without self-loops and without negative weights (whose
+        normalized Laplacian may have lost rows, graph.py:621-628)."""
+        if graph.n_edges == 0 or graph.is_directed():
+            return False
+        report = getattr(graph, "setup_report", None)
+        if report is not None and graph._adj_dev is not None:  # (W still lies on the device: the set-up's own counts)
+            return not (report["self_loops"] or report["negative"])
+        W = graph.W
+        return not (W.diagonal().any() or (W.nnz and W.data.min() < 0))
 
 
 def _sample_pairs_within(rng, n, p):

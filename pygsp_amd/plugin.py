@@ -398,10 +398,43 @@ def _fruchterman_reingold_on_device(self, dim=2, k=None, pos=None, fixed=[], ite
     return out
 
 
+def _linegraph_on_device(graph):
+    """Whether the device builds the line graph of a reference graph: an undirected graph with edges, a sparse W
+    without self-loops or negative weights, and a device graph that is built from W (laplacian='device')."""
+    if _config["laplacian"] != "device" or not sparse.issparse(graph.W) or graph.n_edges == 0 or graph.is_directed():
+        return False
+    return not (graph.W.diagonal().any() or graph.W.data.min() < 0)
+
+
+def _linegraph_init(linegraph_cls):
+    """What install(linegraph=True) puts in place of ``LineGraph.__init__`` (linegraph.py:34-53): the adjacency of an
+    undirected graph without self-loops comes from the device (engine.line_graph on device_graph_for(graph), in
+    ``get_edge_list`` order) instead of the host's sparse product B^T B - I; it is downloaded and handed to the
+    package's own ``Graph.__init__`` with the reference's arguments - integer unit weights, midpoint coordinates,
+    the graph's plotting settings.  Directed graphs and graphs with self-loops run the package's own code."""
+    def __init__(self, graph, **kwargs):
+        if not _linegraph_on_device(graph):
+            return _saved_on(linegraph_cls)["__init__"](self, graph, **kwargs)
+        if graph.is_weighted():
+            import logging
+            logging.getLogger(linegraph_cls.__module__).warning(
+                "Your graph is weighted, and is considered unweighted to build a binary line graph.")
+        dev = device_graph_for(graph)
+        adjacency, _ = engine.line_graph(dev, keep_on_device=False)
+        adjacency = adjacency.astype(int)
+        points, coords = getattr(graph, "coords", None), None
+        if points is not None:  # the midpoint of every edge
+            sources, targets, _ = dev.edge_list()
+            coords = (points[sources] + points[targets]) / 2
+        super(linegraph_cls, self).__init__(adjacency, coords=coords, plotting=graph.plotting, **kwargs)
+
+    return __init__
+
+
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
             lanczos=False, features=False, learning=False, topology=False, optimization=False, harmonic=False,
-            layout=False, exact=False, full_basis=False):
+            layout=False, exact=False, full_basis=False, linegraph=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -441,6 +474,9 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     ``Graph.set_coordinates('spring')``, so that undirected graphs without negative weights are laid out on the device
     in 2 or 3 dimensions (gspx_layout_spring_dev); other graphs keep the reference's code.  The eigenmap kinds follow
     ``fourier=True``.
+    `linegraph` (default False): also replace ``graphs.LineGraph.__init__`` so that the line graph of an undirected
+    graph without self-loops is built on the device (gspx_linegraph_build) and handed to the package's own
+    ``Graph.__init__``; directed graphs and graphs with self-loops keep the reference's code.
     `exact` (default False; needs ``wrap_filter=True``): ``Filter.filter(method='exact')`` and ``Modulation.filter``
     also run on the device, against a device copy of the full ``G.U`` (float64 signals; the basis is the reference's
     own eigh, uploaded once, or the device's under ``full_basis=True``); ``Gabor`` follows through ``Filter.filter``.
@@ -499,6 +535,10 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
         if layout:
             methods.update(zip(_LAYOUT, (_fruchterman_reingold_on_device,)))
         _apply(on["Graph"], methods)
+    if on["LineGraph"] is not None:
+        _apply(on["LineGraph"], {"__init__": _linegraph_init(on["LineGraph"])} if linegraph else {})
+    elif linegraph:
+        raise ValueError("linegraph=True: {} has no graphs.LineGraph".format(pygsp_module.__name__))
     for name, asked, names, replacements in (
             ("features", features, _FEATURES, lambda saved: _feature_functions(pygsp_module, saved)),
             ("learning", learning, _LEARNING, lambda saved: _learning_functions(saved, harmonic)),
@@ -516,6 +556,7 @@ def _targets(pygsp_module):
     return {"approximations": filters.approximations, "filters": filters, "Filter": getattr(filters, "Filter", None),
             "Modulation": getattr(filters, "Modulation", None),
             "Graph": getattr(getattr(pygsp_module, "graphs", None), "Graph", None),
+            "LineGraph": getattr(getattr(pygsp_module, "graphs", None), "LineGraph", None),
             "features": getattr(pygsp_module, "features", None), "learning": getattr(pygsp_module, "learning", None),
             "optimization": getattr(pygsp_module, "optimization", None)}
 

@@ -78,8 +78,9 @@ extern "C" const char* gspx_version(void) { return "gspx 0.1 (gfx950)"; }
 #include "gspx_calib.hip.h"       // bandwidth / gather / mix calibrations, the placement tuner       (on poly)
 #include "gspx_ops.hip.h"         // L x, Dirichlet energy, Tikhonov CG, grad / div, panel primitives; brings
                                   // gspx_reduce.hip.h and gspx_ops_kernels.hip.h                     (on poly)
-#include "gspx_knn.hip.h"         // k-NN / radius / SBM graphs on the device; brings gspx_knn_bf.hip.h (on graph)
-#include "gspx_setup.hip.h"       // graph set-up in one call, curve orders                           (on graph, knn)
+#include "gspx_knn.hip.h"         // k-NN / radius graphs on the device, the gspx_knn handle; brings gspx_knn_bf.hip.h (on graph)
+#include "gspx_sbm.hip.h"         // stochastic block model / Erdos-Renyi sampler                     (on graph, knn)
+#include "gspx_setup.hip.h"       // graph set-up in one call, curve keys and orders                  (on graph, knn)
 #include "gspx_linegraph.hip.h"   // line graphs from the edge tables of grad / div                   (on ops, knn)
 #include "gspx_components.hip.h"  // connected components                                             (on graph)
 #include "gspx_spectral.hip.h"    // panel Gram / combine / residual norms of the Fourier basis       (on ops)

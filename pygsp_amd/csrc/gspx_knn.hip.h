@@ -1,7 +1,9 @@
-// gspx_knn.hip.h - k-nearest-neighbour graph construction on the device.
-// After gspx_graph.hip.h (scan_exclusive).  gfx950 only.
+// gspx_knn.hip.h - neighbour graphs on the device: k nearest neighbours and, at the end of the file, the radius
+// search.  After gspx_graph.hip.h (scan_exclusive).  gfx950 only.  Also defines the handle
+// gspx_knn, which stands for any adjacency a device builder leaves on the device (the block-model sampler and the
+// line-graph builder make such handles too).
 //
-// Replaces, for NNtype='knn' (1 <= d <= 3 by the grid search below; 4 <= d <= 64 by the tiled brute force on the
+// Replaces, for NNtype='knn' (1 <= d <= 3 by the grid search below; 4 <= d <= 4096 by the tiled brute force on the
 // matrix cores of gspx_knn_bf.hip.h; the weights / symmetrisation / CSR stages are shared):
 //   pygsp/graphs/nngraphs/nngraph.py:213-216  kdt = spatial.KDTree(Xout); D, NN = kdt.query(Xout, k + 1)
 //   nngraph.py:218-226                        sigma = mean(D[:, 1:]);  w = exp(-D^2 / sigma)
@@ -122,8 +124,60 @@ __device__ __forceinline__ double knn_sqrt(double x) {
   return s + r / (2.0 * s);
 }
 
-// one thread per query (in cell order: a wave's queries are neighbours in space).  best[] is kept
-// sorted by (distance, index) through a chain of conditional swaps - no dynamic register indexing.
+// The KMAX best candidates of one thread's query, in registers: bd[] sorted ascending, kept so by a chain of
+// conditional swaps.  Every element is indexed with compile-time constants only (fully unrolled loops) - no dynamic
+// register indexing, so nothing goes to scratch memory.  Two forms: keys alone, compared with a strict < (for a bound:
+// the k-th smallest key), and keys with the candidates' indices bi[], ordered by (key, index) - the KD-tree's answer
+// for exactly equal distances.  (Plain arrays of the kernel, not members of a struct: with a struct the register
+// allocator needed 14 to 30 more VGPRs at KMAX = 16 and two builds lost a wave of occupancy, profiles/knn_refactor.md.)
+template <int KMAX> __device__ __forceinline__ void knn_best_init(double (&bd)[KMAX]) {
+#pragma unroll
+  for (int t = 0; t < KMAX; ++t) bd[t] = 1e300;
+}
+template <int KMAX> __device__ __forceinline__ void knn_best_init(double (&bd)[KMAX], int (&bi)[KMAX]) {
+#pragma unroll
+  for (int t = 0; t < KMAX; ++t) {
+    bd[t] = 1e300;
+    bi[t] = 0x7fffffff;
+  }
+}
+// the cheap test against the last entry guards the chain: once the list has settled, few candidates pass it
+template <int KMAX> __device__ __forceinline__ void knn_best_insert(double (&bd)[KMAX], double cd) {
+  if (cd < bd[KMAX - 1]) {
+#pragma unroll
+    for (int t = 0; t < KMAX; ++t) {
+      const bool lt = cd < bd[t];
+      const double td = bd[t];
+      bd[t] = lt ? cd : td;
+      cd = lt ? td : cd;
+    }
+  }
+}
+template <int KMAX>
+__device__ __forceinline__ void knn_best_insert(double (&bd)[KMAX], int (&bi)[KMAX], double cd, int ci) {
+  if (cd < bd[KMAX - 1] || (cd == bd[KMAX - 1] && ci < bi[KMAX - 1])) {
+#pragma unroll
+    for (int t = 0; t < KMAX; ++t) {
+      const bool lt = cd < bd[t] || (cd == bd[t] && ci < bi[t]);
+      const double td = bd[t];
+      const int ti = bi[t];
+      bd[t] = lt ? cd : td;
+      bi[t] = lt ? ci : ti;
+      cd = lt ? td : cd;
+      ci = lt ? ti : ci;
+    }
+  }
+}
+// the k-th entry (1 <= k <= KMAX, a run-time value) by a compile-time scan
+template <int KMAX> __device__ __forceinline__ double knn_best_kth(const double (&bd)[KMAX], int k) {
+  double kth = 1e300;
+#pragma unroll
+  for (int t = 0; t < KMAX; ++t)
+    if (t == k - 1) kth = bd[t];
+  return kth;
+}
+
+// one thread per query (in cell order: a wave's queries are neighbours in space)
 template <int KMAX>
 __global__ __launch_bounds__(128) void k_knn_query(const double* __restrict__ sorted,
                                                    const int* __restrict__ order,
@@ -147,11 +201,7 @@ __global__ __launch_bounds__(128) void k_knn_query(const double* __restrict__ so
   m = fmax(m, 0.0);
   double bd[KMAX];
   int bi[KMAX];
-#pragma unroll
-  for (int t = 0; t < KMAX; ++t) {
-    bd[t] = 1e300;
-    bi[t] = 0x7fffffff;
-  }
+  knn_best_init<KMAX>(bd, bi);
   const int rmax = max(g.n[0], max(g.n[1], g.n[2]));
   const int r2 = g.d >= 2 ? 1 : 0, r3 = g.d >= 3 ? 1 : 0;
   for (int r = 0; r <= rmax; ++r) {
@@ -171,30 +221,13 @@ __global__ __launch_bounds__(128) void k_knn_query(const double* __restrict__ so
           for (int a = start[cid]; a < start[cid + 1]; ++a) {
             const int idx = order[a];
             if (idx == self) continue;
-            const double d2 = knn_key(q, sorted + (size_t)a * g.d, g.d, g.metric);
-            if (d2 < bd[KMAX - 1] || (d2 == bd[KMAX - 1] && idx < bi[KMAX - 1])) {
-              double cd = d2;
-              int ci = idx;
-#pragma unroll
-              for (int t = 0; t < KMAX; ++t) {
-                const bool lt = cd < bd[t] || (cd == bd[t] && ci < bi[t]);
-                const double td = bd[t];
-                const int ti = bi[t];
-                bd[t] = lt ? cd : td;
-                bi[t] = lt ? ci : ti;
-                cd = lt ? td : cd;
-                ci = lt ? ti : ci;
-              }
-            }
+            knn_best_insert<KMAX>(bd, bi, knn_key(q, sorted + (size_t)a * g.d, g.d, g.metric), idx);
           }
         }
       }
     }
     // every point not yet visited lies beyond r whole cells plus the way out of the own cell
-    double kth = 1e300;
-#pragma unroll
-    for (int t = 0; t < KMAX; ++t)
-      if (t == k - 1) kth = bd[t];
+    const double kth = knn_best_kth<KMAX>(bd, k);
     const double lb = (r * g.h_min + m) * (1.0 - 1e-12);
     if (kth < 1e300 && kth <= (g.metric == 0 ? lb * lb : lb)) break;  // every p-norm is >= the max norm
   }
@@ -333,92 +366,7 @@ __global__ void k_knn_row_sort(const int* __restrict__ rowptr, int N, int* __res
   }
 }
 
-// space-filling-curve key of every point (internal vertex order = argsort of the keys):
-// curve 0 = Morton (bit interleave, 31 bits per axis in 2-D, 21 in 3-D), 1 = Hilbert (2-D, 16 bits
-// per axis; the classic xy -> d walk)
-__global__ void k_curve_keys(const double* __restrict__ x, int N, int d, double lo0, double lo1, double lo2,
-                             double inv0, double inv1, double inv2, int curve,
-                             unsigned long long* __restrict__ key) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const double lo[3] = {lo0, lo1, lo2}, inv[3] = {inv0, inv1, inv2};
-  if (curve == 1) {
-    const unsigned long long top = (1ull << 16) - 1;
-    long long q[2];
-    for (int j = 0; j < 2; ++j) {
-      long long v = (long long)((x[(size_t)i * d + j] - lo[j]) * inv[j] * 65536.0);
-      q[j] = v < 0 ? 0 : (v > (long long)top ? (long long)top : v);
-    }
-    long long px = q[0], py = q[1];
-    unsigned long long dd = 0;
-    for (long long s = 1ll << 15; s > 0; s >>= 1) {
-      const long long rx = (px & s) ? 1 : 0, ry = (py & s) ? 1 : 0;
-      dd += (unsigned long long)(s * s) * (unsigned long long)((3 * rx) ^ ry);
-      if (ry == 0) {
-        if (rx == 1) {
-          px = s - 1 - px;
-          py = s - 1 - py;
-        }
-        const long long t = px;
-        px = py;
-        py = t;
-      }
-    }
-    key[i] = dd;
-    return;
-  }
-  const int dm = d >= 3 ? 3 : 2;
-  const int bits = dm == 3 ? 21 : 31;
-  const double scale = (double)((1ull << bits) - 1);
-  unsigned long long code = 0;
-  unsigned long long q[3] = {0, 0, 0};
-  for (int j = 0; j < dm; ++j) {
-    double v = (x[(size_t)i * d + j] - lo[j]) * inv[j] * scale;
-    v = v < 0 ? 0 : (v > scale ? scale : v);
-    q[j] = (unsigned long long)v;
-  }
-  for (int b = 0; b < bits; ++b)
-    for (int j = 0; j < dm; ++j) code |= ((q[j] >> b) & 1ull) << (b * dm + j);
-  key[i] = code;
-}
-
 }  // namespace gspx
-
-// keys of N host points into a device buffer (queued on the context's stream; returns after the launch)
-static int curve_keys_dev(gspx_ctx* ctx, int64_t N, int d, const double* coords, int curve, unsigned long long* keys_dev) {
-  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, inv[3] = {1, 1, 1};
-  const int dm = std::min(d, 3);
-  for (int j = 0; j < dm; ++j) lo[j] = hi[j] = coords[j];
-  for (int64_t i = 0; i < N; ++i)
-    for (int j = 0; j < dm; ++j) {
-      const double v = coords[i * d + j];
-      if (!std::isfinite(v)) return set_err(GSPX_ERR_INVALID, "non-finite coordinate");
-      lo[j] = std::min(lo[j], v);
-      hi[j] = std::max(hi[j], v);
-    }
-  for (int j = 0; j < dm; ++j) inv[j] = hi[j] > lo[j] ? 1.0 / (hi[j] - lo[j]) : 1.0;
-  DevMem x;
-  CHK(x.alloc((size_t)N * d * sizeof(double)));
-  HIPCHK(hipMemcpyAsync(x.p, coords, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_curve_keys, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, x.as<double>(),
-                     (int)N, d, lo[0], lo[1], lo[2], inv[0], inv[1], inv[2], curve, keys_dev);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));  // x goes out of scope
-  return GSPX_OK;
-}
-
-extern "C" int gspx_curve_keys(gspx_ctx* ctx, int64_t N, int d, const double* coords, int curve,
-                               uint64_t* keys) {
-  if (!ctx || !coords || !keys) return set_err(GSPX_ERR_INVALID, "null argument");
-  if (N < 1 || N >= ((int64_t)1 << 31) || d < 2) return set_err(GSPX_ERR_INVALID, "gspx_curve_keys: bad N or d");
-  if (curve != 0 && curve != 1) return set_err(GSPX_ERR_INVALID, "curve: 0 Morton, 1 Hilbert");
-  HIPCHK(hipSetDevice(ctx->device));
-  DevMem k;
-  CHK(k.alloc((size_t)N * sizeof(uint64_t)));
-  CHK(curve_keys_dev(ctx, N, d, coords, curve, (unsigned long long*)k.p));
-  HIPCHK(hipMemcpy(keys, k.p, (size_t)N * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return GSPX_OK;
-}
 
 struct gspx_knn {
   gspx_ctx* ctx = nullptr;
@@ -433,11 +381,89 @@ struct gspx_knn {
 
 #include "gspx_knn_bf.hip.h"
 
-template <int KMAX>
-static void launch_knn_query(const double* sorted, const int* order, const int* start, int N,
-                             const KnnGrid& g, int k, int* nn, double* dist, hipStream_t st) {
-  hipLaunchKernelGGL((k_knn_query<KMAX>), dim3((N + 127) / 128), dim3(128), 0, st, sorted, order, start, N,
-                     g, k, nn, dist);
+// ---- what gspx_knn_build and gspx_radius_build share ------------------------------------------------------------
+// One pass over the host coordinates: every value must be finite (all d columns).  For the grid search (d <= 3;
+// beyond it g.d = 0, no box is taken and the tiled brute force of gspx_knn_bf.hip.h does the search) it leaves the
+// grid's defaults and the bounding box's lower corner in g and the box's extents in ext; the caller's rule for the
+// cell size finishes g.
+static int knn_scan_coords(int64_t N, int d, const double* coords, int metric, KnnGrid& g, double ext[3]) {
+  g = KnnGrid{};
+  g.d = d <= 3 ? d : 0;
+  g.metric = metric;
+  g.h_min = 1e300;
+  double hi[3] = {0, 0, 0};
+  for (int j = 0; j < 3; ++j) {
+    g.lo[j] = 0;
+    g.inv_h[j] = 1;
+    g.n[j] = 1;
+  }
+  for (int j = 0; j < g.d; ++j) g.lo[j] = hi[j] = coords[j];
+  for (int64_t i = 0; i < N; ++i)
+    for (int j = 0; j < d; ++j) {
+      const double v = coords[i * d + j];
+      if (!std::isfinite(v)) return set_err(GSPX_ERR_INVALID, "non-finite coordinate");
+      if (j < g.d) {
+        g.lo[j] = std::min(g.lo[j], v);
+        hi[j] = std::max(hi[j], v);
+      }
+    }
+  for (int j = 0; j < 3; ++j) ext[j] = hi[j] - g.lo[j];
+  return GSPX_OK;
+}
+// most cells per axis, whatever the rule for the cell size asks for
+static int knn_axis_cap(int d) { return d == 1 ? (1 << 21) : (d == 2 ? 2048 : 128); }
+
+// The grid index of a cloud on the device (d <= 3 only: the brute force allocates none of this): the points are
+// counted into the cells of a finished KnnGrid, an exclusive scan of the counts gives every cell its range (start),
+// the points are scattered into cell order and every cell's members sorted by index (order), and the coordinates
+// gathered in that order (sorted).  The query kernels read those three.  alloc() and build() are two calls because a
+// builder allocates all it needs for the search first, in one fixed order, and only then queues the upload of the
+// cloud (profiles/knn_refactor.md: the 1M-point build in one dimension was timed with the index allocated after it).
+struct KnnGridIndex {
+  DevMem sorted, order, start;  // N x d doubles, N, ncells + 1
+  DevMem cell, count, cursor;   // what the chain needs on the way
+  int ncells = 0;
+  size_t cell_bytes = 0;
+  int alloc(int N, const KnnGrid& g) {
+    ncells = g.n[0] * g.n[1] * g.n[2];  // (at most 2^22: knn_axis_cap)
+    cell_bytes = ((size_t)ncells + 1) * sizeof(int);
+    CHK(sorted.alloc((size_t)N * g.d * sizeof(double)));
+    CHK(cell.alloc((size_t)N * sizeof(int)));
+    CHK(count.alloc(cell_bytes));
+    CHK(start.alloc(cell_bytes));
+    CHK(cursor.alloc(cell_bytes));
+    CHK(order.alloc((size_t)N * sizeof(int)));
+    return GSPX_OK;
+  }
+  int build(gspx_ctx* ctx, const double* x, int N, const KnnGrid& g) {
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemsetAsync(count.p, 0, cell_bytes, st));
+    HIPCHK(hipMemsetAsync(cursor.p, 0, cell_bytes, st));
+    const int nbN = (N + 255) / 256;
+    hipLaunchKernelGGL(k_knn_cell_count, dim3(nbN), dim3(256), 0, st, x, N, g, cell.as<int>(), count.as<int>());
+    CHK(scan_exclusive(ctx, count.as<int>(), start.as<int>(), ncells + 1));
+    hipLaunchKernelGGL(k_knn_scatter, dim3(nbN), dim3(256), 0, st, cell.as<int>(), N, start.as<int>(),
+                       cursor.as<int>(), order.as<int>());
+    hipLaunchKernelGGL(k_knn_cell_sort, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st, start.as<int>(),
+                       ncells, order.as<int>(), x, g.d, sorted.as<double>());
+    return GSPX_OK;
+  }
+};
+
+// mean of n distances on the device (sigma when the caller gives none, nngraph.py:218-219 and 248-262): 1024 blocks'
+// partial sums, added on the host in index order - sigma's last bits depend on both.  Waits for the stream.  (partial:
+// the caller's, so that it is freed with the caller's other buffers, after build_ms is taken.)
+static int knn_mean_dist(gspx_ctx* ctx, const double* dist, size_t n, DevMem& partial, double* mean) {
+  const int nb = 1024;
+  CHK(partial.alloc((size_t)nb * sizeof(double)));
+  hipLaunchKernelGGL(k_knn_sum_partial, dim3(nb), dim3(256), 0, ctx->stream, dist, n, partial.as<double>());
+  std::vector<double> hp(nb);
+  HIPCHK(hipMemcpyAsync(hp.data(), partial.p, nb * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  double s = 0;
+  for (double v : hp) s += v;
+  *mean = s / (double)n;
+  return GSPX_OK;
 }
 
 extern "C" int gspx_knn_build(gspx_ctx* ctx, int64_t N, int d, const double* coords, int k,
@@ -456,160 +482,91 @@ extern "C" int gspx_knn_build(gspx_ctx* ctx, int64_t N, int d, const double* coo
                    k, (long long)N);
   if (!coords) return set_err(GSPX_ERR_INVALID, "null coordinates");
   if (!(sigma >= 0) || !std::isfinite(sigma)) return set_err(GSPX_ERR_INVALID, "sigma must be >= 0 (0: mean distance)");
-  KnnGrid g{};
-  const bool grid_search = d <= 3;  // beyond three dimensions: tiled brute force on the matrix cores (gspx_knn_bf.hip.h)
-  const int dg = grid_search ? d : 0;
-  g.d = dg;
-  g.metric = metric;
-  double hi[3] = {0, 0, 0};
-  for (int j = 0; j < 3; ++j) {
-    g.lo[j] = 0;
-    g.inv_h[j] = 1;
-    g.n[j] = 1;
-  }
-  for (int j = 0; j < dg; ++j) {
-    g.lo[j] = coords[j];
-    hi[j] = coords[j];
-  }
-  for (int64_t i = 0; i < N; ++i)
-    for (int j = 0; j < d; ++j) {
-      const double v = coords[i * d + j];
-      if (!std::isfinite(v)) return set_err(GSPX_ERR_INVALID, "non-finite coordinate");
-      if (j < dg) {
-        g.lo[j] = std::min(g.lo[j], v);
-        hi[j] = std::max(hi[j], v);
-      }
-    }
+  KnnGrid g;
+  double ext[3];
+  CHK(knn_scan_coords(N, d, coords, metric, g, ext));
+  const bool grid_search = g.d > 0;
   // about 2.5 points per cell over the bounding box; degenerate extents get one cell
-  const int cap = d == 1 ? (1 << 21) : (d == 2 ? 2048 : 128);
-  const int per_dim = std::max(1, std::min(cap, (int)std::floor(std::pow((double)N / 2.5, 1.0 / std::max(dg, 1)))));
-  g.h_min = 1e300;
-  int64_t ncells = 1;
-  for (int j = 0; j < dg; ++j) {
-    const double ext = hi[j] - g.lo[j];
-    g.n[j] = ext > 0 ? per_dim : 1;
-    const double h = ext > 0 ? ext / g.n[j] : 1.0;
+  const int per_dim =
+      std::max(1, std::min(knn_axis_cap(d), (int)std::floor(std::pow((double)N / 2.5, 1.0 / std::max(g.d, 1)))));
+  for (int j = 0; j < g.d; ++j) {
+    g.n[j] = ext[j] > 0 ? per_dim : 1;
+    const double h = ext[j] > 0 ? ext[j] / g.n[j] : 1.0;
     g.inv_h[j] = 1.0 / h;
-    if (ext > 0) g.h_min = std::min(g.h_min, h);
-    ncells *= g.n[j];
+    if (ext[j] > 0) g.h_min = std::min(g.h_min, h);
   }
   if (g.h_min == 1e300) g.h_min = 1.0;  // all points coincide
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   auto t0 = std::chrono::steady_clock::now();
-  gspx_knn* h = new gspx_knn();
+  std::unique_ptr<gspx_knn> h(new gspx_knn());
   h->ctx = ctx;
   h->N = N;
   h->d = d;
   h->k = k;
-  auto fail = [&](int rc) {
-    delete h;
-    return rc;
-  };
-#define KCHK(x)                      \
-  do {                               \
-    int rc__ = (x);                  \
-    if (rc__ != GSPX_OK) return fail(rc__); \
-  } while (0)
-#define KHIP(x)                                                                            \
-  do {                                                                                     \
-    hipError_t e__ = (x);                                                                  \
-    if (e__ != hipSuccess) return fail(set_err(GSPX_ERR_HIP, "%s: %s", #x, hipGetErrorString(e__))); \
-  } while (0)
   const int n = (int)N;
   const size_t nk = (size_t)N * k;
-  DevMem x, sorted, cell, count, start, cursor, order, w, mutual, len, partial;
-  KCHK(x.alloc((size_t)N * d * sizeof(double)));
-  KCHK(sorted.alloc((size_t)N * d * sizeof(double)));
-  KCHK(cell.alloc((size_t)N * sizeof(int)));
-  KCHK(count.alloc(((size_t)ncells + 1) * sizeof(int)));
-  KCHK(start.alloc(((size_t)ncells + 1) * sizeof(int)));
-  KCHK(cursor.alloc(((size_t)std::max<int64_t>(ncells, N) + 1) * sizeof(int)));
-  KCHK(order.alloc((size_t)N * sizeof(int)));
-  KCHK(h->nn.alloc(nk * sizeof(int)));
-  KCHK(h->dist.alloc(nk * sizeof(double)));
-  KHIP(hipMemcpyAsync(x.p, coords, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, st));
-  KHIP(hipMemsetAsync(count.p, 0, ((size_t)ncells + 1) * sizeof(int), st));
-  KHIP(hipMemsetAsync(cursor.p, 0, ((size_t)std::max<int64_t>(ncells, N) + 1) * sizeof(int), st));
-  const int nbN = (n + 255) / 256;
+  DevMem x, w, mutual, len, partial;
+  KnnGridIndex index;
+  CHK(x.alloc((size_t)N * d * sizeof(double)));
+  if (grid_search) CHK(index.alloc(n, g));
+  CHK(h->nn.alloc(nk * sizeof(int)));
+  CHK(h->dist.alloc(nk * sizeof(double)));
+  HIPCHK(hipMemcpyAsync(x.p, coords, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, st));
   if (!grid_search) {
-    KHIP(hipStreamSynchronize(st));
-    KCHK(knn_bruteforce(ctx, x.as<double>(), n, d, k, metric, h->nn.as<int>(), h->dist.as<double>(), h->search_stats));
+    HIPCHK(hipStreamSynchronize(st));
+    CHK(knn_bruteforce(ctx, x.as<double>(), n, d, k, metric, h->nn.as<int>(), h->dist.as<double>(), h->search_stats));
   } else {
-  hipLaunchKernelGGL(k_knn_cell_count, dim3(nbN), dim3(256), 0, st, x.as<double>(), n, g, cell.as<int>(),
-                     count.as<int>());
-  KCHK(scan_exclusive(ctx, count.as<int>(), start.as<int>(), (int)ncells + 1));
-  hipLaunchKernelGGL(k_knn_scatter, dim3(nbN), dim3(256), 0, st, cell.as<int>(), n, start.as<int>(),
-                     cursor.as<int>(), order.as<int>());
-  hipLaunchKernelGGL(k_knn_cell_sort, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st,
-                     start.as<int>(), (int)ncells, order.as<int>(), x.as<double>(), d, sorted.as<double>());
-  if (k <= 8)
-    launch_knn_query<8>(sorted.as<double>(), order.as<int>(), start.as<int>(), n, g, k, h->nn.as<int>(),
-                        h->dist.as<double>(), st);
-  else if (k <= 16)
-    launch_knn_query<16>(sorted.as<double>(), order.as<int>(), start.as<int>(), n, g, k, h->nn.as<int>(),
-                         h->dist.as<double>(), st);
-  else if (k <= 32)
-    launch_knn_query<32>(sorted.as<double>(), order.as<int>(), start.as<int>(), n, g, k, h->nn.as<int>(),
-                         h->dist.as<double>(), st);
-  else
-    launch_knn_query<64>(sorted.as<double>(), order.as<int>(), start.as<int>(), n, g, k, h->nn.as<int>(),
-                         h->dist.as<double>(), st);
+    CHK(index.build(ctx, x.as<double>(), n, g));
+    const auto query =
+        k <= 8 ? k_knn_query<8> : (k <= 16 ? k_knn_query<16> : (k <= 32 ? k_knn_query<32> : k_knn_query<64>));
+    hipLaunchKernelGGL(query, dim3((n + 127) / 128), dim3(128), 0, st, index.sorted.as<double>(), index.order.as<int>(),
+                       index.start.as<int>(), n, g, k, h->nn.as<int>(), h->dist.as<double>());
   }
-  KHIP(hipGetLastError());
-  // sigma = mean neighbour distance (nngraph.py:218-219) unless given
-  if (sigma == 0.0) {
-    const int nb = 1024;
-    KCHK(partial.alloc((size_t)nb * sizeof(double)));
-    hipLaunchKernelGGL(k_knn_sum_partial, dim3(nb), dim3(256), 0, st, h->dist.as<double>(), nk,
-                       partial.as<double>());
-    std::vector<double> hp(nb);
-    KHIP(hipMemcpyAsync(hp.data(), partial.p, nb * sizeof(double), hipMemcpyDeviceToHost, st));
-    KHIP(hipStreamSynchronize(st));
-    double s = 0;
-    for (double v : hp) s += v;
-    sigma = s / (double)nk;
-    if (!(sigma > 0)) return fail(set_err(GSPX_ERR_INVALID, "gspx_knn_build: all neighbour distances are zero"));
+  HIPCHK(hipGetLastError());
+  if (sigma == 0.0) {  // the mean neighbour distance (nngraph.py:218-219) unless given
+    CHK(knn_mean_dist(ctx, h->dist.as<double>(), nk, partial, &sigma));
+    if (!(sigma > 0)) return set_err(GSPX_ERR_INVALID, "gspx_knn_build: all neighbour distances are zero");
   }
   h->sigma = sigma;
-  KCHK(w.alloc(nk * sizeof(double)));
-  KCHK(mutual.alloc(nk));
-  KCHK(len.alloc(((size_t)N + 1) * sizeof(int)));
-  KCHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
+  CHK(w.alloc(nk * sizeof(double)));
+  CHK(mutual.alloc(nk));
+  CHK(len.alloc(((size_t)N + 1) * sizeof(int)));
+  CHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
+  const int nbN = (n + 255) / 256;
   const unsigned nbE = (unsigned)((nk + 255) / 256);
-  KHIP(hipMemsetAsync(len.p, 0, ((size_t)N + 1) * sizeof(int), st));
+  HIPCHK(hipMemsetAsync(len.p, 0, ((size_t)N + 1) * sizeof(int), st));
   hipLaunchKernelGGL(k_knn_weights, dim3(nbE), dim3(256), 0, st, h->nn.as<int>(), h->dist.as<double>(), n, k,
                      sigma, symmetrize, w.as<double>(), mutual.as<unsigned char>(), len.as<int>());
-  KCHK(scan_exclusive(ctx, len.as<int>(), h->rowptr.as<int>(), n + 1));
+  CHK(scan_exclusive(ctx, len.as<int>(), h->rowptr.as<int>(), n + 1));
   int nnz = 0;
-  KHIP(hipMemcpyAsync(&nnz, h->rowptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-  KHIP(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpyAsync(&nnz, h->rowptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   h->nnz = nnz;
-  KCHK(h->col.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
-  KCHK(h->val.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
-  KHIP(hipMemsetAsync(cursor.p, 0, ((size_t)N + 1) * sizeof(int), st));
+  CHK(h->col.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
+  CHK(h->val.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
+  // (the row lengths are scanned: cleared again, their N + 1 counters are the rows' fill cursors)
+  HIPCHK(hipMemsetAsync(len.p, 0, ((size_t)N + 1) * sizeof(int), st));
   hipLaunchKernelGGL(k_knn_fill, dim3(nbE), dim3(256), 0, st, h->nn.as<int>(), w.as<double>(),
-                     mutual.as<unsigned char>(), n, k, symmetrize, h->rowptr.as<int>(), cursor.as<int>(), h->col.as<int>(),
+                     mutual.as<unsigned char>(), n, k, symmetrize, h->rowptr.as<int>(), len.as<int>(), h->col.as<int>(),
                      h->val.as<double>());
   {
     DevMem col2, val2;
-    KCHK(col2.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
-    KCHK(val2.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
+    CHK(col2.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
+    CHK(val2.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
     hipLaunchKernelGGL(k_knn_row_rank, dim3(nbN), dim3(256), 0, st, h->rowptr.as<int>(), n, h->col.as<int>(),
                        h->val.as<double>(), col2.as<int>(), val2.as<double>());
     hipLaunchKernelGGL(k_knn_row_rank_long, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, h->rowptr.as<int>(), n,
                        h->col.as<int>(), h->val.as<double>(), col2.as<int>(), val2.as<double>());
-    KHIP(hipGetLastError());
-    KHIP(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
     std::swap(h->col.p, col2.p);      // the sorted arrays become the result; the unsorted ones go with col2 / val2
     std::swap(h->col.bytes, col2.bytes);
     std::swap(h->val.p, val2.p);
     std::swap(h->val.bytes, val2.bytes);
   }
-#undef KCHK
-#undef KHIP
   h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h;
+  *out = h.release();
   return GSPX_OK;
 }
 
@@ -653,249 +610,6 @@ extern "C" int gspx_knn_download_neighbors(gspx_knn* h, int32_t* nn, double* dis
   const size_t nk = (size_t)h->N * h->k;
   if (nn) HIPCHK(hipMemcpy(nn, h->nn.p, nk * sizeof(int), hipMemcpyDeviceToHost));
   if (dist) HIPCHK(hipMemcpy(dist, h->dist.p, nk * sizeof(double), hipMemcpyDeviceToHost));
-  return GSPX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Stochastic block model / Erdos-Renyi sampler on the device (second half).
-// The reference visits all N^2 ordered pairs in a Python loop and keeps pair (r > c) with probability
-// M[z_r][z_c] (pygsp/graphs/stochasticblockmodel.py:125-144; erdosrenyi.py is the one-block case).
-// Same distribution in O(edges): the candidates of every block pair (a, b <= a) - a triangle of
-// n_a (n_a - 1) / 2 pairs for a == b, a rectangle of n_a n_b otherwise - are cut into chunks; one
-// thread walks a chunk by geometric skips (the gap to the next kept pair of independent Bernoulli(p)
-// trials is Geometric(p)), so every pair is kept independently with probability p, chunks are
-// independent, and no duplicate can arise.  Counter-based random numbers (a hash of seed, chunk and
-// draw number): pass 1 counts, pass 2 replays the same stream and emits.  The stream differs from
-// numpy's, so graphs are equal in distribution to the reference's, not bit-equal.
-// ------------------------------------------------------------------------------------------------
-namespace gspx {
-
-struct SbmSeg {       // one block pair
-  long long total;    // candidate pairs
-  long long chunk;    // candidates per chunk
-  long long first;    // global index of its first chunk
-  double log1mp;      // log(1 - p)  (-inf for p == 1)
-  int lo_a, n_a, lo_b, n_b;  // member ranges in `order`
-  int kind;           // candidate index -> (r, c): 0 rectangle n_a x n_b, 1 triangle r > c, 2 triangle r >= c
-                      // (self-loops allowed), 3 square n_a x n_a without its diagonal (directed, no self-loops)
-};
-constexpr int GSPX_SBM_DIRECTED = 1, GSPX_SBM_SELF_LOOPS = 2;
-
-__device__ __forceinline__ unsigned long long sbm_hash(unsigned long long x) {  // splitmix64 finaliser
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-// u in (0, 1]
-__device__ __forceinline__ double sbm_uniform(unsigned long long seed, unsigned long long chunk, unsigned draw) {
-  const unsigned long long h = sbm_hash(sbm_hash(seed ^ (chunk * 0xD1B54A32D192ED03ull)) + draw);
-  return (double)((h >> 11) + 1) * (1.0 / 9007199254740992.0);
-}
-
-// PASS 0: count per chunk; PASS 1: emit (er[], ec[]) at off[chunk] and count degrees
-template <int PASS>
-__global__ void k_sbm_chunks(const SbmSeg* __restrict__ seg, int nseg, long long nchunks,
-                             unsigned long long seed, const int* __restrict__ order,
-                             int* __restrict__ cnt, const int* __restrict__ off, int* __restrict__ er,
-                             int* __restrict__ ec, int* __restrict__ deg, int directed) {
-  const long long ch = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (ch >= nchunks) return;
-  int lo = 0, hi = nseg - 1;  // last segment whose first chunk is <= ch
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (seg[mid].first <= ch) lo = mid; else hi = mid - 1;
-  }
-  const SbmSeg s = seg[lo];
-  const long long base = (ch - s.first) * s.chunk;
-  const long long len = min(s.chunk, s.total - base);
-  long long pos = 0;
-  int n = 0;
-  const int o = PASS ? off[ch] : 0;
-  for (unsigned draw = 0;; ++draw) {
-    const double u = sbm_uniform(seed, (unsigned long long)ch, draw);
-    const double g = floor(log(u) / s.log1mp);  // failures before the next success
-    if (!(g < (double)(len - pos))) break;
-    pos += (long long)g;
-    if (PASS) {
-      const long long idx = base + pos;
-      long long r, c;
-      if (s.kind == 1) {  // idx = r (r - 1) / 2 + c, r > c
-        r = (long long)floor((1.0 + sqrt(1.0 + 8.0 * (double)idx)) * 0.5);
-        if (r * (r - 1) / 2 > idx) --r;
-        if ((r + 1) * r / 2 <= idx) ++r;
-        c = idx - r * (r - 1) / 2;
-      } else if (s.kind == 2) {  // idx = r (r + 1) / 2 + c, r >= c
-        r = (long long)floor((sqrt(1.0 + 8.0 * (double)idx) - 1.0) * 0.5);
-        if (r * (r + 1) / 2 > idx) --r;
-        if ((r + 1) * (r + 2) / 2 <= idx) ++r;
-        c = idx - r * (r + 1) / 2;
-      } else if (s.kind == 3) {  // row r holds its n_a - 1 off-diagonal columns
-        r = idx / (s.n_a - 1);
-        c = idx - r * (s.n_a - 1);
-        if (c >= r) ++c;
-      } else {
-        r = idx / s.n_b;
-        c = idx - r * s.n_b;
-      }
-      const int vr = order[s.lo_a + (int)r], vc = order[s.lo_b + (int)c];
-      er[o + n] = vr;
-      ec[o + n] = vc;
-      atomicAdd(&deg[vr], 1);
-      if (!directed && vr != vc) atomicAdd(&deg[vc], 1);  // (an undirected self-loop is one stored entry)
-    }
-    ++n;
-    ++pos;
-    if (pos >= len) break;
-  }
-  if (!PASS) cnt[ch] = n;
-}
-__global__ void k_sbm_fill(const int* __restrict__ er, const int* __restrict__ ec, long long m,
-                           const int* __restrict__ rowptr, int* __restrict__ cursor, int* __restrict__ col,
-                           double* __restrict__ val, int directed) {
-  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= m) return;
-  const int r = er[e], c = ec[e];
-  const int a = rowptr[r] + atomicAdd(&cursor[r], 1);
-  col[a] = c;
-  val[a] = 1.0;
-  if (directed || r == c) return;  // W[r, c] alone / the one entry of a self-loop
-  const int b = rowptr[c] + atomicAdd(&cursor[c], 1);
-  col[b] = r;
-  val[b] = 1.0;
-}
-
-}  // namespace gspx
-
-extern "C" int gspx_sbm_build(gspx_ctx* ctx, int64_t N, int k, const int32_t* order, const int64_t* bounds,
-                              const double* M, uint64_t seed, gspx_knn** out) {
-  return gspx_sbm_build_ex(ctx, N, k, order, bounds, M, seed, 0, out);
-}
-
-extern "C" int gspx_sbm_build_ex(gspx_ctx* ctx, int64_t N, int k, const int32_t* order, const int64_t* bounds,
-                                 const double* M, uint64_t seed, int flags, gspx_knn** out) {
-  if (!ctx || !out) return set_err(GSPX_ERR_INVALID, "null ctx or output");
-  *out = nullptr;
-  if (N < 1 || N >= ((int64_t)1 << 31) - 1 || k < 1 || k > 4096 || !order || !bounds || !M ||
-      (flags & ~(GSPX_SBM_DIRECTED | GSPX_SBM_SELF_LOOPS)))
-    return set_err(GSPX_ERR_INVALID, "gspx_sbm_build: bad argument");
-  const bool directed = (flags & GSPX_SBM_DIRECTED) != 0, loops = (flags & GSPX_SBM_SELF_LOOPS) != 0;
-  if (bounds[0] != 0 || bounds[k] != N) return set_err(GSPX_ERR_INVALID, "gspx_sbm_build: bounds must span [0, N]");
-  for (int a = 0; a < k; ++a) {
-    if (bounds[a + 1] < bounds[a]) return set_err(GSPX_ERR_INVALID, "gspx_sbm_build: bounds must not decrease");
-    for (int b = 0; b < k; ++b) {
-      const double p = M[(size_t)a * k + b];
-      if (!(p >= 0.0 && p <= 1.0)) return set_err(GSPX_ERR_INVALID, "Probabilities should be in [0, 1].");
-      if (!directed && p != M[(size_t)b * k + a])
-        return set_err(GSPX_ERR_INVALID, "gspx_sbm_build: M must be symmetric (undirected graphs)");
-    }
-  }
-  std::vector<SbmSeg> segs;
-  long long nchunks = 0;
-  // undirected: the block pairs (a, b <= a), the reference's r >= c half (stochasticblockmodel.py:129, mirrored
-  // by utils.symmetrize 'tril'); directed: all k^2 ordered block pairs, entry W[r, c] alone
-  for (int a = 0; a < k; ++a)
-    for (int b = 0; b <= (directed ? k - 1 : a); ++b) {
-      const double p = M[(size_t)a * k + b];
-      const long long na = bounds[a + 1] - bounds[a], nbk = bounds[b + 1] - bounds[b];
-      int kind = 0;
-      long long total = na * nbk;
-      if (a == b && !directed) {
-        kind = loops ? 2 : 1;
-        total = loops ? na * (na + 1) / 2 : na * (na - 1) / 2;
-      } else if (a == b && !loops) {
-        kind = 3;
-        total = na * (na - 1);
-      }
-      if (p <= 0.0 || total <= 0) continue;
-      SbmSeg s{};
-      s.total = total;
-      s.kind = kind;
-      long long c = 64;  // about 16 kept pairs per chunk
-      while (c < ((long long)1 << 22) && (double)c * p < 16.0) c <<= 1;
-      s.chunk = c;
-      s.first = nchunks;
-      s.log1mp = std::log1p(-p);
-      s.lo_a = (int)bounds[a];
-      s.n_a = (int)na;
-      s.lo_b = (int)bounds[b];
-      s.n_b = (int)nbk;
-      nchunks += (total + c - 1) / c;
-      segs.push_back(s);
-    }
-  if (nchunks >= ((long long)1 << 31)) return set_err(GSPX_ERR_INVALID, "gspx_sbm_build: too many candidate chunks");
-  HIPCHK(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  auto t0 = std::chrono::steady_clock::now();
-  gspx_knn* h = new gspx_knn();
-  h->ctx = ctx;
-  h->N = N;
-  auto fail = [&](int rc) {
-    delete h;
-    return rc;
-  };
-#define KCHK(x)                      \
-  do {                               \
-    int rc__ = (x);                  \
-    if (rc__ != GSPX_OK) return fail(rc__); \
-  } while (0)
-#define KHIP(x)                                                                            \
-  do {                                                                                     \
-    hipError_t e__ = (x);                                                                  \
-    if (e__ != hipSuccess) return fail(set_err(GSPX_ERR_HIP, "%s: %s", #x, hipGetErrorString(e__))); \
-  } while (0)
-  const int n = (int)N;
-  DevMem dseg, dorder, cnt, off, er, ec, deg, cursor;
-  KCHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
-  KCHK(deg.alloc(((size_t)N + 1) * sizeof(int)));
-  KHIP(hipMemsetAsync(deg.p, 0, ((size_t)N + 1) * sizeof(int), st));
-  long long m = 0;
-  if (nchunks > 0) {
-    KCHK(dseg.alloc(segs.size() * sizeof(SbmSeg)));
-    KCHK(dorder.alloc((size_t)N * sizeof(int)));
-    KCHK(cnt.alloc(((size_t)nchunks + 1) * sizeof(int)));
-    KCHK(off.alloc(((size_t)nchunks + 1) * sizeof(int)));
-    KHIP(hipMemcpyAsync(dseg.p, segs.data(), segs.size() * sizeof(SbmSeg), hipMemcpyHostToDevice, st));
-    KHIP(hipMemcpyAsync(dorder.p, order, (size_t)N * sizeof(int), hipMemcpyHostToDevice, st));
-    KHIP(hipMemsetAsync(cnt.p, 0, ((size_t)nchunks + 1) * sizeof(int), st));
-    const unsigned nbc = (unsigned)((nchunks + 255) / 256);
-    hipLaunchKernelGGL((k_sbm_chunks<0>), dim3(nbc), dim3(256), 0, st, dseg.as<SbmSeg>(), (int)segs.size(), nchunks,
-                       (unsigned long long)seed, dorder.as<int>(), cnt.as<int>(), (const int*)nullptr,
-                       (int*)nullptr, (int*)nullptr, (int*)nullptr, directed ? 1 : 0);
-    KCHK(scan_exclusive(ctx, cnt.as<int>(), off.as<int>(), (int)nchunks + 1));
-    int mi = 0;
-    KHIP(hipMemcpyAsync(&mi, off.as<int>() + nchunks, sizeof(int), hipMemcpyDeviceToHost, st));
-    KHIP(hipStreamSynchronize(st));
-    if (mi < 0 || (long long)mi * 2 >= ((long long)1 << 31))
-      return fail(set_err(GSPX_ERR_INVALID, "gspx_sbm_build: more than 2^30 edges"));
-    m = mi;
-    KCHK(er.alloc((size_t)std::max<long long>(m, 1) * sizeof(int)));
-    KCHK(ec.alloc((size_t)std::max<long long>(m, 1) * sizeof(int)));
-    hipLaunchKernelGGL((k_sbm_chunks<1>), dim3(nbc), dim3(256), 0, st, dseg.as<SbmSeg>(), (int)segs.size(), nchunks,
-                       (unsigned long long)seed, dorder.as<int>(), (int*)nullptr, off.as<int>(), er.as<int>(),
-                       ec.as<int>(), deg.as<int>(), directed ? 1 : 0);
-  }
-  KCHK(scan_exclusive(ctx, deg.as<int>(), h->rowptr.as<int>(), n + 1));
-  int stored = 0;  // 2 m for an undirected graph without self-loops; fewer with them, m when directed
-  KHIP(hipMemcpyAsync(&stored, h->rowptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-  KHIP(hipStreamSynchronize(st));
-  h->nnz = stored;
-  KCHK(h->col.alloc((size_t)std::max<long long>(stored, 1) * sizeof(int)));
-  KCHK(h->val.alloc((size_t)std::max<long long>(stored, 1) * sizeof(double)));
-  if (m > 0) {
-    KCHK(cursor.alloc(((size_t)N + 1) * sizeof(int)));
-    KHIP(hipMemsetAsync(cursor.p, 0, ((size_t)N + 1) * sizeof(int), st));
-    hipLaunchKernelGGL(k_sbm_fill, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, er.as<int>(), ec.as<int>(),
-                       m, h->rowptr.as<int>(), cursor.as<int>(), h->col.as<int>(), h->val.as<double>(), directed ? 1 : 0);
-    hipLaunchKernelGGL(k_knn_row_sort, dim3((n + 255) / 256), dim3(256), 0, st, h->rowptr.as<int>(), n,
-                       h->col.as<int>(), h->val.as<double>());
-  }
-  KHIP(hipGetLastError());
-  KHIP(hipStreamSynchronize(st));
-#undef KCHK
-#undef KHIP
-  h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h;
   return GSPX_OK;
 }
 
@@ -974,142 +688,83 @@ extern "C" int gspx_radius_build(gspx_ctx* ctx, int64_t N, int d, const double* 
   if (!coords) return set_err(GSPX_ERR_INVALID, "null coordinates");
   if (!(epsilon > 0) || !std::isfinite(epsilon)) return set_err(GSPX_ERR_INVALID, "epsilon must be positive");
   if (!(sigma >= 0) || !std::isfinite(sigma)) return set_err(GSPX_ERR_INVALID, "sigma must be >= 0 (0: mean distance)");
-  KnnGrid g{};
-  const bool grid_search = d <= 3;  // beyond three dimensions: MFMA candidate sweep + exact test (gspx_knn_bf.hip.h)
-  const int dg = grid_search ? d : 0;
-  g.d = dg;
-  g.metric = metric;
-  double hi[3] = {0, 0, 0};
-  for (int j = 0; j < 3; ++j) {
-    g.lo[j] = 0;
-    g.inv_h[j] = 1;
-    g.n[j] = 1;
-  }
-  for (int j = 0; j < dg; ++j) g.lo[j] = hi[j] = coords[j];
-  for (int64_t i = 0; i < N; ++i)
-    for (int j = 0; j < d; ++j) {
-      const double v = coords[i * d + j];
-      if (!std::isfinite(v)) return set_err(GSPX_ERR_INVALID, "non-finite coordinate");
-      if (j < dg) {
-        g.lo[j] = std::min(g.lo[j], v);
-        hi[j] = std::max(hi[j], v);
-      }
-    }
-  // cells of at least epsilon (a little more, against rounding at the walls), at most `cap` per axis
-  const int cap = d == 1 ? (1 << 21) : (d == 2 ? 2048 : 128);
-  int64_t ncells = 1;
-  g.h_min = 1e300;
-  for (int j = 0; j < dg; ++j) {
-    const double ext = hi[j] - g.lo[j];
-    int n = ext > 0 ? (int)std::min<double>((double)cap, std::floor(ext / (epsilon * 1.0000001))) : 1;
+  KnnGrid g;
+  double ext[3];
+  CHK(knn_scan_coords(N, d, coords, metric, g, ext));
+  const bool grid_search = g.d > 0;  // beyond three dimensions: MFMA candidate sweep + exact test (gspx_knn_bf.hip.h)
+  // cells of at least epsilon (a little more, against rounding at the walls), at most knn_axis_cap per axis
+  for (int j = 0; j < g.d; ++j) {
+    int n = ext[j] > 0 ? (int)std::min<double>((double)knn_axis_cap(d), std::floor(ext[j] / (epsilon * 1.0000001))) : 1;
     n = std::max(n, 1);
-    const double h = ext > 0 ? ext / n : 1.0;
+    const double h = ext[j] > 0 ? ext[j] / n : 1.0;
     g.n[j] = n;
     g.inv_h[j] = 1.0 / h;
     g.h_min = std::min(g.h_min, h);
-    ncells *= n;
   }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   auto t0 = std::chrono::steady_clock::now();
-  gspx_knn* h = new gspx_knn();
+  std::unique_ptr<gspx_knn> h(new gspx_knn());
   h->ctx = ctx;
   h->N = N;
   h->d = d;
-  auto fail = [&](int rc) {
-    delete h;
-    return rc;
-  };
-#define KCHK(x)                      \
-  do {                               \
-    int rc__ = (x);                  \
-    if (rc__ != GSPX_OK) return fail(rc__); \
-  } while (0)
-#define KHIP(x)                                                                            \
-  do {                                                                                     \
-    hipError_t e__ = (x);                                                                  \
-    if (e__ != hipSuccess) return fail(set_err(GSPX_ERR_HIP, "%s: %s", #x, hipGetErrorString(e__))); \
-  } while (0)
   const int n = (int)N;
-  DevMem x, sorted, cell, count, start, cursor, order, cnt, partial;
-  KCHK(x.alloc((size_t)N * d * sizeof(double)));
-  KCHK(sorted.alloc((size_t)N * d * sizeof(double)));
-  KCHK(cell.alloc((size_t)N * sizeof(int)));
-  KCHK(count.alloc(((size_t)ncells + 1) * sizeof(int)));
-  KCHK(start.alloc(((size_t)ncells + 1) * sizeof(int)));
-  KCHK(cursor.alloc(((size_t)ncells + 1) * sizeof(int)));
-  KCHK(order.alloc((size_t)N * sizeof(int)));
-  KCHK(cnt.alloc(((size_t)N + 1) * sizeof(int)));
-  KCHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
-  KHIP(hipMemcpyAsync(x.p, coords, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, st));
-  KHIP(hipMemsetAsync(count.p, 0, ((size_t)ncells + 1) * sizeof(int), st));
-  KHIP(hipMemsetAsync(cursor.p, 0, ((size_t)ncells + 1) * sizeof(int), st));
-  KHIP(hipMemsetAsync(cnt.p, 0, ((size_t)N + 1) * sizeof(int), st));
-  const int nbN = (n + 255) / 256;
-  const double eps2 = metric == 0 ? epsilon * epsilon : epsilon;  // threshold on the comparison key
+  DevMem x, cnt, partial;
+  KnnGridIndex index;
   DevMem c_off, c_buf;  // candidate lists of the brute-force search
+  CHK(x.alloc((size_t)N * d * sizeof(double)));
+  if (grid_search) CHK(index.alloc(n, g));
+  CHK(cnt.alloc(((size_t)N + 1) * sizeof(int)));
+  CHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
+  HIPCHK(hipMemcpyAsync(x.p, coords, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(cnt.p, 0, ((size_t)N + 1) * sizeof(int), st));
+  const double eps2 = metric == 0 ? epsilon * epsilon : epsilon;  // threshold on the comparison key
   const bool swept = !grid_search && metric == 0 && N > 256;
+  const dim3 qgrid((n + 127) / 128), qblock(128);
   if (!grid_search) {
-    KHIP(hipStreamSynchronize(st));
-    if (swept) KCHK(radius_candidates(ctx, x.as<double>(), n, d, eps2, c_off, c_buf));
+    HIPCHK(hipStreamSynchronize(st));
+    if (swept) CHK(radius_candidates(ctx, x.as<double>(), n, d, eps2, c_off, c_buf));
     launch_bf_radius<0>(ctx, x.as<double>(), n, d, metric, eps2, swept ? c_off.as<int>() : nullptr,
                         swept ? c_buf.as<int>() : nullptr, cnt.as<int>(), nullptr, nullptr, nullptr);
   } else {
-  hipLaunchKernelGGL(k_knn_cell_count, dim3(nbN), dim3(256), 0, st, x.as<double>(), n, g, cell.as<int>(),
-                     count.as<int>());
-  KCHK(scan_exclusive(ctx, count.as<int>(), start.as<int>(), (int)ncells + 1));
-  hipLaunchKernelGGL(k_knn_scatter, dim3(nbN), dim3(256), 0, st, cell.as<int>(), n, start.as<int>(),
-                     cursor.as<int>(), order.as<int>());
-  hipLaunchKernelGGL(k_knn_cell_sort, dim3((unsigned)((ncells + 255) / 256)), dim3(256), 0, st,
-                     start.as<int>(), (int)ncells, order.as<int>(), x.as<double>(), d, sorted.as<double>());
-  hipLaunchKernelGGL((k_radius_query<0>), dim3((n + 127) / 128), dim3(128), 0, st, sorted.as<double>(),
-                     order.as<int>(), start.as<int>(), n, g, eps2, cnt.as<int>(), (const int*)nullptr,
-                     (int*)nullptr, (double*)nullptr);
+    CHK(index.build(ctx, x.as<double>(), n, g));
+    hipLaunchKernelGGL((k_radius_query<0>), qgrid, qblock, 0, st, index.sorted.as<double>(), index.order.as<int>(),
+                       index.start.as<int>(), n, g, eps2, cnt.as<int>(), (const int*)nullptr, (int*)nullptr,
+                       (double*)nullptr);
   }
-  KCHK(scan_exclusive(ctx, cnt.as<int>(), h->rowptr.as<int>(), n + 1));
+  CHK(scan_exclusive(ctx, cnt.as<int>(), h->rowptr.as<int>(), n + 1));
   int nnz = 0;
-  KHIP(hipMemcpyAsync(&nnz, h->rowptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-  KHIP(hipStreamSynchronize(st));
-  if (nnz < 0) return fail(set_err(GSPX_ERR_INVALID, "gspx_radius_build: more than 2^31 neighbour pairs"));
+  HIPCHK(hipMemcpyAsync(&nnz, h->rowptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (nnz < 0) return set_err(GSPX_ERR_INVALID, "gspx_radius_build: more than 2^31 neighbour pairs");
   h->nnz = nnz;
-  KCHK(h->col.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
-  KCHK(h->val.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
-  KCHK(h->dist.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
+  CHK(h->col.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
+  CHK(h->val.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
+  CHK(h->dist.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
   if (nnz > 0) {
     if (!grid_search)
       launch_bf_radius<1>(ctx, x.as<double>(), n, d, metric, eps2, swept ? c_off.as<int>() : nullptr,
                           swept ? c_buf.as<int>() : nullptr, nullptr, h->rowptr.as<int>(), h->col.as<int>(),
                           h->dist.as<double>());
     else
-    hipLaunchKernelGGL((k_radius_query<1>), dim3((n + 127) / 128), dim3(128), 0, st, sorted.as<double>(),
-                       order.as<int>(), start.as<int>(), n, g, eps2, (int*)nullptr, h->rowptr.as<int>(),
-                       h->col.as<int>(), h->dist.as<double>());
-    hipLaunchKernelGGL(k_knn_row_sort, dim3(nbN), dim3(256), 0, st, h->rowptr.as<int>(), n, h->col.as<int>(),
+      hipLaunchKernelGGL((k_radius_query<1>), qgrid, qblock, 0, st, index.sorted.as<double>(), index.order.as<int>(),
+                         index.start.as<int>(), n, g, eps2, (int*)nullptr, h->rowptr.as<int>(), h->col.as<int>(),
+                         h->dist.as<double>());
+    hipLaunchKernelGGL(k_knn_row_sort, dim3((n + 255) / 256), dim3(256), 0, st, h->rowptr.as<int>(), n, h->col.as<int>(),
                        h->dist.as<double>());
     if (sigma == 0.0) {  // mean neighbour distance (nngraph.py:248-262)
-      const int nb = 1024;
-      KCHK(partial.alloc((size_t)nb * sizeof(double)));
-      hipLaunchKernelGGL(k_knn_sum_partial, dim3(nb), dim3(256), 0, st, h->dist.as<double>(), (size_t)nnz,
-                         partial.as<double>());
-      std::vector<double> hp(nb);
-      KHIP(hipMemcpyAsync(hp.data(), partial.p, nb * sizeof(double), hipMemcpyDeviceToHost, st));
-      KHIP(hipStreamSynchronize(st));
-      double s = 0;
-      for (double v : hp) s += v;
-      sigma = s / (double)nnz;
-      if (!(sigma > 0)) return fail(set_err(GSPX_ERR_INVALID, "gspx_radius_build: all neighbour distances are zero"));
+      CHK(knn_mean_dist(ctx, h->dist.as<double>(), (size_t)nnz, partial, &sigma));
+      if (!(sigma > 0)) return set_err(GSPX_ERR_INVALID, "gspx_radius_build: all neighbour distances are zero");
     }
     hipLaunchKernelGGL(k_radius_weights, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st,
                        h->dist.as<double>(), (size_t)nnz, sigma, h->val.as<double>());
   } else if (sigma == 0.0) {
-    return fail(set_err(GSPX_ERR_INVALID, "No neighbors found"));  // nngraph.py:263-264
+    return set_err(GSPX_ERR_INVALID, "No neighbors found");  // nngraph.py:263-264
   }
   h->sigma = sigma;
-  KHIP(hipGetLastError());
-  KHIP(hipStreamSynchronize(st));
-#undef KCHK
-#undef KHIP
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
   h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h;
+  *out = h.release();
   return GSPX_OK;
 }

@@ -9,14 +9,14 @@
 // must not lose a true neighbour to rounding).  Four stages:
 //   1. k_bf_prepare   points -> MFMA operand order (per 16-point tile and 4 dimensions: one coalesced 512-byte
 //                     line, lane l = point l % 16, dimension l / 16), squared norms
-//   2. k_bf_tau       per query an UPPER BOUND tau of its k-th neighbour distance: the exact k-th smallest
+//   2. k_bf_exact<0>  per query an UPPER BOUND tau of its k-th neighbour distance: the exact k-th smallest
 //                     squared distance to a strided sample of M points (a subset's order statistics bound the
 //                     full set's from above)
 //   3. k_bf_collect   MFMA sweep of every 64-query block over the points: every pair whose approximate squared
 //                     distance is <= tau (+ a rounding margin) is appended to the query's candidate list.  Two
-//                     sweeps: a strided subset of sqrt(N M) points, then - after k_bf_refine tightened every bound to the
+//                     sweeps: a strided subset of sqrt(N M) points, then - after k_bf_exact<1> tightened every bound to the
 //                     exact k-th smallest of the candidates so far - the rest: k (N1 / M + N / N1) entries per query
-//   4. k_bf_select    candidates re-evaluated in the KD-tree's own arithmetic (knn_sqdist: per-dimension
+//   4. k_bf_exact<2>  candidates re-evaluated in the KD-tree's own arithmetic (knn_sqdist: per-dimension
 //                     differences, no fused multiply-add; correctly rounded square root) and the k smallest by
 //                     (distance, index) kept - so neighbours and distances equal scipy's bit for bit, exactly
 //                     like the grid search in 1-3 dimensions.  A query whose list overflowed (heavy ties /
@@ -110,36 +110,63 @@ __global__ void k_bf_prepare(const double* __restrict__ x, int N, int d, int DT,
   }
 }
 
-// tau[i] = k-th smallest exact key (squared euclidean distance in the KD-tree's arithmetic) from point i to the
-// sample {0, stride, 2 stride, ...} without i itself: an upper bound of its k-th neighbour's key
-template <int KMAX, int DT>
-__global__ __launch_bounds__(128) void k_bf_tau(const double* __restrict__ x, int N, int d, int k, int stride,
-                                                double* __restrict__ tau) {
+// The three exact stages of the plan up to 64 dimensions, one thread per query with the query and its list of the
+// KMAX best (knn_best_*, gspx_knn.hip.h) in registers.  All of them evaluate candidates in the KD-tree's arithmetic:
+//   WHAT 0  tau[i] = the k-th smallest key (squared euclidean distance) from point i to the sample {0, stride,
+//           2 stride, ...} without i itself: an upper bound of its k-th neighbour's key
+//   WHAT 1  between the two sweeps: the exact k-th smallest key among the query's candidates so far (all from the first
+//           point range) is a tighter bound than the sample gave; tau[i] only ever goes down
+//   WHAT 2  the candidates (or every point, when the list overflowed / holds fewer than k / no list was made)
+//           evaluated in the caller's metric and the k smallest by (key, index) written, nearest first
+// Stages 0 and 1 keep keys alone and are euclidean only (knn_sqdist_reg); stage 2 keeps indices and goes through
+// knn_key_reg.  A stage reads only its own arguments: 0 - stride, tau; 1 - cap, cnt, buf, tau; 2 - metric, cap, cnt
+// (nullable), buf, nn, dist, n_scans.  k_bf_exact_wide<WHAT> is the same beyond 64 dimensions.
+template <int WHAT, int KMAX, int DT>
+__global__ __launch_bounds__(128) void k_bf_exact(const double* __restrict__ x, int N, int d, int k, int metric,
+                                                  int stride, int cap, const int* __restrict__ cnt,
+                                                  const int* __restrict__ buf, double* __restrict__ tau,
+                                                  int* __restrict__ nn, double* __restrict__ dist,
+                                                  int* __restrict__ n_scans) {
   const int i = blockIdx.x * 128 + threadIdx.x;
   if (i >= N) return;
   double q[4 * DT];
   bf_load_query<DT>(q, x + (size_t)i * d, d);
+  constexpr bool IDX = WHAT == 2;
   double bd[KMAX];
-#pragma unroll
-  for (int t = 0; t < KMAX; ++t) bd[t] = 1e300;
-  for (int c = 0; c < N; c += stride) {
-    if (c == i) continue;
-    double cd = knn_sqdist_reg<DT>(q, x + (size_t)c * d, d);
-    if (cd < bd[KMAX - 1]) {
-#pragma unroll
-      for (int t = 0; t < KMAX; ++t) {
-        const bool lt = cd < bd[t];
-        const double td = bd[t];
-        bd[t] = lt ? cd : td;
-        cd = lt ? td : cd;
-      }
-    }
+  int bi[IDX ? KMAX : 1];  // (stages 0 and 1 carry no indices: never touched)
+  if constexpr (IDX) knn_best_init<KMAX>(bd, bi);
+  else knn_best_init<KMAX>(bd);
+  // the candidates: a = 0, inc, 2 inc, ... below n, each either a point itself or a slot of the query's list
+  bool scan = false;
+  int n = N, inc = 1;
+  if constexpr (WHAT == 0) {
+    inc = stride;
+  } else if constexpr (WHAT == 1) {
+    n = min(cnt[i], cap);
+  } else {
+    const int have = cnt ? cnt[i] : -1;
+    scan = have < 0 || have > cap || have < k;
+    n = scan ? N : have;
+    if (scan && cnt) atomicAdd(n_scans, 1);
   }
-  double kth = 1e300;
+  for (int a = 0; a < n; a += inc) {
+    const int idx = (WHAT == 0 || scan) ? a : buf[(size_t)i * cap + a];
+    if (idx == i) continue;
+    const double* p = x + (size_t)idx * d;
+    if constexpr (IDX) knn_best_insert<KMAX>(bd, bi, knn_key_reg<DT>(q, p, d, metric), idx);
+    else knn_best_insert<KMAX>(bd, knn_sqdist_reg<DT>(q, p, d));
+  }
+  if constexpr (IDX) {
 #pragma unroll
-  for (int t = 0; t < KMAX; ++t)
-    if (t == k - 1) kth = bd[t];
-  tau[i] = kth;
+    for (int t = 0; t < KMAX; ++t)
+      if (t < k) {
+        nn[(size_t)i * k + t] = bi[t];
+        dist[(size_t)i * k + t] = metric == 0 ? knn_sqrt(bd[t]) : bd[t];
+      }
+  } else {
+    const double kth = knn_best_kth<KMAX>(bd, k);
+    if (WHAT == 0 || kth < tau[i]) tau[i] = kth;
+  }
 }
 
 // candidate lists: either N fixed-capacity rows (off == null; cap == 0: count only), or rows of their own lengths
@@ -156,7 +183,7 @@ __device__ __forceinline__ void bf_append(const int* __restrict__ off, int cap, 
 
 // ---- what the narrow (d <= 64) and the wide (d > 64) sweep share ---------------------------------------------------
 // F = double: v_mfma_f64_16x16x4f64.  F = float: v_mfma_f32_16x16x4f32 at twice the rate - the sweep only has to
-// admit a SUPERSET of the true neighbours (k_bf_select decides in the KD-tree's arithmetic), so single precision
+// admit a SUPERSET of the true neighbours (the exact stage decides in the KD-tree's arithmetic), so single precision
 // does when its rounding margin, (4 DT + 8) 2^-24 (|x|^2 + |y|^2), is small against the bounds (the caller checks);
 // the bound is rounded up and the point's norm down, towards admitting.
 typedef float bf_f4 __attribute__((ext_vector_type(4)));
@@ -207,7 +234,7 @@ __device__ __forceinline__ int bf_tile_of(int phase, int step, int j) {
 }
 // The 16 (query, point) tests of a lane for one point tile (acc: the four query tiles' products with it, nc: the
 // point's norm), folded into one mask: a single wave-wide branch per tile guards the rare appends.  (The point itself
-// is not filtered here: k_bf_select skips it.)  Hits are parked in the wave's LDS queue ((query << 32) | point, 128
+// is not filtered here: the exact stages skip it.)  Hits are parked in the wave's LDS queue ((query << 32) | point, 128
 // slots) and appended 64 at a time: an append is an atomic (whose return the wave must wait for) plus a scattered
 // store, and about 60 % of the tiles hit something - appending on the spot stalled the wave a memory round trip per
 // tile.  queued is wave-uniform.
@@ -421,89 +448,6 @@ __global__ __launch_bounds__(256) void k_bf_collect_wide(const F* __restrict__ x
   bf_flush(lane, queue, queued, off, cap, cnt, buf);
 }
 
-// Between the two sweeps: the exact k-th smallest key among a query's candidates so far (all from the first
-// point range) is a tighter upper bound of its k-th neighbour's key than the sample gave
-template <int KMAX, int DT>
-__global__ __launch_bounds__(128) void k_bf_refine(const double* __restrict__ x, int N, int d, int k, int cap,
-                                                   const int* __restrict__ cnt, const int* __restrict__ buf,
-                                                   double* __restrict__ tau) {
-  const int i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= N) return;
-  double q[4 * DT];
-  bf_load_query<DT>(q, x + (size_t)i * d, d);
-  double bd[KMAX];
-#pragma unroll
-  for (int t = 0; t < KMAX; ++t) bd[t] = 1e300;
-  const int n = min(cnt[i], cap);
-  for (int a = 0; a < n; ++a) {
-    const int idx = buf[(size_t)i * cap + a];
-    if (idx == i) continue;
-    double cd = knn_sqdist_reg<DT>(q, x + (size_t)idx * d, d);
-    if (cd < bd[KMAX - 1]) {
-#pragma unroll
-      for (int t = 0; t < KMAX; ++t) {
-        const bool lt = cd < bd[t];
-        const double td = bd[t];
-        bd[t] = lt ? cd : td;
-        cd = lt ? td : cd;
-      }
-    }
-  }
-  double kth = 1e300;
-#pragma unroll
-  for (int t = 0; t < KMAX; ++t)
-    if (t == k - 1) kth = bd[t];
-  if (kth < tau[i]) tau[i] = kth;
-}
-
-// exact evaluation of the candidates (or of every point when the list overflowed / no list was made) and
-// selection of the k smallest by (key, index); nearest first
-template <int KMAX, int DT>
-__global__ __launch_bounds__(128) void k_bf_select(const double* __restrict__ x, int N, int d, int k, int metric,
-                                                   int cap, const int* __restrict__ cnt, const int* __restrict__ buf,
-                                                   int* __restrict__ nn, double* __restrict__ dist,
-                                                   int* __restrict__ n_scans) {
-  const int i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= N) return;
-  double q[4 * DT];
-  bf_load_query<DT>(q, x + (size_t)i * d, d);
-  double bd[KMAX];
-  int bi[KMAX];
-#pragma unroll
-  for (int t = 0; t < KMAX; ++t) {
-    bd[t] = 1e300;
-    bi[t] = 0x7fffffff;
-  }
-  const int have = cnt ? cnt[i] : -1;
-  const bool scan = have < 0 || have > cap || have < k;
-  const int n = scan ? N : have;
-  if (scan && cnt) atomicAdd(n_scans, 1);
-  for (int a = 0; a < n; ++a) {
-    const int idx = scan ? a : buf[(size_t)i * cap + a];
-    if (idx == i) continue;
-    double cd = knn_key_reg<DT>(q, x + (size_t)idx * d, d, metric);
-    int ci = idx;
-    if (cd < bd[KMAX - 1] || (cd == bd[KMAX - 1] && ci < bi[KMAX - 1])) {
-#pragma unroll
-      for (int t = 0; t < KMAX; ++t) {
-        const bool lt = cd < bd[t] || (cd == bd[t] && ci < bi[t]);
-        const double td = bd[t];
-        const int ti = bi[t];
-        bd[t] = lt ? cd : td;
-        bi[t] = lt ? ci : ti;
-        cd = lt ? td : cd;
-        ci = lt ? ti : ci;
-      }
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < KMAX; ++t)
-    if (t < k) {
-      nn[(size_t)i * k + t] = bi[t];
-      dist[(size_t)i * k + t] = metric == 0 ? knn_sqrt(bd[t]) : bd[t];
-    }
-}
-
 // ---- exact evaluation in more than 64 dimensions --------------------------------------------------------------
 // A query row of that width in a per-thread array would live in scratch memory (see knn_sqdist_reg), so here ONE WAVE
 // serves a query: the row is staged once in LDS (d doubles; every lane reads the same word: a broadcast), the lanes take
@@ -539,8 +483,9 @@ __device__ __forceinline__ void bf_stage_query(double* qs, const double* __restr
   for (int j = lane; j < d; j += 64) qs[j] = row[j];
   __syncthreads();  // (a one-wave workgroup)
 }
-// WHAT 0: k_bf_tau (candidates: the strided sample), 1: k_bf_refine (the candidates so far), 2: k_bf_select (the
-// candidates, or every point).  One 64-thread workgroup per query; dynamic LDS: d doubles.
+// WHAT as in k_bf_exact - 0: the sample bounds (candidates: the strided sample), 1: their refinement (the candidates
+// so far), 2: the selection (the candidates, or every point).  One 64-thread workgroup per query; dynamic LDS: d
+// doubles.
 template <int WHAT>
 __global__ __launch_bounds__(64) void k_bf_exact_wide(const double* __restrict__ x, int N, int d, int k, int metric,
                                                       int stride, int cap, const int* __restrict__ cnt,
@@ -584,50 +529,90 @@ __global__ __launch_bounds__(64) void k_bf_exact_wide(const double* __restrict__
 
 }  // namespace gspx
 
-template <int KMAX, int DT>
-static void launch_bf_kd(gspx_ctx* ctx, const double* x, int N, int d, int k, int metric, int stride, double* tau,
-                         int cap, const int* cnt, const int* buf, int* nn, double* dist, int* n_scans, int what) {
-  const dim3 grid((unsigned)((N + 127) / 128));
-  if (what == 0)
-    hipLaunchKernelGGL((gspx::k_bf_tau<KMAX, DT>), grid, dim3(128), 0, ctx->stream, x, N, d, k, stride, tau);
-  else if (what == 1)
-    hipLaunchKernelGGL((gspx::k_bf_refine<KMAX, DT>), grid, dim3(128), 0, ctx->stream, x, N, d, k, cap, cnt, buf, tau);
-  else
-    hipLaunchKernelGGL((gspx::k_bf_select<KMAX, DT>), grid, dim3(128), 0, ctx->stream, x, N, d, k, metric, cap, cnt, buf,
-                       nn, dist, n_scans);
+// The exact stage WHAT (0 the sample bounds, 1 their refinement between the sweeps, 2 the selection): up to 64
+// dimensions the build of k_bf_exact for k <= 8 / 16 / 32 / 64 and d <= 16 / 32 / 64 (36 builds), one thread per query;
+// beyond, k_bf_exact_wide, one wave per query with its row in LDS and one build for every k.  The kernels share one
+// argument list (what a stage does not read may be null / 0).
+template <int WHAT, int KMAX> static auto bf_exact_kernel(int d) {
+  return d <= 16 ? gspx::k_bf_exact<WHAT, KMAX, 4>
+                 : (d <= 32 ? gspx::k_bf_exact<WHAT, KMAX, 8> : gspx::k_bf_exact<WHAT, KMAX, 16>);
 }
-template <int KMAX>
-static void launch_bf_k(gspx_ctx* ctx, const double* x, int N, int d, int k, int metric, int stride, double* tau, int cap,
-                        const int* cnt, const int* buf, int* nn, double* dist, int* n_scans, int what) {
-  if (d <= 16) launch_bf_kd<KMAX, 4>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
-  else if (d <= 32) launch_bf_kd<KMAX, 8>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
-  else launch_bf_kd<KMAX, 16>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
-}
-// what: 0 the sample bounds (k_bf_tau), 1 their refinement between the sweeps (k_bf_refine), 2 the selection
+template <int WHAT>
 static void launch_bf(gspx_ctx* ctx, const double* x, int N, int d, int k, int metric, int stride, double* tau, int cap,
-                      const int* cnt, const int* buf, int* nn, double* dist, int* n_scans, int what) {
-  if (d > 64) {  // one wave per query, one build for every k (k_bf_exact_wide)
-    const dim3 grid((unsigned)N), block(64);
-    const size_t lds = (size_t)d * sizeof(double);
-    if (what == 0)
-      hipLaunchKernelGGL((gspx::k_bf_exact_wide<0>), grid, block, lds, ctx->stream, x, N, d, k, metric, stride, cap, cnt, buf,
-                         tau, nn, dist, n_scans);
-    else if (what == 1)
-      hipLaunchKernelGGL((gspx::k_bf_exact_wide<1>), grid, block, lds, ctx->stream, x, N, d, k, metric, stride, cap, cnt, buf,
-                         tau, nn, dist, n_scans);
-    else
-      hipLaunchKernelGGL((gspx::k_bf_exact_wide<2>), grid, block, lds, ctx->stream, x, N, d, k, metric, stride, cap, cnt, buf,
-                         tau, nn, dist, n_scans);
-    return;
+                      const int* cnt, const int* buf, int* nn, double* dist, int* n_scans) {
+  auto kernel = gspx::k_bf_exact_wide<WHAT>;
+  dim3 grid((unsigned)N), block(64);
+  size_t lds = (size_t)d * sizeof(double);
+  if (d <= 64) {
+    kernel = k <= 8 ? bf_exact_kernel<WHAT, 8>(d)
+                    : (k <= 16 ? bf_exact_kernel<WHAT, 16>(d)
+                               : (k <= 32 ? bf_exact_kernel<WHAT, 32>(d) : bf_exact_kernel<WHAT, 64>(d)));
+    grid = dim3((unsigned)((N + 127) / 128));
+    block = dim3(128);
+    lds = 0;
   }
-  if (k <= 8) launch_bf_k<8>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
-  else if (k <= 16) launch_bf_k<16>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
-  else if (k <= 32) launch_bf_k<32>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
-  else launch_bf_k<64>(ctx, x, N, d, k, metric, stride, tau, cap, cnt, buf, nn, dist, n_scans, what);
+  hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, x, N, d, k, metric, stride, cap, cnt, buf, tau, nn, dist,
+                     n_scans);
 }
 
 // 4-column MFMA steps of the sweep: the narrow builds' template constant up to 64 dimensions, ceil(d / 4) beyond
 static int bf_steps(int d) { return d <= 16 ? 4 : (d <= 32 ? 8 : (d <= 64 ? 16 : (d + 3) / 4)); }
+
+// What a sweep multiplies: the cloud in MFMA operand order (fp64, and fp32 on request), the squared norms and their
+// maximum, and the rounding margin of the fp64 product form.  prepare() queues k_bf_prepare; norm_max() downloads the
+// norms and waits for the stream - whatever the caller queued in between runs meanwhile.
+struct BfOperands {
+  DevMem xop, xop32, norm;
+  int N = 0, d = 0, DT = 0, ntiles = 0;
+  double nmax = 0;
+  // |fl(|y|^2 - 2 x.y) + |x|^2 - |x - y|^2| <= (4 DT + 8) u (|x|^2 + |y|^2) with u = 2^-53; ten times that
+  // (DT = ceil(d / 4) steps beyond 64 dimensions: the bound grows with the length of the dot product)
+  double margin64 = 0;
+  int prepare(gspx_ctx* ctx, const double* x, int N_, int d_, bool with32) {
+    N = N_, d = d_, DT = bf_steps(d), ntiles = (N + 15) / 16;
+    margin64 = 10.0 * (4.0 * DT + 8.0) * 1.1102230246251565e-16;
+    CHK(xop.alloc((size_t)ntiles * DT * 64 * sizeof(double)));
+    if (with32) CHK(xop32.alloc((size_t)ntiles * DT * 64 * sizeof(float)));
+    CHK(norm.alloc((size_t)ntiles * 16 * sizeof(double)));
+    const long long total = (long long)ntiles * DT * 64;
+    hipLaunchKernelGGL(gspx::k_bf_prepare, dim3((unsigned)((std::max<long long>(total, N) + 255) / 256)), dim3(256), 0,
+                       ctx->stream, x, N, d, DT, xop.as<double>(), norm.as<double>(),
+                       with32 ? xop32.as<float>() : (float*)nullptr);
+    return GSPX_OK;
+  }
+  int norm_max(gspx_ctx* ctx) {
+    std::vector<double> hn((size_t)N);
+    HIPCHK(hipMemcpyAsync(hn.data(), norm.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    nmax = 0;
+    for (double v : hn) nmax = std::max(nmax, v);
+    return GSPX_OK;
+  }
+};
+
+// One sweep of the 64-query blocks over `count` point tiles (phase / step: bf_tile_of) on the fp32 or the fp64 matrix
+// cores: k_bf_collect<4 | 8 | 16> up to 64 dimensions, k_bf_collect_wide beyond.  Every pair within the query's bound
+// tau (+ margin (|x|^2 + nmax)) is counted in cnt and appended to buf: fixed-capacity rows (cap), or rows off[q] ..
+// off[q + 1] (bf_append).
+template <typename F>
+static void launch_bf_collect_as(hipStream_t st, const BfOperands& op, const F* xop, const double* tau, int phase, int step,
+                                 int count, double margin, int cap, const int* off, int* cnt, int* buf) {
+  const dim3 grid((unsigned)((op.N + 255) / 256)), block(256);
+  if (op.d > 64) {
+    hipLaunchKernelGGL(gspx::k_bf_collect_wide<F>, grid, block, 0, st, xop, op.norm.as<double>(), tau, op.N, op.DT, phase,
+                       step, count, margin, op.nmax, cap, off, cnt, buf);
+    return;
+  }
+  const auto kernel =
+      op.DT == 4 ? gspx::k_bf_collect<4, F> : (op.DT == 8 ? gspx::k_bf_collect<8, F> : gspx::k_bf_collect<16, F>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, st, xop, op.norm.as<double>(), tau, op.N, phase, step, count, margin, op.nmax,
+                     cap, off, cnt, buf);
+}
+static void launch_bf_collect(hipStream_t st, bool f32, const BfOperands& op, const double* tau, int phase, int step,
+                              int count, double margin, int cap, const int* off, int* cnt, int* buf) {
+  if (f32) launch_bf_collect_as<float>(st, op, op.xop32.as<float>(), tau, phase, step, count, margin, cap, off, cnt, buf);
+  else launch_bf_collect_as<double>(st, op, op.xop.as<double>(), tau, phase, step, count, margin, cap, off, cnt, buf);
+}
 
 // x: N x d doubles on the device; nn / dist: N x k outputs (nearest first, the point itself excluded).
 // stats (nullable, 4 values): sample size, candidate capacity per query, mean candidates per query, queries that
@@ -639,13 +624,12 @@ static int knn_bruteforce(gspx_ctx* ctx, const double* x, int N, int d, int k, i
   CHK(n_scans.alloc(64));
   HIPCHK(hipMemsetAsync(n_scans.p, 0, 64, st));
   if (metric != 0 || N <= 4 * k + 64) {  // no product form (or too few points to bother): exact scan for everybody
-    launch_bf(ctx, x, N, d, k, metric, 1, nullptr, 0, nullptr, nullptr, nn, dist, n_scans.as<int>(), 2);
+    launch_bf<2>(ctx, x, N, d, k, metric, 1, nullptr, 0, nullptr, nullptr, nn, dist, n_scans.as<int>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     if (stats) stats[0] = 0, stats[1] = 0, stats[2] = (double)N, stats[3] = (double)N;
     return GSPX_OK;
   }
-  const int DT = bf_steps(d);
   const int ntiles = (N + 15) / 16;
   // sample: about max(2048, N / 128) points (at least 4 k + 1), strided through the cloud
   const int want = std::max(std::max(2048, N / 128), 4 * k + 1);
@@ -663,74 +647,39 @@ static int knn_bruteforce(gspx_ctx* ctx, const double* x, int N, int d, int k, i
   const double expect = (double)k * (n1 / std::max(M - 1, 1) + (step > 1 ? (double)N / n1 : 0.0));
   // room for four times the expectation (clustered clouds), at least 8 k (+ 1: the point itself passes its own bound)
   const int cap = (int)std::min<int64_t>(std::max<int64_t>((int64_t)(4.0 * expect), 8 * k) + 1, N);
-  DevMem xop, xop32, norm, tau, cnt, buf, pmax;
-  CHK(xop.alloc((size_t)ntiles * DT * 64 * sizeof(double)));
   const bool try32 = ctx->opt.knn_f32 != 0;
-  if (try32) CHK(xop32.alloc((size_t)ntiles * DT * 64 * sizeof(float)));
-  CHK(norm.alloc((size_t)ntiles * 16 * sizeof(double)));
+  BfOperands op;
+  DevMem tau, cnt, buf;
   CHK(tau.alloc((size_t)N * sizeof(double)));
   CHK(cnt.alloc((size_t)N * sizeof(int)));
   CHK(buf.alloc((size_t)N * cap * sizeof(int)));
   HIPCHK(hipMemsetAsync(cnt.p, 0, (size_t)N * sizeof(int), st));
-  const long long total = (long long)ntiles * DT * 64;
-  hipLaunchKernelGGL(gspx::k_bf_prepare, dim3((unsigned)((std::max<long long>(total, N) + 255) / 256)), dim3(256), 0, st, x,
-                     N, d, DT, xop.as<double>(), norm.as<double>(), try32 ? xop32.as<float>() : (float*)nullptr);
-  launch_bf(ctx, x, N, d, k, metric, stride, tau.as<double>(), 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-  std::vector<double> hn((size_t)N), ht((size_t)N);
-  HIPCHK(hipMemcpyAsync(hn.data(), norm.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+  CHK(op.prepare(ctx, x, N, d, try32));
+  launch_bf<0>(ctx, x, N, d, k, metric, stride, tau.as<double>(), 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+  std::vector<double> ht((size_t)N);
   if (try32) HIPCHK(hipMemcpyAsync(ht.data(), tau.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  double nmax = 0;
-  for (double v : hn) nmax = std::max(nmax, v);
-  // |fl(|y|^2 - 2 x.y) + |x|^2 - |x - y|^2| <= (4 DT + 8) u (|x|^2 + |y|^2) with u = 2^-53; ten times that
-  // (DT = ceil(d / 4) steps beyond 64 dimensions: the bound grows with the length of the dot product)
-  const double margin64 = 10.0 * (4.0 * DT + 8.0) * 1.1102230246251565e-16;
-  // The same bound with u = 2^-24 for the single-precision sweep: used when it widens a typical bound (the
-  // median over a sample of the queries) by at most half a percent - clouds far from the origin (|x|^2 >> the
+  CHK(op.norm_max(ctx));
+  // The same bound as op.margin64 with u = 2^-24 for the single-precision sweep: used when it widens a typical bound
+  // (the median over a sample of the queries) by at most half a percent - clouds far from the origin (|x|^2 >> the
   // neighbour distances) keep the fp64 sweep.
-  const double margin32 = 10.0 * (4.0 * DT + 8.0) * 5.9604644775390625e-08;
+  const double margin32 = 10.0 * (4.0 * op.DT + 8.0) * 5.9604644775390625e-08;
   bool use32 = false;
-  if (try32 && nmax < 1e30) {
+  if (try32 && op.nmax < 1e30) {
     std::vector<double> sample;
     for (size_t i = 0; i < (size_t)N; i += std::max<size_t>(1, (size_t)N / 2048)) sample.push_back(ht[i]);
     std::nth_element(sample.begin(), sample.begin() + sample.size() / 2, sample.end());
     const double tmed = sample[sample.size() / 2];
-    use32 = ctx->opt.knn_f32 == 2 || margin32 * 2.0 * nmax <= 0.005 * tmed;
+    use32 = ctx->opt.knn_f32 == 2 || margin32 * 2.0 * op.nmax <= 0.005 * tmed;
   }
-  const double margin = use32 ? margin32 : margin64;
-  const dim3 grid((unsigned)((N + 255) / 256));
-#define GSPX_BF(D_, PH_, CNT_)                                                                                           \
-  do {                                                                                                                   \
-    if (use32)                                                                                                           \
-      hipLaunchKernelGGL((gspx::k_bf_collect<D_, float>), grid, dim3(256), 0, st, xop32.as<float>(), norm.as<double>(),  \
-                         tau.as<double>(), N, PH_, step, CNT_, margin, nmax, cap, (const int*)nullptr, cnt.as<int>(),    \
-                         buf.as<int>());                                                                                 \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((gspx::k_bf_collect<D_, double>), grid, dim3(256), 0, st, xop.as<double>(), norm.as<double>(),  \
-                         tau.as<double>(), N, PH_, step, CNT_, margin, nmax, cap, (const int*)nullptr, cnt.as<int>(),    \
-                         buf.as<int>());                                                                                 \
-  } while (0)
-  auto sweep = [&](int phase, int count) {
-    if (d > 64) {
-      if (use32)
-        hipLaunchKernelGGL((gspx::k_bf_collect_wide<float>), grid, dim3(256), 0, st, xop32.as<float>(), norm.as<double>(),
-                           tau.as<double>(), N, DT, phase, step, count, margin, nmax, cap, (const int*)nullptr,
-                           cnt.as<int>(), buf.as<int>());
-      else
-        hipLaunchKernelGGL((gspx::k_bf_collect_wide<double>), grid, dim3(256), 0, st, xop.as<double>(), norm.as<double>(),
-                           tau.as<double>(), N, DT, phase, step, count, margin, nmax, cap, (const int*)nullptr,
-                           cnt.as<int>(), buf.as<int>());
-    } else if (DT == 4) GSPX_BF(4, phase, count);
-    else if (DT == 8) GSPX_BF(8, phase, count);
-    else GSPX_BF(16, phase, count);
-  };
-  sweep(0, t1);
+  const double margin = use32 ? margin32 : op.margin64;
+  launch_bf_collect(st, use32, op, tau.as<double>(), 0, step, t1, margin, cap, nullptr, cnt.as<int>(), buf.as<int>());
   if (step > 1) {
-    launch_bf(ctx, x, N, d, k, metric, stride, tau.as<double>(), cap, cnt.as<int>(), buf.as<int>(), nullptr, nullptr, nullptr, 1);
-    sweep(1, ntiles - t1);
+    launch_bf<1>(ctx, x, N, d, k, metric, stride, tau.as<double>(), cap, cnt.as<int>(), buf.as<int>(), nullptr, nullptr,
+                 nullptr);
+    launch_bf_collect(st, use32, op, tau.as<double>(), 1, step, ntiles - t1, margin, cap, nullptr, cnt.as<int>(),
+                      buf.as<int>());
   }
-#undef GSPX_BF
-  launch_bf(ctx, x, N, d, k, metric, stride, nullptr, cap, cnt.as<int>(), buf.as<int>(), nn, dist, n_scans.as<int>(), 2);
+  launch_bf<2>(ctx, x, N, d, k, metric, stride, nullptr, cap, cnt.as<int>(), buf.as<int>(), nn, dist, n_scans.as<int>());
   HIPCHK(hipGetLastError());
   int scans = 0;
   HIPCHK(hipMemcpyAsync(&scans, n_scans.p, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -837,37 +786,17 @@ static void launch_bf_radius(gspx_ctx* ctx, const double* x, int N, int d, int m
 // Leaves off (N + 1) and buf; euclidean only (the other metrics scan every point in k_bf_radius).
 static int radius_candidates(gspx_ctx* ctx, const double* x, int N, int d, double eps2, DevMem& off, DevMem& buf) {
   hipStream_t st = ctx->stream;
-  const int DT = bf_steps(d);
-  const int ntiles = (N + 15) / 16;
-  DevMem xop, norm, tau, cnt;
-  CHK(xop.alloc((size_t)ntiles * DT * 64 * sizeof(double)));
-  CHK(norm.alloc((size_t)ntiles * 16 * sizeof(double)));
+  BfOperands op;
+  DevMem tau, cnt;
   CHK(tau.alloc((size_t)N * sizeof(double)));
   CHK(cnt.alloc(((size_t)N + 1) * sizeof(int)));
   CHK(off.alloc(((size_t)N + 1) * sizeof(int)));
   HIPCHK(hipMemsetAsync(cnt.p, 0, ((size_t)N + 1) * sizeof(int), st));
-  const long long total = (long long)ntiles * DT * 64;
-  hipLaunchKernelGGL(gspx::k_bf_prepare, dim3((unsigned)((std::max<long long>(total, N) + 255) / 256)), dim3(256), 0, st, x,
-                     N, d, DT, xop.as<double>(), norm.as<double>(), (float*)nullptr);
+  CHK(op.prepare(ctx, x, N, d, false));
   hipLaunchKernelGGL((k_fill<double>), dim3(1024), dim3(256), 0, st, tau.as<double>(), (size_t)N, eps2);
-  std::vector<double> hn((size_t)N);
-  HIPCHK(hipMemcpyAsync(hn.data(), norm.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  double nmax = 0;
-  for (double v : hn) nmax = std::max(nmax, v);
-  const double margin = 10.0 * (4.0 * DT + 8.0) * 1.1102230246251565e-16;
-  const dim3 grid((unsigned)((N + 255) / 256));
-  auto sweep = [&](const int* offp, int* bufp) {
-#define GSPX_BF(D_)                                                                                                  \
-  hipLaunchKernelGGL((gspx::k_bf_collect<D_, double>), grid, dim3(256), 0, st, xop.as<double>(), norm.as<double>(),  \
-                     tau.as<double>(), N, 0, 1, ntiles, margin, nmax, 0, offp, cnt.as<int>(), bufp)
-    if (d > 64)
-      hipLaunchKernelGGL((gspx::k_bf_collect_wide<double>), grid, dim3(256), 0, st, xop.as<double>(), norm.as<double>(),
-                         tau.as<double>(), N, DT, 0, 1, ntiles, margin, nmax, 0, offp, cnt.as<int>(), bufp);
-    else if (DT == 4) GSPX_BF(4);
-    else if (DT == 8) GSPX_BF(8);
-    else GSPX_BF(16);
-#undef GSPX_BF
+  CHK(op.norm_max(ctx));
+  auto sweep = [&](const int* offp, int* bufp) {  // every tile, on the fp64 matrix cores
+    launch_bf_collect(st, false, op, tau.as<double>(), 0, 1, op.ntiles, op.margin64, 0, offp, cnt.as<int>(), bufp);
   };
   sweep(nullptr, nullptr);  // count only
   {  // the total in 64 bits BEFORE the 32-bit scan: a sum beyond 2^32 would wrap back to a plausible positive value

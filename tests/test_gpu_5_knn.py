@@ -6,6 +6,8 @@ The bar here is integer/bit work for the neighbour lists and distances (same ari
 KD-tree: bit-exact), 1e-12 relative for the weights (the mean distance sigma is summed in a different order, and it sits
 in the exponent).
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -63,7 +65,7 @@ def test_golden(ctx, golden_knn):
 @pytest.mark.parametrize("d", [1, 2, 3])
 def test_oracle_uniform(ctx, d):
     rng = np.random.default_rng(10 + d)
-    for N, k in ((3000, 6), (50000, 8), (20000, 20), (5000, 40)):
+    for N, k in ((3000, 6), (50000, 8), (20000, 20), (5000, 40), (3000, 12)):
         check_against_oracle(ctx, rng.uniform(0, 1, (N, d)), k)
 
 
@@ -392,9 +394,13 @@ def test_highdim_radius_oracle(ctx):
     """Ball queries in 5 to 40 dimensions against the KD-tree oracle: identical neighbour sets (the membership test runs
     in the KD-tree's arithmetic on the candidates of the MFMA sweep), weights to 1e-12; a radius that catches nobody is
     the reference's ValueError."""
+    from scipy import spatial
     rng = np.random.default_rng(17)
-    for N, d, eps in ((8000, 5, 0.6), (5000, 12, 2.2), (3000, 40, 6.4), (200, 6, 1.5)):
+    # (the last case, 17 < d <= 32: eps = the 1 % quantile of the pair distances among the first 400 points)
+    for N, d, eps in ((8000, 5, 0.6), (5000, 12, 2.2), (3000, 40, 6.4), (200, 6, 1.5), (3000, 25, None)):
         X = rng.standard_normal((N, d))
+        if eps is None:
+            eps = float(np.quantile(spatial.distance.pdist(X[:400]), 0.01))
         W, sg, _ = engine.radius_graph(X, eps, ctx=ctx)
         Wr, sr = knn.radius_weights(X, eps)
         assert W.nnz == Wr.nnz and W.nnz > 0, (N, d, W.nnz, Wr.nnz)
@@ -422,6 +428,43 @@ def test_highdim_oracle(ctx, N, d, k):
             ctx.set_option("knn_f32", 1)
         if N > 4 * k + 64:  # (a query in the thin tail of the cloud may outgrow its list and take the exact scan)
             assert st["exact_scans"] <= N // 1000 and k <= st["mean_candidates"] <= st["capacity"], (f32, st)
+
+
+@functools.lru_cache(maxsize=None)
+def _cloud_and_tree(N, d):
+    """The module's usual cloud and its KD-tree, built once for every k and sweep precision."""
+    from scipy import spatial
+    rng = np.random.default_rng(N + d)
+    X = rng.standard_normal((N, d)) * rng.uniform(0.5, 2.0, d) + rng.uniform(-1, 1, d)
+    X.setflags(write=False)
+    return X, spatial.KDTree(X)
+
+
+@pytest.mark.parametrize("d", [13, 30, 61])
+@pytest.mark.parametrize("k", [8, 16, 32, 64])
+def test_highdim_every_build(ctx, k, d):
+    """Every narrow build of the exact stages (the list lengths 8 / 16 / 32 / 64 at their upper edge, the query widths
+    16 / 32 / 64 with a remainder modulo 4) through the whole two-sweep plan: 8192 points give a sample of 2048
+    (stride 4), every second tile in the first sweep, the refinement in between, capacity 16 k + 1.  Neighbours and
+    distances of 400 rows equal the KD-tree's bit for bit under the fp64, the forced fp32 and the default sweep.  (A
+    numpy emulation of the fp64 plan on these twelve clouds: no query over capacity or under k; 24.5 - 25.1 candidates
+    per query at k = 8, at most 55; 48 - 50 / 90 at 16; 96 - 98 / 149 at 32; 190 - 195 / 264 at 64.)"""
+    N = 8192
+    X, tree = _cloud_and_tree(N, d)
+    rows = np.random.default_rng(d).choice(N, 400, replace=False)
+    D, NN = tree.query(X[rows], k=k + 1)
+    for f32 in (0, 2, 1):
+        ctx.set_option("knn_f32", f32)
+        try:
+            W, sg, info = engine.knn_graph(X, k, ctx=ctx, neighbors=True)
+            st = _search_stats(ctx, X, k)
+        finally:
+            ctx.set_option("knn_f32", 1)
+        np.testing.assert_array_equal(info["NN"][rows], NN[:, 1:])
+        np.testing.assert_array_equal(info["D"][rows], D[:, 1:])       # bit for bit
+        assert abs(W - W.T).max() == 0
+        assert st["sample"] == 2048 and st["capacity"] == {8: 129, 16: 257, 32: 513, 64: 1025}[k], (f32, st)
+        assert st["exact_scans"] <= N // 1000 and k <= st["mean_candidates"] <= st["capacity"], (f32, st)
 
 
 def test_highdim_clustered_ties_and_other_metrics(ctx):

@@ -85,7 +85,7 @@ def test_wide_oracle(ctx, N, d, k):
 
 @pytest.mark.parametrize("d", [96, 160])
 def test_wide_two_sweeps(ctx, d):
-    """8192 points: a sample of 2048 (stride 4), every second tile in the first sweep, k_bf_refine in between,
+    """8192 points: a sample of 2048 (stride 4), every second tile in the first sweep, the refinement stage in between,
     capacity 161 - about 31 candidates per query, at most 69 (numpy emulation of the plan)."""
     N, k = 8192, 10
     X = cloud(N, d)

@@ -29,6 +29,8 @@ struct Options {
   int64_t copy_threads = 0;       // host threads of a staged copy (0: 8)
   int64_t tile_regroup = 1;     // 1: rows of 3 / 5 / 6 / 7 / 10 / 12 / 14 sixteen-byte pieces run the builds whose compute
                                 // phases regroup the lanes by pieces (k_step_tile<..., CL>); 0: the power-of-two builds
+  int64_t tile_acc_builds = 1;  // 1: steps without a flush run the flush-free builds of k_step_tile (ACC = false: no
+                                // accumulator registers or loads, no flush formed; the same bits); 0: the general build
   int64_t tile_lg = 0;          // lanes per row of the narrow builds: 0 by row size (1 / 2 / 4 / 8); 2, 4 or 8: at least that
   int64_t edge_vertex_walk = 1; // grad / div walk the vertices in the internal order (k_grad_v / k_div_v); 0: edge order
   int64_t fuse_input = 1;       // 1: k_step_tile reads the caller's panel directly in steps 1-2 (no permute-in copy)
@@ -323,6 +325,7 @@ static const OptionDef OPTION_TABLE[] = {
     {"tile_workgroups", &Options::tile_workgroups, nullptr, nullptr},
     {"tile_lg", &Options::tile_lg, nullptr, nullptr},
     {"tile_regroup", &Options::tile_regroup, nullptr, nullptr},
+    {"tile_acc_builds", &Options::tile_acc_builds, nullptr, nullptr},
     {"staged_copy", &Options::staged_copy, nullptr, nullptr},
     {"staged_copy_min_mb", &Options::staged_copy_min_mb, nullptr, nullptr},
     {"copy_threads", &Options::copy_threads, nullptr, nullptr},

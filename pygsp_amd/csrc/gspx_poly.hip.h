@@ -382,6 +382,16 @@ static int launch_step_tile(gspx_graph* g, const Options& opt, TileArgs<T> t, un
        k_step_tile<T, 1, 4, false, true, 256>, k_step_tile<T, 1, 8, false, true>}};
   kern_t kern = narrow ? slim[flavour][lg == 1 ? 0 : lg == 2 ? 1 : lg == 4 ? 2 : 3] : wide[flavour][ncol <= 2 ? ncol : 0];
   unsigned threads = narrow ? 64u * (unsigned)lg : 512u;
+  // a step without a flush (every step of a Newton or product program and of a deferred combine; 18 of the 30 steps of
+  // the headline call): the flush-free builds of the wide plain flavour (gspx_tile_kernels.hip.h, ACC = false) - the
+  // same T_k, bit for bit.  (Synthesis steps, the narrow and the regrouped builds have none: not measured.)
+  const bool noacc = opt.tile_acc_builds && t.flush == 0 && !narrow && flavour == 0;
+  if (noacc) {
+    static const kern_t freek[3] = {k_step_tile<T, 0, 16, false, false, 512, 16, 0, false>,
+                                    k_step_tile<T, 1, 16, false, false, 512, 16, 0, false>,
+                                    k_step_tile<T, 2, 16, false, false, 512, 16, 0, false>};
+    kern = freek[ncol <= 2 ? ncol : 0];
+  }
   // calibration (gspx_bench_step_mix): the same launch with the row products removed (gspx_tile_kernels.hip.h, MIX)
   bool mix = false;
   if (opt.calib_mix && !narrow && flavour == 0) {
@@ -390,7 +400,13 @@ static int launch_step_tile(gspx_graph* g, const Options& opt, TileArgs<T> t, un
          k_step_tile<T, 2, 16, false, false, 512, 16, 1>},
         {k_step_tile<T, 0, 16, false, false, 512, 16, 2>, k_step_tile<T, 1, 16, false, false, 512, 16, 2>,
          k_step_tile<T, 2, 16, false, false, 512, 16, 2>}};
-    kern = mixk[opt.calib_mix == 2 ? 1 : 0][ncol <= 2 ? ncol : 0];
+    // (the same split as the real launches: a flush-free step is calibrated against its flush-free twin)
+    static const kern_t mixfree[2][3] = {
+        {k_step_tile<T, 0, 16, false, false, 512, 16, 1, false>, k_step_tile<T, 1, 16, false, false, 512, 16, 1, false>,
+         k_step_tile<T, 2, 16, false, false, 512, 16, 1, false>},
+        {k_step_tile<T, 0, 16, false, false, 512, 16, 2, false>, k_step_tile<T, 1, 16, false, false, 512, 16, 2, false>,
+         k_step_tile<T, 2, 16, false, false, 512, 16, 2, false>}};
+    kern = (noacc ? mixfree : mixk)[opt.calib_mix == 2 ? 1 : 0][ncol <= 2 ? ncol : 0];
     mix = true;
   }
   // rows of fewer 16-byte pieces than the lanes they are staged with: the builds whose compute phases regroup the

@@ -83,11 +83,22 @@ constexpr int GSPX_TILE_MAXN1 = 160;  // S1 rows a workgroup stages (5 per group
 // -0.8 ... -1.4 %: the previous build did not wait for a wave's own tile at all (see the first barrier below).
 // The OLDNAT builds (one launch per call) keep the plain order and a full wait.
 // Narrow panels (8-lane groups) issue the tile first and wait for everything: measured better there.
-template <typename T, int NCOL, int LG, bool OLDNAT> struct TileSchedule {
+//   EARLY_OLD   (a flush-free build, ACC = false) the NEXT pass's T_{k-2} rows are requested right after the first
+//               barrier of a pass, into a second register set: in flight during the row products, when a workgroup
+//               otherwise has nothing outstanding, and out of the tile DMA's way after the second barrier.  The next
+//               pass is the next chunk of this block or chunk 0 of the workgroup's next block; either way its row
+//               numbers follow from the walk alone (no row list).  Measured on one box against the flush-free build
+//               WITHOUT it, all six wide builds (profiles/flushfree_step.md): it loses 2 - 6 % of a call to the
+//               plain flush-free build everywhere but on the product form (+0.6 ... 1.3 %), so only the one build takes it
+//               whose plain flush-free form does not fit the register budget (fp32, two chunks: 128 VGPRs and 16 bytes
+//               of scratch; with the early request 121 and none).  Requesting a new block's entry slice there too
+//               measured no better in any build: not kept.
+template <typename T, int NCOL, int LG, bool OLDNAT, bool ACC = true> struct TileSchedule {
   static constexpr bool PF = !OLDNAT;
   static constexpr bool TILE_LAST = PF && LG == 16;
   static constexpr bool PF_ENTRIES = PF;  // (leaving the entries with their own pass measured 2-3 % slower)
   static constexpr bool META_AFTER = !OLDNAT && LG == 16 && NCOL == 0;
+  static constexpr bool EARLY_OLD = !ACC && PF && LG == 16 && NCOL == 2 && sizeof(T) == 4;
 };
 
 // INS: the step adds extra input panels to the row (synthesis by Clenshaw, a.nin > 0) - its own build, so
@@ -110,18 +121,26 @@ template <typename T, int NCOL, int LG, bool OLDNAT> struct TileSchedule {
 // replaced by one tile read per row.  1: both barriers of a pass kept (what the memory system delivers to this
 // access mix behind this synchronisation); 2: the barriers dropped too (the access mix alone; tile rows may be read
 // while still arriving - the values mean nothing in either build).
+// ACC = false (the flush-free builds): a.flush == 0 by contract (launch_step_tile) - every step of a Newton or product
+// program, every step of a deferred combine, and the steps of a fused single-filter call between two flushes.  No
+// accumulator rows (no resource descriptor, no loads - a poisoned load is still a VMEM instruction and still counts in
+// vmcnt), no flush formed or stored: 8 - 10 registers fewer across the barrier wait, one kind of load fewer in the
+// queue in front of the tile DMA.  T_k is the general build's, bit for bit.
 template <typename T, int NCOL, int LG = 16, bool OLDNAT = false, bool INS = false, int NT = 512, int CL = LG,
-          int MIX = 0>
+          int MIX = 0, bool ACC = true>
 __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
   static_assert(NT == 512 || (NT == 64 * LG && NCOL == 1) || (CL < LG && NCOL == 1 && NT % 64 == 0 && NT % CL == 0),
                 "narrow builds: one row per group, one chunk per row");
   constexpr int BR = GSPX_TILE_BR;
   static_assert(CL <= LG && (BR % (NT / CL)) == 0, "compute groups must tile the block's rows");
   constexpr int MAXN1 = GSPX_TILE_MAXN1;
-  constexpr bool PF = TileSchedule<T, NCOL, LG, OLDNAT>::PF;
-  constexpr bool META_AFTER = TileSchedule<T, NCOL, LG, OLDNAT>::META_AFTER;
-  constexpr bool TILE_LAST = TileSchedule<T, NCOL, LG, OLDNAT>::TILE_LAST;
-  constexpr bool PF_ENTRIES = TileSchedule<T, NCOL, LG, OLDNAT>::PF_ENTRIES;
+  typedef TileSchedule<T, NCOL, LG, OLDNAT, ACC> Sched;
+  constexpr bool PF = Sched::PF;
+  constexpr bool META_AFTER = Sched::META_AFTER;
+  constexpr bool TILE_LAST = Sched::TILE_LAST;
+  constexpr bool PF_ENTRIES = Sched::PF_ENTRIES;
+  constexpr bool EARLY_OLD = Sched::EARLY_OLD;
+  static_assert(ACC || (!OLDNAT && !INS && CL == LG), "flush-free builds: the plain flavour only");
   constexpr int VEC = 16 / (int)sizeof(T);
   typedef typename VT<T, VEC>::t V;
   typedef __attribute__((address_space(3))) void* lds_ptr;
@@ -205,11 +224,12 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
   // accumulator) of the group's rows, and - for the first pass of a block - the block's slice of matrix
   // entries.  By the time the pass reaches its first barrier they are as old as the tile loads, so the
   // barrier does not expose a fresh memory round trip every pass.
-  V ov[RPG], ra[RPG];
+  V ov[RPG], ra[ACC ? RPG : 1];
+  V ov2[EARLY_OLD ? RPG : 1];  // EARLY_OLD: the set the next pass's T_{k-2} rows arrive in (the sets swap every pass)
   u32x4 ev[NE], ei = 0;
 #pragma unroll
   for (int q = 0; q < NE; ++q) ev[q] = 0;
-  auto prefetch_rows = [&](const Meta& m, int blk, int c) {
+  auto prefetch_rows = [&](const Meta& m, int blk, int c, V (&dst)[RPG]) {
     const int r0 = phys(blk) * BR + grp * RPG;
     const u32 cb = chunk_off(c);
 #pragma unroll
@@ -217,11 +237,13 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
       const u32 off = (r0 + t < a.N && cb != POISON) ? (u32)(r0 + t) * ldb + cb : POISON;
       u32 oo = a.gamma != T(0) ? off : POISON;
       if constexpr (OLDNAT) oo = (off != POISON && a.gamma != T(0)) ? (u32)m.orow[t] * ldb + cb : POISON;
-      if (a.nt & 4) ov[t] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rold, oo, 0, 2));
-      else ov[t] = VT<T, VEC>::bload(rold, oo);
-      const u32 ro = a.flush == 2 ? off : POISON;
-      if (a.nt & 2) ra[t] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rra, ro, 0, 2));
-      else ra[t] = VT<T, VEC>::bload(rra, ro);
+      if (a.nt & 4) dst[t] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rold, oo, 0, 2));
+      else dst[t] = VT<T, VEC>::bload(rold, oo);
+      if constexpr (ACC) {
+        const u32 ro = a.flush == 2 ? off : POISON;
+        if (a.nt & 2) ra[t] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(rra, ro, 0, 2));
+        else ra[t] = VT<T, VEC>::bload(rra, ro);
+      }
     }
   };
   auto prefetch_entries = [&](const int4& h) {  // the block's slice of matrix entries, coalesced 16-byte pieces
@@ -247,7 +269,13 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
   if constexpr (!TILE_LAST) {
     if (H.y >= 0) stage(M, H.y, chunk_off_d(0));
   }
-  if constexpr (PF) prefetch_rows(M, k0, 0);
+  if constexpr (EARLY_OLD) {  // gamma == 0 (step 1, gather-and-write steps): no T_{k-2} load at all, both sets stay 0
+#pragma unroll
+    for (int t = 0; t < RPG; ++t) ov[t] = 0, ov2[t] = 0;
+    if (a.gamma != T(0)) prefetch_rows(M, k0, 0, ov);
+  } else if constexpr (PF) {
+    prefetch_rows(M, k0, 0, ov);
+  }
   if constexpr (PF_ENTRIES) {
     if (H.y >= 0) prefetch_entries(H);
   }
@@ -258,7 +286,9 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
   }
 
   // one pass = column chunk c of block k; returns false after the workgroup's last pass
-  auto pass = [&](const int c, const bool first, const bool last) __attribute__((always_inline)) {
+  // ovc: the T_{k-2} rows this pass consumes; ovn: where the next pass's arrive (the same set unless EARLY_OLD)
+  auto pass = [&](const int c, const bool first, const bool last, V (&ovc)[RPG], V (&ovn)[RPG])
+                  __attribute__((always_inline)) {
     const int n1 = H.y, rp0 = H.z, ent = H.w;
     const bool fast = n1 >= 0;
     T* const mval = (T*)(tile + (fast ? n1 : 0) * LG);
@@ -270,7 +300,7 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
     const u32 col0 = (c * LG + lane16) * VEC;
     const bool on = col0 < a.ld;
     const u32 cb = on ? col0 * (u32)sizeof(T) : POISON;
-    if constexpr (!PF) prefetch_rows(M, k, c);
+    if constexpr (!PF) prefetch_rows(M, k, c, ovc);
     V ins[INS ? RPG : 1];
 #pragma unroll
     for (int t = 0; t < (INS ? RPG : 1); ++t) ins[t] = 0;
@@ -317,7 +347,11 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
     if constexpr (TILE_LAST && !META_AFTER) {
       // the tile DMA was the last thing issued one pass ago; the only VMEM operations younger than it are the
       // NMETA loads of the next block's row lists / header issued above in a block's last pass (and the extra
-      // input panels of a synthesis step, which make the count data dependent: full wait then)
+      // input panels of a synthesis step, which make the count data dependent: full wait then).
+      // EARLY_OLD, re-derived: what the previous pass requested after ITS first barrier (this pass's T_{k-2} rows)
+      // was issued before that pass's stores and tile DMA - it is OLDER than the DMA, so the wait covers it, and in
+      // a block's last pass the NMETA youngest operations are still exactly the row lists and the header: the
+      // count does not change.
       constexpr int NMETA = ST + RPG + 1 + 1;
       static_assert(NMETA < 16, "vmcnt immediate");
       // (entries loaded in this pass were issued before the row lists: they are older, hence covered)
@@ -333,8 +367,15 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
         Hv = load_hdr(knn < k1 ? knn : k);
       }
     }
+    if constexpr (EARLY_OLD) {
+      // the next pass's T_{k-2} rows: in flight during the row products.  The workgroup's very last pass requests
+      // nothing; gamma == 0: nothing to read (wave-uniform).  The rows are this thread's own rows of the next pass -
+      // T_k overwrites T_{k-2} in place, and the thread that reads a piece here is the one that stores it one pass
+      // later.
+      if ((!last || kn < k1) && a.gamma != T(0)) prefetch_rows(M, last ? kn : k, last ? 0 : c + 1, ovn);
+    }
     __builtin_amdgcn_sched_barrier(0);
-    V nv[RPG], res[RPG];
+    V nv[RPG], res[ACC ? RPG : 1];
 #pragma unroll
     for (int t = 0; t < RPG; ++t) {
       const int s = rs[t], e = rs[t + 1];
@@ -353,12 +394,22 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
           acc += a.val[j] * xv;
         }
       }
-      nv[t] = a.scale * acc + a.gamma * ov[t] + a.beta * self;
+      if constexpr (ACC) {
+        nv[t] = a.scale * acc + a.gamma * ovc[t] + a.beta * self;
+      } else {
+        // the same three roundings as the general builds, spelled out: there the compiler contracts the line above to
+        // fma(beta, self, fma(gamma, ov, scale * acc)); in a build without the flush beside it, it picked gamma * ov
+        // as the product that is rounded on its own - another last bit whenever beta and gamma are both at work
+        // (the Newton form)
+        nv[t] = __builtin_elementwise_fma((V)a.beta, self, __builtin_elementwise_fma((V)a.gamma, ovc[t], a.scale * acc));
+      }
       if constexpr (INS) nv[t] += ins[t];
       // the flush is formed here, while T_{k-1} (self) and T_{k-2} (ov) are at hand: after the barrier
       // their registers receive the next pass's rows
-      res[t] = a.wn * nv[t] + a.wc * self + a.wo * ov[t];
-      if (a.flush == 2) res[t] += ra[t];
+      if constexpr (ACC) {
+        res[t] = a.wn * nv[t] + a.wc * self + a.wo * ovc[t];
+        if (a.flush == 2) res[t] += ra[t];
+      }
     }
     // everybody is done with the tile (their LDS reads were consumed above).  A bare barrier: the
     // fence of __syncthreads() would also wait for the prefetches still in flight.
@@ -381,20 +432,22 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
     for (int t = 0; t < RPG; ++t) {
       const int row = row0 + t;
       if (row < a.N && on) {
-        if (a.final && !a.flush) {  // Newton form: the last step's result is the output
+        if (a.final && (!ACC || !a.flush)) {  // Newton form: the last step's result is the output
           const size_t orow = a.perm ? (size_t)a.perm[row] : (size_t)row;
           *(V*)(a.y + orow * a.ldy + col0) = nv[t];
           continue;
         }
         if (a.nt & 8) __builtin_nontemporal_store(nv[t], (V*)(a.out + (size_t)row * a.ld + col0));
         else *(V*)(a.out + (size_t)row * a.ld + col0) = nv[t];
-        if (a.flush) {
-          if (a.final) {
-            const size_t orow = a.perm ? (size_t)a.perm[row] : (size_t)row;
-            *(V*)(a.y + orow * a.ldy + col0) = res[t];
-          } else {
-            if (a.nt & 2) __builtin_nontemporal_store(res[t], (V*)(a.racc + (size_t)row * a.ld + col0));
-            else *(V*)(a.racc + (size_t)row * a.ld + col0) = res[t];
+        if constexpr (ACC) {
+          if (a.flush) {
+            if (a.final) {
+              const size_t orow = a.perm ? (size_t)a.perm[row] : (size_t)row;
+              *(V*)(a.y + orow * a.ldy + col0) = res[t];
+            } else {
+              if (a.nt & 2) __builtin_nontemporal_store(res[t], (V*)(a.racc + (size_t)row * a.ld + col0));
+              else *(V*)(a.racc + (size_t)row * a.ld + col0) = res[t];
+            }
           }
         }
       }
@@ -408,7 +461,7 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
         if constexpr (!TILE_LAST) {
           if (H.y >= 0) stage(M, H.y, chunk_off_d(nc));
         }
-        prefetch_rows(M, last ? kn : k, nc);
+        if constexpr (!EARLY_OLD) prefetch_rows(M, last ? kn : k, nc, ovn);
         if constexpr (PF_ENTRIES) {
           if (last && H.y >= 0) prefetch_entries(H);
         }
@@ -426,16 +479,24 @@ __global__ __launch_bounds__(NT, 4) void k_step_tile(const TileArgs<T> a) {
     }
     return more;
   };
-  for (;;) {
-    if constexpr (NCOL == 1) {
-      if (!pass(0, true, true)) break;
-    } else if constexpr (NCOL == 2) {
-      pass(0, true, false);
-      if (!pass(1, false, true)) break;
-    } else {
-      bool more = true;
-      for (int c = 0; c < a.ncol; ++c) more = pass(c, c == 0, c == a.ncol - 1);
-      if (!more) break;
+  if constexpr (EARLY_OLD) {  // the two T_{k-2} sets swap roles every pass: no moves (a two-chunk build only)
+    static_assert(NCOL == 2, "an even number of passes per block");
+    for (;;) {
+      pass(0, true, false, ov, ov2);
+      if (!pass(1, false, true, ov2, ov)) break;
+    }
+  } else {
+    for (;;) {
+      if constexpr (NCOL == 1) {
+        if (!pass(0, true, true, ov, ov)) break;
+      } else if constexpr (NCOL == 2) {
+        pass(0, true, false, ov, ov);
+        if (!pass(1, false, true, ov, ov)) break;
+      } else {
+        bool more = true;
+        for (int c = 0; c < a.ncol; ++c) more = pass(c, c == 0, c == a.ncol - 1, ov, ov);
+        if (!more) break;
+      }
     }
   }
 }

@@ -373,6 +373,16 @@ int gspx_identity_panel_dev(gspx_ctx* ctx, int dtype, int64_t N, int64_t j0, int
  * compute_spectrogram) without the frame. */
 int gspx_cheby_sqnorms_dev(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs, int64_t Nsig,
                            const void* x_dev, double* out, double* kernel_ms);
+/* Chebyshev self-moments of DEVICE signals: out (HOST, M x Nsig fp64, row-major)
+ *   out[k][j] = sum_n x[n][j] * (T_k(Lt) x)[n][j],  Lt = (L - a I)/a, a = lmax/2 (approximations.py:93-99), k < M.
+ * x_dev as for gspx_cheby_filter_dev (N x Nsig, row-major, the graph's compute dtype, the caller's vertex order);
+ * 2 <= M <= 2048.  L is symmetric, so T_i T_j = (T_{i+j} + T_{|i-j|}) / 2 yields M moments from floor(M / 2)
+ * recurrence steps: the inner products <T_i, T_i> and <T_{i+1}, T_i> of the kept T_0 .. T_{floor(M/2)} are formed
+ * in fp64 for both graph dtypes (k_slot_dots) and doubled on the host.  Identical calls give identical bits.  The
+ * moments of random +-1 vectors are the kernel polynomial method's estimate of the density of states
+ * (pygsp_amd.spectrum).  Nsig == 0: nothing happens; N == 0: zeros. */
+int gspx_cheby_moments_dev(gspx_graph* g, double lmax, int M, int64_t Nsig, const void* x_dev,
+                           double* out, double* kernel_ms);
 
 /* PCI address ("0000:c1:00.0", NUL-terminated) of HIP device `device`: what a host driver needs to find the NUMA
  * node the GPU hangs off (/sys/bus/pci/devices/<address>/numa_node) and pin the thread - and the packing threads

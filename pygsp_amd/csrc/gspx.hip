@@ -9,6 +9,8 @@
 // builders (on gspx_kernels.hip.h)
 #include "gspx_kernels.hip.h"
 #include "gspx_tile_kernels.hip.h"
+// the inner products of kept slots: Chebyshev self-moments (on gspx_kernels.hip.h)
+#include "gspx_moments.hip.h"
 // (The kernels that measured slower than what runs by default - two recurrence orders per launch, the fused Newton
 // pair, the small pair kernel, 128-row blocks - were retired in round 6; their counter-backed records are
 // profiles/r04_pair_experiment.md, profiles/r05_pair_experiment.md and profiles/r05_narrow_rows.md.)

@@ -1,8 +1,8 @@
 // gspx_poly.hip.h - the polynomial-filter pipeline (replaces approximations.py:58-114 cheby_op and the synthesis loop of
 // filter.py:313-322): step plans, launch shapes and the launch_* family, the work panels of a batch, the column-batch
 // driver (batch_width, run_batches), the three batch runners (run_batch, run_synthesis_batch, run_program_batch),
-// filter_dev_t / program_dev_t / sqnorms_dev_t, device_call / host_call and the gspx_cheby_* / gspx_newton_* /
-// gspx_poly_program* entry points.
+// filter_dev_t / program_dev_t / sqnorms_dev_t / moments_dev_t, device_call / host_call and the gspx_cheby_* /
+// gspx_newton_* / gspx_poly_program* entry points.
 // After gspx_graph.hip.h (ensure_factor, ensure_s1nat) and gspx_hostpipe.hip.h (host_call hands large calls to it).
 #pragma once
 
@@ -331,6 +331,56 @@ static int launch_combine_sqnorm(gspx_ctx* ctx, const T* slots, int nslots, size
   return GSPX_OK;
 }
 
+// The inner products of neighbouring kept slots of a deferred batch instead of its outputs (gspx_cheby_moments_dev):
+// out [2 S - 1][ldo] fp64 at the batch's first column (a_0 .. a_{S-1}, then b_0 .. b_{S-2}: k_slot_dots,
+// gspx_moments.hip.h), part the workgroup partials (dots_parts doubles at the call's widest batch).
+struct SlotDots {
+  double* out;
+  size_t ldo;
+  double* part;
+};
+// the two builds of k_slot_dots: one column per lane in chunks of 16 slots; two columns per lane in chunks of 8 (the
+// same registers) for fp32 panels whose rows split into pairs
+static const int DOTS_CS[2] = {16, 8};
+template <typename T> static int dots_vec(unsigned w, unsigned pitch) {
+  return sizeof(T) == 4 && w % 2 == 0 && pitch % 2 == 0 ? 2 : 1;
+}
+static int dots_chunks(int S, int vec) { return (S - 1 + DOTS_CS[vec - 1] - 1) / DOTS_CS[vec - 1]; }  // grid.y, S >= 2
+// row groups of a k_slot_dots launch: about eight workgroups per CU over all chunks and column blocks, no more than
+// there are tiles of four waves, and at most 64 MiB of partials.  A function of N, w, S, the build and the CU count.
+static int dots_gx(const gspx_ctx* ctx, int N, unsigned w, int S, int vec) {
+  const int cwl = sqnorm_cwl(w / vec);
+  const int64_t rows = 4 * (int64_t)(64 >> cwl);
+  const int64_t tiles = ((int64_t)N + rows - 1) / rows;
+  const int64_t others = (((int64_t)(w / vec) + (1 << cwl) - 1) >> cwl) * dots_chunks(S, vec);
+  const int64_t fit = ((int64_t)64 << 20) / ((int64_t)(2 * S - 1) * w * (int64_t)sizeof(double));
+  const int64_t want = (8 * (int64_t)ctx->cu_count + others - 1) / others;
+  return (int)std::max<int64_t>(1, std::min(std::min(tiles, want), fit));
+}
+static size_t dots_parts(const gspx_ctx* ctx, int N, unsigned w, int S) {  // (whichever build a batch takes)
+  const int gx = std::max(dots_gx(ctx, N, w, S, 1), w % 2 == 0 ? dots_gx(ctx, N, w, S, 2) : 0);
+  return (size_t)gx * (size_t)(2 * S - 1) * w;
+}
+
+template <typename T>
+static int launch_slot_dots(gspx_ctx* ctx, const T* slots, int S, size_t slot_stride, unsigned pitch, int N, unsigned w,
+                            const SlotDots& sd, hipStream_t st) {
+  const int vec = dots_vec<T>(w, pitch);
+  const int cwl = sqnorm_cwl(w / vec);
+  const int gx = dots_gx(ctx, N, w, S, vec);
+  const dim3 grid((unsigned)gx, (unsigned)dots_chunks(S, vec), (w / vec + (1u << cwl) - 1) >> cwl);
+  typedef void (*kern_t)(const T*, int, size_t, u32, int, int, int, double*);
+  kern_t kern = k_slot_dots<T, 1, 16>;
+  if constexpr (sizeof(T) == 4) {
+    if (vec == 2) kern = k_slot_dots<T, 2, 8>;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, slots, S, slot_stride, (u32)pitch, N, (int)w, cwl, sd.part);
+  const int64_t n = (int64_t)(2 * S - 1) * w;
+  hipLaunchKernelGGL(k_dots_reduce, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, sd.part, gx, n, (int)w, sd.out,
+                     sd.ldo);
+  return GSPX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the filter
 // ------------------------------------------------------------------------------------------------
@@ -605,7 +655,8 @@ static int run_batches(gspx_graph* g, int64_t Nsig, int64_t width, int steps, co
 template <typename T>
 static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp, const T* x,
                      unsigned ldx, T* y, unsigned ldy, unsigned ld, bool deferred,
-                     bool acc_existing, bool final_to_y, size_t& ev_idx, const SqNorms* sq = nullptr) {
+                     bool acc_existing, bool final_to_y, size_t& ev_idx, const SqNorms* sq = nullptr,
+                     const SlotDots* sd = nullptr) {
   gspx_ctx* ctx = g->ctx;
   const Options& opt = ctx->opt;
   hipStream_t st = ctx->stream;
@@ -740,6 +791,8 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
   if (!cap) HIPCHK(hipEventRecord(ev[2], st));
   if (deferred && sq) {  // the squared column norms in place of the outputs (rows in any order: no perm)
     CHK(launch_combine_sqnorm<T>(ctx, slots, M, SU, ldw, N, ld, *sq, st));
+  } else if (deferred && sd) {  // the slots' inner products in place of the outputs (likewise)
+    CHK(launch_slot_dots<T>(ctx, slots, M, SU, ldw, N, ld, *sd, st));
   } else if (deferred) {
     launch_combine<T>(slots, M, SU, ctx->ws_w.as<T>(), M, nf, N, ld, y, ldy, (size_t)N * ldy, perm,
                       padded ? 1 : vec_cap(shape.vec, ldy, y), st, ldw);
@@ -1336,6 +1389,70 @@ extern "C" int gspx_cheby_sqnorms_dev(gspx_graph* g, double lmax, int Nf, int M,
   if (Nsig > 0 && !out) return set_err(GSPX_ERR_INVALID, "gspx_cheby_sqnorms_dev: null output");
   return device_call(g, Nsig, x_dev, out, kernel_ms, [&](auto x, auto, int64_t n) {
     return sqnorms_dev_t(g, lmax, Nf, M, coeffs, n, x, out);
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Chebyshev self-moments of device signals (pygsp_amd.spectrum: density of states, eigenvalue counts):
+//     out[k][j] = x_j^T T_k(Lt) x_j,  k < M.
+// L is symmetric, so T_i T_j = (T_{i+j} + T_{|i-j|}) / 2 gives  m_{2i} = 2 <T_i, T_i> - m_0  and
+// m_{2i+1} = 2 <T_{i+1}, T_i> - m_1:  S = M / 2 + 1 kept slots, S - 1 recurrence steps instead of M - 1.  Per column
+// batch the deferred plan of ONE filter with S slots, then k_slot_dots over the kept slots in place of k_combine; the
+// 2 S - 1 dot rows come back in one download and the doubling is fp64 host arithmetic.  out: HOST, M x Nsig.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+static int moments_dev_t(gspx_graph* g, double lmax, int M, int64_t Nsig, const T* x, double* out) {
+  gspx_ctx* ctx = g->ctx;
+  const int64_t N = g->N;
+  for (int i = 0; i < 5; ++i) ctx->timing[i] = 0;
+  ctx->step_kinds[0] = ctx->step_kinds[1] = 0;
+  if (Nsig == 0) return GSPX_OK;
+  if (N == 0) {
+    std::fill(out, out + (size_t)M * Nsig, 0.0);
+    return GSPX_OK;
+  }
+  const int S = M / 2 + 1, rows = 2 * S - 1;
+  int64_t width = 0;
+  CHK(batch_width(g, sizeof(T), (size_t)S, Nsig, &width));
+  const std::vector<double> cp((size_t)S, 0.0);  // (the deferred plan uploads its filter's coefficients; none are read)
+  const size_t obytes = (size_t)rows * Nsig * sizeof(double);
+  const int64_t first = std::min<int64_t>(width, Nsig), last = Nsig - (Nsig - 1) / width * width;
+  const size_t parts =
+      std::max(dots_parts(ctx, (int)N, (unsigned)first, S), dots_parts(ctx, (int)N, (unsigned)last, S));
+  CHK(ctx->ws_sq.ensure(obytes + 256));
+  CHK(ctx->ws_sqp.ensure(parts * sizeof(double) + 256));
+  hipStream_t st = ctx->stream;
+  CHK(ensure_factor<T>(g, lmax));
+  double* outd = ctx->ws_sq.as<double>();
+  CHK(run_batches(g, Nsig, width, S - 1, [&](int64_t c0, unsigned ld, size_t& ev_idx) -> int {
+    const SlotDots b{outd + c0, (size_t)Nsig, ctx->ws_sqp.as<double>()};
+    return run_batch<T>(g, 1, S, cp, x + c0, (unsigned)Nsig, (T*)nullptr, ld, ld, true, false, false, ev_idx, nullptr,
+                        &b);
+  }));
+  std::vector<double> d((size_t)rows * Nsig);
+  HIPCHK(hipMemcpyAsync(d.data(), outd, obytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const double *a = d.data(), *b = d.data() + (size_t)S * Nsig;  // a_i = <T_i, T_i>, b_i = <T_{i+1}, T_i>
+  for (int k = 0; k < M; ++k)
+    for (int64_t j = 0; j < Nsig; ++j) {
+      const double dot = (k & 1 ? b : a)[(size_t)(k / 2) * Nsig + j];
+      out[(size_t)k * Nsig + j] = k < 2 ? dot : 2.0 * dot - (k & 1 ? b : a)[j];
+    }
+  return GSPX_OK;
+}
+
+extern "C" int gspx_cheby_moments_dev(gspx_graph* g, double lmax, int M, int64_t Nsig, const void* x_dev, double* out,
+                                      double* kernel_ms) {
+  if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
+  if (M < 2 || M > 2048) return set_err(GSPX_ERR_INVALID, "gspx_cheby_moments_dev: 2 to 2048 moments (got %d)", M);
+  if (Nsig < 0) return set_err(GSPX_ERR_INVALID, "negative number of signals");
+  if (!(lmax > 0.0) || !std::isfinite(lmax))
+    return set_err(GSPX_ERR_INVALID, "lmax must be positive and finite (got %g)", lmax);
+  if (Nsig > 0 && (!out || (g->N > 0 && !x_dev))) return set_err(GSPX_ERR_INVALID, "null signal pointer");
+  if (Nsig >= ((int64_t)1 << 31) / 16) return set_err(GSPX_ERR_INVALID, "too many signals");
+  replay_reset(g->ctx);  // (the kept slots overwrite the panels a recorded filter call replays from)
+  return device_call(g, Nsig, x_dev, out, kernel_ms, [&](auto x, auto, int64_t n) {
+    return moments_dev_t(g, lmax, M, n, x, out);
   });
 }
 

@@ -1000,6 +1000,25 @@ class DeviceGraph:
                       ctypes.c_void_p(x_ptr), _capi.ptr(out), ctypes.byref(ms))
         return out, ms.value
 
+    def cheby_moments_dev(self, x_ptr, nsig, lmax, M):
+        """Chebyshev self-moments of the device signals at x_ptr (N x nsig): ((M, nsig) float64 host array of
+        x_j^T T_k(Lt) x_j for k < M, device milliseconds of the call) from M // 2 recurrence steps
+        (gspx_cheby_moments_dev)."""
+        out = np.zeros((int(M), int(nsig)))
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_cheby_moments_dev, self._h, float(lmax), int(M), int(nsig),
+                      ctypes.c_void_p(x_ptr), _capi.ptr(out), ctypes.byref(ms))
+        return out, ms.value
+
+    def cheby_moments(self, x, lmax, M):
+        """cheby_moments_dev of a host array (N, nsig): uploaded in the graph's dtype, freed afterwards."""
+        x = self._signals(x)
+        with self.ctx._temporaries() as t:
+            bx = t.alloc(x.nbytes)
+            if x.nbytes:
+                bx.upload(x)
+            return self.cheby_moments_dev(bx.ptr, x.shape[1], lmax, M)
+
     def tune_placement(self, coeffs, x_ptr, y_ptr, nsig, lmax, candidates=6, stride_mb=0):
         """Draw `candidates` physical backings for the context's streamed workspaces and keep the one on which THIS call
         (the arguments of cheby_filter_dev, one filter) runs fastest (gspx_ctx_tune_placement; on MI355X the same call

@@ -587,6 +587,18 @@ class Graph:
             candidates.append(np.max(deg + W.dot(deg) / deg))
         return min(candidates)
 
+    # ---- where the eigenvalues lie, without a basis (spectrum.py) ---------------------------------
+    def estimate_spectral_density(self, order=100, n_vectors=32, seed=0, damping="jackson"):
+        """The density of states of L by the kernel polynomial method: a spectrum.SpectralDensity (cdf, pdf, count,
+        quantile) from the order + 1 Chebyshev moments of `n_vectors` random +-1 vectors - order / 2 recurrence steps
+        on the device, no eigendecomposition.  Uses G.lmax."""
+        from . import spectrum
+        return spectrum.estimate_spectral_density(self, order, n_vectors, seed, damping)
+
+    def count_eigenvalues(self, lo, hi, **kwargs):
+        """The estimated number of eigenvalues of L in (lo, hi]; kwargs: those of estimate_spectral_density."""
+        return self.estimate_spectral_density(**kwargs).count(lo, hi)
+
     def compute_fourier_basis(self, n_eigenvectors=None, *, method="auto", tol=None, maxiter=None, seed=0,
                               degree=(10, 300)):
         """The (partial) Fourier basis of L (fourier.py:97-195), cached in ``G.e`` / ``G.U``.

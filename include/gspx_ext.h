@@ -253,6 +253,28 @@ int gspx_sbm_build_ex(gspx_ctx* ctx, int64_t N, int k, const int32_t* order, con
 int gspx_linegraph_size(gspx_graph* g, int64_t* n_vertices, int64_t* nnz);
 int gspx_linegraph_build(gspx_graph* g, gspx_knn** out, double* kernel_ms);
 
+/* Schur complements of A = L + shift I, shift >= 0 (pygsp/reduction.py: kron_reduction, interpolate).
+ * schur_cg: the harmonic extension of gspx_dirichlet_cg_dev at a shift.  x = f on the kept vertices (mask != 0) and
+ * A_uu x_u = -A_uk f_k on the others, the same conjugate-gradient loop, column batches (<= 256), dtypes (fp32, fp64),
+ * stopping rule and reproducibility.  f_dev (N x Nsig) is read only at kept rows.  x_dev (may be NULL) receives the
+ * extension; alpha_dev (may be NULL) receives (A x) at the kept rows - the Schur complement applied to f_k, K_reg f of
+ * reduction.interpolate - and exact zeros elsewhere, N x Nsig in the caller's vertex order; eliminated rows are not
+ * computed.  With shift == 0, x_dev holds the bytes gspx_dirichlet_cg_dev writes.
+ * kron_build: the Kron reduction A_kk - A_ku A_uu^-1 A_uk for the kept vertices ind_host[0 .. nk) (HOST; any order,
+ * unique and in range: vertex ind[c] becomes vertex c of the result).  fp64 graphs only.  lnew_dev (may be NULL): the
+ * dense nk x nk matrix (DEVICE, row-major), symmetrised as (S + S^T) / 2, diagonal included.  w_out (may be NULL):
+ * W = max(0, -offdiag) as a handle of the kind gspx_linegraph_build returns - canonical CSR, no diagonal, no stored
+ * zero or negative value, equal to its transpose bit for bit, the same bits on every call.  An entry the iteration
+ * never reaches (two kept vertices further apart than its step count) is an exact zero; a direct solve leaves a
+ * value below the tolerance there.  iterations: nk ints (HOST) or NULL.  kernel_ms: the whole device work; after the
+ * call gspx_last_timing holds its parts - [0] the solves, [1] the row products, [2] the finalising pass.  GSPX_ERR_INVALID, with the sizes in the
+ * message, when the nk x nk buffer and the work panels of one batch exceed the context's ws_limit_mb. */
+int gspx_schur_cg_dev(gspx_graph* g, double shift, const void* mask_dev, int64_t Nsig, const void* f_dev, void* x_dev,
+                      void* alpha_dev, double rtol, double atol, int64_t maxiter, int32_t* iterations,
+                      double* kernel_ms);
+int gspx_kron_build(gspx_graph* g, double shift, const int32_t* ind_host, int64_t nk, double rtol, int64_t maxiter,
+                    double* lnew_dev, gspx_knn** w_out, int32_t* iterations, double* kernel_ms);
+
 /* Space-filling-curve keys of N points (coords: N x d doubles on the HOST, d >= 2; the first two /
  * three axes are used): curve 0 = Morton, 1 = Hilbert (2-D).  The engine's internal vertex order
  * for graphs with coordinates is the stable argsort of these keys (pygsp_amd.engine.locality_order). */

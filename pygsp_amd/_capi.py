@@ -141,6 +141,11 @@ SIGNATURES = {
     # line graphs (graphs.LineGraph, engine.line_graph)
     "gspx_linegraph_size": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     "gspx_linegraph_build": (_c.c_int, [_P, _c.POINTER(_P), _c.POINTER(_c.c_double)]),
+    # Schur complements of L + shift I (pygsp_amd/reduction.py)
+    "gspx_schur_cg_dev": (_c.c_int, [_P, _c.c_double, _P, _c.c_int64, _P, _P, _P, _c.c_double, _c.c_double, _c.c_int64,
+                                     _P, _P]),
+    "gspx_kron_build": (_c.c_int, [_P, _c.c_double, _P, _c.c_int64, _c.c_double, _c.c_int64, _P, _c.POINTER(_P), _P,
+                                   _c.POINTER(_c.c_double)]),
     "gspx_radius_build": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_double, _c.c_double, _c.c_int, _P]),
     "gspx_last_timing": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),
     "gspx_last_host_timing": (_c.c_int, [_P, _c.POINTER(_c.c_double)]),

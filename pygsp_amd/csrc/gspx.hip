@@ -84,6 +84,7 @@ extern "C" const char* gspx_version(void) { return "gspx 0.1 (gfx950)"; }
 #include "gspx_sbm.hip.h"         // stochastic block model / Erdos-Renyi sampler                     (on graph, knn)
 #include "gspx_setup.hip.h"       // graph set-up in one call, curve keys and orders                  (on graph, knn)
 #include "gspx_linegraph.hip.h"   // line graphs from the edge tables of grad / div                   (on ops, knn)
+#include "gspx_schur.hip.h"       // Schur complements of L + shift I: schur_cg, Kron reduction     (on ops, knn)
 #include "gspx_components.hip.h"  // connected components                                             (on graph)
 #include "gspx_spectral.hip.h"    // panel Gram / combine / residual norms of the Fourier basis       (on ops)
 #include "gspx_eig.hip.h"         // the full Fourier basis: dense symmetric eigensolver by block Jacobi   (on spectral)

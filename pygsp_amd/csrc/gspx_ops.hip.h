@@ -326,9 +326,55 @@ extern "C" int gspx_tikhonov_cg_dev(gspx_graph* g, double tau, const void* mask_
 // graph's CSR pattern (k_dirichlet_values: P_u L P_u); with r = p = 0 on the measured rows from the start every
 // iterate stays zero there, so cg_iterate runs CG on the block L_uu, which is positive definite on every component
 // that holds a measured vertex.  On a component without one b = 0 and x stays 0.
+//
+// The same frame serves A = L + shift I, shift >= 0 (gspx_schur_cg_dev, gspx_schur.hip.h): the shift sits on the diagonal
+// of the unmeasured rows of the value array, the right-hand side -A_ul y_l = -L_ul y_l is the same, and the measured
+// rows of A x (the Schur complement applied to y_l) leave through schur_kept_rows.  With shift == 0 and no alpha this is
+// gspx_dirichlet_cg_dev, launch for launch.
+template <typename T> struct HarmonicSystem {
+  DevMem mint, aval, scal, partial;  // the mask in the internal order, P_u A P_u, the iteration's scratch
+  T shift = T(0);
+};
+
+// the value array of a system whose mint is in place
+template <typename T> static int harmonic_values(gspx_graph* g, HarmonicSystem<T>& hs) {
+  const int nbN = std::max(1, (int)((g->N + 255) / 256));
+  hipLaunchKernelGGL((k_dirichlet_values<T>), dim3(nbN), dim3(256), 0, g->ctx->stream, g->rptr.as<int>(),
+                     g->rcol.as<int>(), g->rval.as<T>(), (int)g->N, hs.mint.template as<T>(), hs.shift,
+                     hs.aval.template as<T>());
+  return GSPX_OK;
+}
+template <typename T> static int harmonic_alloc(gspx_graph* g, T shift, HarmonicSystem<T>& hs) {
+  hs.shift = shift;
+  CHK(hs.mint.alloc((size_t)g->N * sizeof(T)));
+  CHK(hs.aval.alloc(((size_t)g->nnz_int + 64) * sizeof(T)));
+  HIPCHK(hipMemsetAsync(hs.aval.p, 0, ((size_t)g->nnz_int + 64) * sizeof(T), g->ctx->stream));
+  return GSPX_OK;
+}
+// one column batch: w.B holds y where measured and 0 elsewhere (internal order); leaves the extension in w.X
 template <typename T>
-static int dirichlet_cg_t(gspx_graph* g, const T* mask, int64_t Nsig, const T* y, T* x, double rtol, double atol,
-                          int64_t maxiter, int32_t* iters, double* ms) {
+static int harmonic_solve(gspx_graph* g, HarmonicSystem<T>& hs, const CgPanels<T>& w, unsigned ld, double rtol,
+                          double atol, int64_t maxiter, int32_t* iters) {
+  hipStream_t st = g->ctx->stream;
+  const size_t U = (size_t)g->N * ld;
+  const unsigned nbU = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
+  const T* m = hs.mint.template as<T>();
+  // r = -(L B) on the unmeasured rows
+  CHK(spmm_internal<T>(g, g->rval.as<T>(), T(1), T(0), w.B, w.Q, ld, nullptr, 0));
+  hipLaunchKernelGGL((k_dirichlet_rhs<T>), dim3(nbU), dim3(256), 0, st, m, w.Q, w.R, U, (int)ld);
+  CHK(cg_iterate<T>(g, hs.aval.template as<T>(), w, ld, rtol, atol, maxiter, hs.scal, hs.partial, iters));
+  hipLaunchKernelGGL((k_dirichlet_merge<T>), dim3(nbU), dim3(256), 0, st, m, w.B, w.X, U, (int)ld);
+  return GSPX_OK;
+}
+
+// rows of (L + shift I) X at the measured vertices, X an internal-order panel (gspx_schur.hip.h)
+template <typename T>
+static int schur_kept_rows(gspx_graph* g, T shift, const T* m, const T* X, unsigned ld, const int* orow, bool zero_fill,
+                           T* out, size_t ldo);
+
+template <typename T>
+static int dirichlet_cg_t(gspx_graph* g, T shift, const T* mask, int64_t Nsig, const T* y, T* x, T* alpha, double rtol,
+                          double atol, int64_t maxiter, int32_t* iters, double* ms) {
   gspx_ctx* ctx = g->ctx;
   hipStream_t st = ctx->stream;
   const int64_t N = g->N;
@@ -337,29 +383,24 @@ static int dirichlet_cg_t(gspx_graph* g, const T* mask, int64_t Nsig, const T* y
   const int64_t max_ld = cg_max_ld(g, sizeof(T));
   if (max_ld < 1) return set_err(GSPX_ERR_INVALID, "graph too large: one signal column exceeds 2 GiB");
   const int* perm = g->has_perm ? g->perm.as<int>() : nullptr;
-  const int nbN = std::max(1, (int)((N + 255) / 256));
-  DevMem mint, aval, scal, partial;
-  CHK(mint.alloc((size_t)N * sizeof(T)));
-  CHK(aval.alloc(((size_t)g->nnz_int + 64) * sizeof(T)));
-  HIPCHK(hipMemsetAsync(aval.p, 0, ((size_t)g->nnz_int + 64) * sizeof(T), st));
+  HarmonicSystem<T> hs;
+  CHK(harmonic_alloc<T>(g, shift, hs));
   HIPCHK(hipEventRecord(ctx->ev[0], st));
-  CHK(permute_panel<T>(g, mask, 1, mint.as<T>(), 1, perm));
-  hipLaunchKernelGGL((k_dirichlet_values<T>), dim3(nbN), dim3(256), 0, st, g->rptr.as<int>(), g->rcol.as<int>(),
-                     g->rval.as<T>(), (int)N, mint.as<T>(), aval.as<T>());
+  CHK(permute_panel<T>(g, mask, 1, hs.mint.template as<T>(), 1, perm));
+  CHK(harmonic_values<T>(g, hs));
   for (int64_t c0 = 0; c0 < Nsig; c0 += max_ld) {
     const unsigned ld = (unsigned)std::min<int64_t>(max_ld, Nsig - c0);
     const size_t U = (size_t)N * ld;
     CgPanels<T> w;
     CHK(cg_panels<T>(g, ld, &w));
     const unsigned nbU = (unsigned)std::min<size_t>((U + 255) / 256, 65536);
-    // B = y where measured, 0 elsewhere (y is read there, never multiplied); r = -(L B) on the unmeasured rows
+    // B = y where measured, 0 elsewhere (y is read there, never multiplied)
     CHK(permute_panel<T>(g, y + c0, (unsigned)Nsig, w.B, ld, perm));
-    hipLaunchKernelGGL((k_dirichlet_select<T>), dim3(nbU), dim3(256), 0, st, mint.as<T>(), w.B, U, (int)ld);
-    CHK(spmm_internal<T>(g, g->rval.as<T>(), T(1), T(0), w.B, w.Q, ld, nullptr, 0));
-    hipLaunchKernelGGL((k_dirichlet_rhs<T>), dim3(nbU), dim3(256), 0, st, mint.as<T>(), w.Q, w.R, U, (int)ld);
-    CHK(cg_iterate<T>(g, aval.as<T>(), w, ld, rtol, atol, maxiter, scal, partial, iters ? iters + c0 : nullptr));
-    hipLaunchKernelGGL((k_dirichlet_merge<T>), dim3(nbU), dim3(256), 0, st, mint.as<T>(), w.B, w.X, U, (int)ld);
-    CHK(cg_store<T>(g, w.X, ld, x, c0, Nsig));
+    hipLaunchKernelGGL((k_dirichlet_select<T>), dim3(nbU), dim3(256), 0, st, hs.mint.template as<T>(), w.B, U, (int)ld);
+    CHK(harmonic_solve<T>(g, hs, w, ld, rtol, atol, maxiter, iters ? iters + c0 : nullptr));
+    if (x) CHK(cg_store<T>(g, w.X, ld, x, c0, Nsig));
+    if (alpha)  // (perm: internal position -> the caller's row)
+      CHK(schur_kept_rows<T>(g, shift, hs.mint.template as<T>(), w.X, ld, perm, true, alpha + c0, (size_t)Nsig));
   }
   HIPCHK(hipEventRecord(ctx->ev[1], st));
   return finish_timed(ctx, ms);
@@ -373,10 +414,10 @@ extern "C" int gspx_dirichlet_cg_dev(gspx_graph* g, const void* mask_dev, int64_
   CHK(cg_check_args("dirichlet_cg", g, mask_dev, Nsig, y_dev, x_dev, rtol, atol, maxiter));
   HIPCHK(hipSetDevice(g->ctx->device));
   return g->dtype == GSPX_F32
-             ? dirichlet_cg_t<float>(g, (const float*)mask_dev, Nsig, (const float*)y_dev, (float*)x_dev, rtol, atol,
-                                     maxiter, iterations, kernel_ms)
-             : dirichlet_cg_t<double>(g, (const double*)mask_dev, Nsig, (const double*)y_dev, (double*)x_dev, rtol,
-                                      atol, maxiter, iterations, kernel_ms);
+             ? dirichlet_cg_t<float>(g, 0.f, (const float*)mask_dev, Nsig, (const float*)y_dev, (float*)x_dev, nullptr,
+                                     rtol, atol, maxiter, iterations, kernel_ms)
+             : dirichlet_cg_t<double>(g, 0.0, (const double*)mask_dev, Nsig, (const double*)y_dev, (double*)x_dev,
+                                      nullptr, rtol, atol, maxiter, iterations, kernel_ms);
 }
 
 // ---- differential operator (undirected graphs, no self loops) ------------------------------------------

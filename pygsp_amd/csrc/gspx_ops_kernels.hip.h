@@ -35,16 +35,20 @@ __global__ void k_affine_values(const int* __restrict__ rptr, const int* __restr
 // A = P_u L P_u on the internal layout, P_u = diag(m == 0): the entries of L between two unmeasured vertices, zero
 // elsewhere, so that CG on it with r = p = 0 on the measured rows is CG on the block L_uu (harmonic extension).
 // m is indexed by internal row and has N entries: a pad (col == N) is recognised before m is read.
+// shift != 0: P_u (L + shift I) P_u, the shift added on the diagonal slot of the unmeasured rows (gspx_schur_cg_dev);
+// with shift == 0 the values are L's own bits.
 template <typename T>
 __global__ void k_dirichlet_values(const int* __restrict__ rptr, const int* __restrict__ rcol,
-                                   const T* __restrict__ rval, int N, const T* __restrict__ m,
+                                   const T* __restrict__ rval, int N, const T* __restrict__ m, T shift,
                                    T* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const bool free_row = m[i] == T(0);
   for (int j = rptr[i] & ~3; j < (rptr[i + 1] & ~3); ++j) {
     const int c = rcol[j];
-    out[j] = (c != N && free_row && m[c] == T(0)) ? rval[j] : T(0);
+    T v = (c != N && free_row && m[c] == T(0)) ? rval[j] : T(0);
+    if (shift != T(0) && c == i && free_row) v += shift;
+    out[j] = v;
   }
 }
 // b[i][c] = m[i] != 0 ? b[i][c] : 0 in place (a select: NaN at an unmeasured row does not get through)

@@ -1244,6 +1244,63 @@ class DeviceGraph:
             x = bx.download(y2.shape, self.dtype)
         return (x[:, 0] if one_d else x), iters, ms
 
+    # ---- reduction (Schur complements of L + shift I) -------------------------------------------------
+    def schur_cg_dev(self, shift, mask_ptr, f_ptr, x_ptr, alpha_ptr, nsig, rtol=None, atol=0.0, maxiter=None):
+        """gspx_schur_cg_dev on device pointers (x_ptr / alpha_ptr may be None); returns (iterations, device ms)."""
+        rtol = (1e-10 if self.dtype == np.float64 else 1e-5) if rtol is None else float(rtol)
+        maxiter = 10 * self.N if maxiter is None else int(maxiter)
+        iters = np.zeros(max(int(nsig), 1), dtype=np.int32)
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_schur_cg_dev,
+            self._h, float(shift), ctypes.c_void_p(mask_ptr), int(nsig), ctypes.c_void_p(f_ptr),
+            ctypes.c_void_p(x_ptr), ctypes.c_void_p(alpha_ptr), rtol, float(atol), maxiter, _capi.ptr(iters),
+            ctypes.byref(ms))
+        return iters[:int(nsig)], ms.value
+
+    def schur_cg(self, shift, mask, f, rtol=None, atol=0.0, maxiter=None):
+        """The harmonic extension at a shift: with A = L + shift I, x = f on the kept vertices (mask != 0) and
+        A_uu x_u = -A_uk f_k on the others, per column by conjugate gradients (gspx_schur_cg_dev; shift = 0 is
+        dirichlet_cg, byte for byte); alpha = A x on the kept rows - the Schur complement applied to f_k - and exact
+        zeros elsewhere.  f (N,) or (N, Nsig) is read at kept vertices only.  Defaults as dirichlet_cg.  Returns
+        (x, alpha, iterations per column, device ms)."""
+        f2, one_d = self._panel(f, self.N, "schur_cg")
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=self.dtype)
+        if m.size != self.N:
+            raise ValueError("the mask should be of size [G.n_vertices,]")
+        with self.ctx._temporaries() as t:
+            bm, bf, bx, ba = t.upload(m), t.upload(f2), t.alloc(f2.nbytes), t.alloc(f2.nbytes)
+            iters, ms = self.schur_cg_dev(shift, bm.ptr, bf.ptr, bx.ptr, ba.ptr, f2.shape[1], rtol, atol, maxiter)
+            x, alpha = bx.download(f2.shape, self.dtype), ba.download(f2.shape, self.dtype)
+        return (x[:, 0] if one_d else x), (alpha[:, 0] if one_d else alpha), iters, ms
+
+    def kron(self, ind, shift=0.0, rtol=1e-10, maxiter=None, dense=True, adjacency=False):
+        """Kron reduction of A = L + shift I onto the vertices `ind` (gspx_kron_build, float64 graphs): vertex ind[c]
+        becomes vertex c.  Returns (Lnew, W, iterations, info): Lnew the dense symmetrised (nk, nk) Schur complement
+        (None unless `dense`), W = max(0, -offdiag) as a DeviceAdjacency (None unless `adjacency`), the iteration
+        count of every kept vertex's solve, info = {"kernel_ms", "solve_ms", "rows_ms", "finalise_ms"}.  Entries the iteration never reaches are exact
+        zeros.  ValueError for an empty, repeated or out-of-range `ind` and when the dense result exceeds the
+        context's ws_limit_mb."""
+        if self.dtype != np.float64:
+            raise ValueError("kron runs on the float64 device graph")
+        ind = check_kept(ind, self.N)
+        nk = ind.size
+        maxiter = 10 * self.N if maxiter is None else int(maxiter)
+        iters = np.zeros(nk, dtype=np.int32)
+        h, ms = ctypes.c_void_p(), ctypes.c_double(0)
+        lnew = W = None
+        with self.ctx._temporaries() as t:
+            bl = t.alloc(nk * nk * 8) if dense else None
+            self.ctx.call(_capi.load().gspx_kron_build, self._h, float(shift), _capi.ptr(ind), nk, float(rtol), maxiter,
+                          ctypes.c_void_p(bl.ptr if dense else None), ctypes.byref(h) if adjacency else None,
+                          _capi.ptr(iters), ctypes.byref(ms))
+            if adjacency:
+                W, _, _ = _adjacency(h, self.ctx, nk, True)
+            if dense:
+                lnew = bl.download((nk, nk), np.float64)
+        parts = (ctypes.c_double * 5)()  # (gspx_kron_build leaves its phases where gspx_last_timing reads)
+        _capi.check(_capi.load().gspx_last_timing(self.ctx._h, parts))
+        return lnew, W, iters, {"kernel_ms": ms.value, "solve_ms": parts[0], "rows_ms": parts[1], "finalise_ms": parts[2]}
+
     def tikhonov_simplex(self, tau, step, labels, n_classes, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
         """FISTA on the simplex-constrained Tikhonov problem of learning.classification_tikhonov_simplex
         (gspx_tikhonov_simplex_dev), on this float64 graph.  labels: N ints in the graph's vertex order, the class
@@ -1535,6 +1592,21 @@ def sbm_graph(z, M, seed=None, ctx=None, keep_on_device=False, directed=False, s
     # (keep_on_device: unit int64 weights in the host copy, like the reference's W)
     W, _, ms = _adjacency(h, ctx, N, keep_on_device, weights=np.int64 if keep_on_device else np.float64)
     return W, ms
+
+
+def check_kept(ind, n_vertices):
+    """The kept vertices of a reduction as a contiguous int32 array: ValueError when `ind` is empty, not
+    one-dimensional integers, out of range or holds a vertex twice (host only)."""
+    a = np.asarray(ind)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError("ind must be a non-empty one-dimensional list of vertices")
+    if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("ind must hold integer vertex indices, got {}".format(a.dtype))
+    if a.min() < 0 or a.max() >= n_vertices:
+        raise ValueError("ind must lie in [0, {}), got {} .. {}".format(n_vertices, a.min(), a.max()))
+    if np.unique(a).size != a.size:
+        raise ValueError("ind holds a vertex more than once")
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def line_graph_size(dev):

@@ -340,6 +340,51 @@ def _optimization_functions(saved):
     return {"prox_tv": prox_tv}
 
 
+_REDUCTION = ("kron_reduction", "interpolate")
+
+
+def _reduction_functions(pygsp_module, saved):
+    """kron_reduction and interpolate of pygsp.reduction on the device (pygsp_amd.reduction: conjugate gradients where
+    the package solves directly) for the inputs that qualify - an undirected graph with a sparse combinatorial
+    Laplacian, or a sparse matrix of the form Lap(W) + sigma I, and a valid vertex list; everything else calls the
+    saved original.  Results keep the package's types and shapes: a graph of its own Graph class, a CSR matrix, and
+    the interpolated columns one below the other, (N Nv, 1).  graph_multiresolution and the pyramid functions look
+    both names up at call time and follow."""
+    from . import reduction
+    graph_cls = pygsp_module.graphs.Graph
+
+    def kept(ind, n):
+        try:
+            return engine.check_kept(ind, n)
+        except ValueError:
+            return None
+
+    def kron_reduction(G, ind):
+        if isinstance(G, graph_cls):
+            keep = kept(ind, G.N)
+            if keep is None or G.lap_type != "combinatorial" or not sparse.issparse(G.L) or G.is_directed():
+                return saved["kron_reduction"](G, ind)
+            W = device_graph_for(G, dtype=np.float64).kron(keep, dense=False, adjacency=True)[1].download()
+            coords = G.coords[keep, :] if len(G.coords.shape) else np.ndarray(None)
+            return graph_cls(W, coords=coords, lap_type=G.lap_type, plotting=G.plotting)
+        if sparse.issparse(G) and kept(ind, G.shape[0]) is not None and reduction.split_laplacian(G) is not None:
+            return reduction.kron_reduction(G, ind)
+        return saved["kron_reduction"](G, ind)
+
+    def interpolate(G, f_subsampled, keep_inds, order=100, reg_eps=0.005, **kwargs):
+        keep = kept(keep_inds, G.N)
+        shape = np.shape(f_subsampled)
+        if (keep is None or not sparse.issparse(G.L) or len(shape) not in (1, 2) or shape[0] != keep.size or
+                not reg_eps > 0 or set(kwargs) - {"method"} or kwargs.get("method", "chebyshev") not in ("chebyshev", "exact")):
+            return saved["interpolate"](G, f_subsampled, keep_inds, order=order, reg_eps=reg_eps, **kwargs)
+        out = reduction.interpolate(G, np.asarray(f_subsampled, dtype=np.float64), keep, order, reg_eps, **kwargs)
+        return out.reshape(-1, 1, order="F")  # (the package's legacy analysis stacks the columns)
+
+    kron_reduction.__doc__ = saved["kron_reduction"].__doc__
+    interpolate.__doc__ = saved["interpolate"].__doc__
+    return {"kron_reduction": kron_reduction, "interpolate": interpolate}
+
+
 _TOPOLOGY = ("is_connected", "extract_components")
 
 
@@ -434,7 +479,7 @@ def _linegraph_init(linegraph_cls):
 def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, reorder="auto",
             tiles="auto", devices=None, lmax="reference", wrap_filter=True, evaluation=None, fourier=False,
             lanczos=False, features=False, learning=False, topology=False, optimization=False, harmonic=False,
-            layout=False, exact=False, full_basis=False, linegraph=False):
+            layout=False, exact=False, full_basis=False, linegraph=False, reduction=False):
     """Patch the real pygsp in place.  `laplacian`: 'device' (L assembled by HIP kernels from
     G.W) or 'host' (upload the reference's G.L).  `devices` (a list of GPU ids, optional): every
     ``Filter.filter(method='chebyshev')`` splits its signal columns over these GPUs - the graph is replicated
@@ -480,7 +525,10 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     `exact` (default False; needs ``wrap_filter=True``): ``Filter.filter(method='exact')`` and ``Modulation.filter``
     also run on the device, against a device copy of the full ``G.U`` (float64 signals; the basis is the reference's
     own eigh, uploaded once, or the device's under ``full_basis=True``); ``Gabor`` follows through ``Filter.filter``.
-    Off, the package's own code answers ``method='exact'``."""
+    Off, the package's own code answers ``method='exact'``.
+    `reduction` (default False): also replace ``pygsp.reduction.kron_reduction`` and ``interpolate`` with their device
+    forms (pygsp_amd.reduction) for the inputs that qualify; the rest calls the original.  Iterative where the package
+    is direct (conjugate gradients at rtol 1e-10 in place of spsolve), hence opt-in."""
     if evaluation is not None and evaluation not in _filters.EVALUATIONS:
         raise ValueError("evaluation must be 'recurrence', 'newton', 'product' or 'auto'")
     if laplacian not in ("device", "host"):
@@ -542,7 +590,8 @@ def install(pygsp_module=None, laplacian="device", dtype=np.float64, device=0, r
     for name, asked, names, replacements in (
             ("features", features, _FEATURES, lambda saved: _feature_functions(pygsp_module, saved)),
             ("learning", learning, _LEARNING, lambda saved: _learning_functions(saved, harmonic)),
-            ("optimization", optimization, _OPTIMIZATION, _optimization_functions)):
+            ("optimization", optimization, _OPTIMIZATION, _optimization_functions),
+            ("reduction", reduction, _REDUCTION, lambda saved: _reduction_functions(pygsp_module, saved))):
         if on[name] is not None:
             _apply(on[name], replacements(_originals(on[name], names)) if asked else {})
         elif asked:
@@ -558,7 +607,8 @@ def _targets(pygsp_module):
             "Graph": getattr(getattr(pygsp_module, "graphs", None), "Graph", None),
             "LineGraph": getattr(getattr(pygsp_module, "graphs", None), "LineGraph", None),
             "features": getattr(pygsp_module, "features", None), "learning": getattr(pygsp_module, "learning", None),
-            "optimization": getattr(pygsp_module, "optimization", None)}
+            "optimization": getattr(pygsp_module, "optimization", None),
+            "reduction": getattr(pygsp_module, "reduction", None)}
 
 
 def _apply(obj, wanted):

@@ -1145,7 +1145,8 @@ class DeviceGraph:
     def _panel(self, x, rows, what):
         x = np.asarray(x)
         one_d = x.ndim == 1
-        x2 = np.ascontiguousarray(x.reshape(x.shape[0], -1), dtype=self.dtype)
+        # (the columns spelled out: reshape(0, -1) cannot infer them for the empty edge signal of an edgeless graph)
+        x2 = np.ascontiguousarray(x.reshape(x.shape[0], int(np.prod(x.shape[1:]))), dtype=self.dtype)
         if x2.shape[0] != rows:
             raise ValueError("{}: first dimension must be {}, got {}".format(what, rows, x.shape))
         return x2, one_d

@@ -1,5 +1,6 @@
 """What the modules that pin k_step_tile at small shapes share (tests/test_gpu_o_programs_on_tiles.py: polynomial
-programs; tests/test_gpu_p_recurrence_on_tiles.py: the recurrence, filter banks and synthesis): one cached case per
+programs; tests/test_gpu_p_recurrence_on_tiles.py: the recurrence, filter banks and synthesis; the squared norms and
+L x of tests/test_gpu_u_sqnorms_small.py and tests/test_gpu_u_lx_on_tiles.py use them too): one cached case per
 graph, cached device graphs with gather tiles from both builders, option scopes, the comparison with the oracle that
 keeps the worst figures, and the restated rules of which launches take the tile kernel."""
 import contextlib
@@ -170,6 +171,36 @@ def expected_kinds(nsig, elt, max_batch, S, tile_min_row=16):
     for c0, ld in batch_columns(nsig, max_batch):
         tile = ((ld * elt) % 16 == 0 and (nsig * elt) % 16 == 0 and ld * elt >= tile_min_row and (c0 * elt) % 16 == 0)
         kinds["tile" if tile else "plain"] += S
+    return kinds
+
+
+def expected_kinds_lx(nsig, elt, max_batch=0, fuse_input=1, tile_gather=1, tiles=True, slow_blocks=0, x_offset=0,
+                      in_place=False, tile_min_row=16):
+    """The rule of gspx_ops.hip.h for y = L x (lap_apply_t) restated, for nsig signals of elt bytes; one launch per
+    batch, counted like a filter's steps.
+    - Fused: ONE tile launch that gathers from the caller's panel, iff the panel fits one batch (ops_max_ld: max_batch
+      columns, a multiple of 4 from 4 on), fuse_input is on, every block of the graph is staged (slow_blocks = 0), x is
+      16-byte aligned (x_offset: bytes of x into its aligned buffer), x and y do not overlap, and the tile kernel can
+      take the whole panel: rows of whole 16-byte pieces of at least tile_min_row bytes (y's buffer is aligned).
+    - Else column batches through the workspace: a batch of ld columns starting at c0 takes the tile kernel iff its
+      rows and the rows of y are whole 16-byte pieces, its rows have at least tile_min_row bytes and y + c0 is 16-byte
+      aligned - expected_kinds' rule with one step -, else the plain kernel.
+    (The 2 GiB windows and the workspace budget bind on no graph this small.)"""
+    tvec = 16 // elt
+    on = tiles and bool(tile_gather)
+
+    def usable(ld, c0):
+        return on and ld * elt >= tile_min_row and ld % tvec == 0 and nsig % tvec == 0 and (c0 * elt) % 16 == 0
+
+    width = max_batch if max_batch > 0 else 1 << 30
+    if width >= 4:
+        width &= ~3
+    if (nsig <= width and fuse_input and slow_blocks == 0 and x_offset % 16 == 0 and not in_place
+            and usable(nsig, 0)):
+        return {"tile": 1, "plain": 0}
+    kinds = {"tile": 0, "plain": 0}
+    for c0 in range(0, nsig, width):
+        kinds["tile" if usable(min(width, nsig - c0), c0) else "plain"] += 1
     return kinds
 
 

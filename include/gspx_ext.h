@@ -406,6 +406,22 @@ int gspx_cheby_sqnorms_dev(gspx_graph* g, double lmax, int Nf, int M, const doub
 int gspx_cheby_moments_dev(gspx_graph* g, double lmax, int M, int64_t Nsig, const void* x_dev,
                            double* out, double* kernel_ms);
 
+/* Chebyshev CROSS-moments of DEVICE signals: out (HOST, Nf x M x Nsig fp64, row-major)
+ *   out[f][k][j] = sum_n z[f][n][j] * (T_k(Lt) x)[n][j],  k < M,
+ * the inner products of the recurrence on x with Nf foreign planes - what the derivative of a Chebyshev filter's output
+ * with respect to its coefficients is made of (pygsp_amd.filters.cheby_op_vjp).  x_dev: N x Nsig; z_dev: Nf planes
+ * [f][n][s] of N x Nsig; both row-major, the graph's compute dtype, the CALLER's vertex order.  2 <= M <= 256, Nf >= 1.
+ * M - 1 recurrence steps (no doubling: z is not x); every product and sum is fp64 for both graph dtypes
+ * (k_slot_cross_dots) and identical calls give identical bits.  z_dev == x_dev with Nf = 1 is legal (the self-moments,
+ * the long way).  Nsig == 0: nothing happens; N == 0: zeros. */
+int gspx_cheby_cross_moments_dev(gspx_graph* g, double lmax, int M, int64_t Nsig, const void* x_dev, int Nf,
+                                 const void* z_dev, double* out, double* kernel_ms);
+/* The device ordinal of a pointer, asked of the HIP runtime libgspx itself is bound to (hipPointerGetAttributes):
+ * GSPX_OK and *device for device memory that runtime knows; GSPX_ERR_INVALID for anything else - host memory, a null
+ * pointer, memory of ANOTHER HIP runtime loaded into the same process - with the runtime's error state cleared.
+ * Launches nothing and touches no memory: the gate a binding puts in front of pointers it did not allocate. */
+int gspx_ptr_device(const void* p, int* device);
+
 /* PCI address ("0000:c1:00.0", NUL-terminated) of HIP device `device`: what a host driver needs to find the NUMA
  * node the GPU hangs off (/sys/bus/pci/devices/<address>/numa_node) and pin the thread - and the packing threads
  * libgspx starts from it - that feeds this GPU to the cores next to it (pygsp_amd.multi). */

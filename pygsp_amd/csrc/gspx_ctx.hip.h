@@ -536,6 +536,26 @@ extern "C" int gspx_buf_ptr(gspx_buf* b, void** p) {
   return GSPX_OK;
 }
 
+// Which device a pointer belongs to, as THIS library's HIP runtime sees it: the gate for pointers another library
+// allocated (pygsp_amd.nn).  A process can hold two HIP runtimes, and a pointer of the other one means nothing here.
+// No kernel, no memory access; a failed query leaves no sticky error behind.
+extern "C" int gspx_ptr_device(const void* p, int* device) {
+  if (!p || !device) return set_err(GSPX_ERR_INVALID, "gspx_ptr_device: null argument");
+  *device = -1;
+  hipPointerAttribute_t a;
+  memset(&a, 0, sizeof(a));
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(GSPX_ERR_INVALID, "gspx_ptr_device: not a pointer this HIP runtime knows (%s)", hipGetErrorName(e));
+  }
+  if (a.type != hipMemoryTypeDevice)
+    return set_err(GSPX_ERR_INVALID, "gspx_ptr_device: not device memory of this HIP runtime (memory type %d)",
+                   (int)a.type);
+  *device = a.device;
+  return GSPX_OK;
+}
+
 extern "C" int gspx_buf_bytes(gspx_buf* b, int64_t* bytes) {
   if (!b || !bytes) return set_err(GSPX_ERR_INVALID, "gspx_buf_bytes: null argument");
   *bytes = b->bytes;

@@ -1,6 +1,8 @@
 // gspx_moments.hip.h - device code of the Chebyshev self-moments (gspx_cheby_moments_dev, pygsp_amd.spectrum): the
-// inner products of neighbouring kept slots of a deferred batch.  The recurrence steps that fill the slots are the
-// ones every filter runs (gspx_kernels.hip.h, gspx_tile_kernels.hip.h); the driver is in gspx_poly.hip.h.
+// inner products of neighbouring kept slots of a deferred batch - and of the cross-moments
+// (gspx_cheby_cross_moments_dev, filters.cheby_op_vjp): the kept slots against foreign planes.  The recurrence steps
+// that fill the slots are the ones every filter runs (gspx_kernels.hip.h, gspx_tile_kernels.hip.h); the drivers are in
+// gspx_poly.hip.h.
 #pragma once
 #include "gspx_kernels.hip.h"
 
@@ -102,6 +104,98 @@ __global__ __launch_bounds__(256) void k_slot_dots(const T* __restrict__ slots, 
         if (s < CS && i + 1 < nslots) pr[(size_t)(nslots + i) * w + j] = red[CS + 1 + s][j][e] + b[s][j];
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cross-moments (gspx_cheby_cross_moments_dev): the kept slots T_0 .. T_{nslots-1} of a column batch dotted against
+// np <= P FOREIGN planes z_p (row pitch ldz, plane pitch zplane, the caller's vertex order):
+//     c_{p,i}[j] = sum_rows z_p[rows(row)][j] T_i[row][j]      (p < np, i < nslots)
+// The slots are in the internal vertex order and z is not, and a cross-moment does care: slot row `row` meets z row
+// zrows[row] (zrows == null: the same row).  The row index is one 4-byte load per row and lane, 64 >> cwl distinct
+// addresses per wave; the z rows themselves stay whole 2^cwl VEC-element pieces, so an internal order that keeps
+// neighbours together keeps the z stream nearly sequential.
+// Lane layout, row walk, fp64 products and sums, the wave butterfly, the LDS pass over the four waves in wave order
+// and the per-workgroup partials are those of k_slot_dots above.  A lane owns VEC neighbouring columns, one chunk of
+// CS slots (blockIdx.y) and the pass's planes; per row it loads its elements of the chunk's slots and of the np
+// planes - CS + P independent loads - for CS P VEC fused multiply-adds, and the CS P VEC accumulators stay in
+// registers over the row loop.  A slot is read once per pass, a plane once per chunk of slots.  Pad columns (>= w)
+// and rows >= N are never read, of the slots or of z.
+// part[blockIdx.x][p][i][w]: n = np nslots w doubles per workgroup row, summed by k_dots_reduce in a fixed order.
+// grid: (row groups, ceil(nslots / CS) chunks, blocks of 2^cwl column groups).
+// ---------------------------------------------------------------------------------------------
+template <typename T, int VEC, int CS, int P>
+__global__ __launch_bounds__(256) void k_slot_cross_dots(const T* __restrict__ slots, int nslots, size_t slot_stride,
+                                                         u32 pitch, const T* __restrict__ z, int np, size_t zplane,
+                                                         u32 ldz, const int* __restrict__ zrows, int N, int w, int cwl,
+                                                         double* __restrict__ part) {
+  typedef typename VT<T, VEC>::t V;
+  __shared__ double red[CS * P][VEC][64];
+  const int e = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cw = 1 << cwl;
+  const int rpt = 64 >> cwl;  // rows per tile
+  const int col = (blockIdx.z * cw + (e & (cw - 1))) * VEC;
+  const bool colok = col < w;  // (w is a multiple of VEC)
+  const int i0 = blockIdx.y * CS;
+  const int ns = min(CS, nslots - i0);  // slots this chunk reads
+  double acc[CS][P][VEC];
+#pragma unroll
+  for (int s = 0; s < CS; ++s)
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) acc[s][p][j] = 0.0;
+  const T* __restrict__ base = slots + (size_t)i0 * slot_stride + col;
+  const int stride = (int)gridDim.x * 4 * rpt;
+  for (int row = ((int)blockIdx.x * 4 + wave) * rpt + (e >> cwl); row < N; row += stride) {
+    const T* __restrict__ ps = base + (size_t)row * pitch;
+    const size_t zr = zrows ? (size_t)zrows[row] : (size_t)row;
+    const T* __restrict__ pz = z + zr * ldz + col;
+    V v[CS], u[P];
+#pragma unroll
+    for (int s = 0; s < CS; ++s) v[s] = (s < ns && colok) ? *(const V*)(ps + (size_t)s * slot_stride) : V(0);
+#pragma unroll
+    for (int p = 0; p < P; ++p) u[p] = (p < np && colok) ? *(const V*)(pz + (size_t)p * zplane) : V(0);
+#pragma unroll
+    for (int s = 0; s < CS; ++s)
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+          acc[s][p][j] = fma(dots_elem<VEC>(u[p], j), dots_elem<VEC>(v[s], j), acc[s][p][j]);
+  }
+  for (int off = cw; off < 64; off <<= 1) {
+#pragma unroll
+    for (int s = 0; s < CS; ++s)
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) acc[s][p][j] += __shfl_xor(acc[s][p][j], off);
+  }
+  // lanes e < 2^cwl hold their columns' sums over the wave's rows: waves 0..2 add theirs up in LDS, in wave order
+  const bool owner = (e >> cwl) == 0;
+  for (int q = 0; q < 3; ++q) {
+    if (wave == q && owner) {
+#pragma unroll
+      for (int s = 0; s < CS; ++s)
+#pragma unroll
+        for (int p = 0; p < P; ++p)
+#pragma unroll
+          for (int j = 0; j < VEC; ++j)
+            red[s * P + p][j][e] = q ? red[s * P + p][j][e] + acc[s][p][j] : acc[s][p][j];
+    }
+    __syncthreads();
+  }
+  if (wave == 3 && owner && colok) {
+    double* __restrict__ pr = part + (size_t)blockIdx.x * (size_t)np * (size_t)nslots * w + col;
+#pragma unroll
+    for (int s = 0; s < CS; ++s)
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j)
+          if (s < ns && p < np) pr[((size_t)p * nslots + (i0 + s)) * w + j] = red[s * P + p][j][e] + acc[s][p][j];
   }
 }
 

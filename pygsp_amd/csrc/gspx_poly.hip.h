@@ -381,6 +381,74 @@ static int launch_slot_dots(gspx_ctx* ctx, const T* slots, int S, size_t slot_st
   return GSPX_OK;
 }
 
+// The inner products of the kept slots of a deferred batch with nf foreign planes z instead of its outputs
+// (gspx_cheby_cross_moments_dev): z [nf][N][ldz] at the batch's first column, in the CALLER's vertex order
+// (k_slot_cross_dots reads its rows through the graph's permutation); out [nf][M][ldo] fp64 at the batch's first column;
+// part the workgroup partials (cross_parts doubles at the call's widest batch).
+struct CrossDots {
+  const void* z;
+  unsigned ldz;
+  size_t zplane;
+  int nf;
+  double* out;
+  size_t ldo;
+  double* part;
+};
+// The builds of k_slot_cross_dots.  A pass takes at most CROSS_PASS planes; a pass of more than CROSS_FEW planes runs
+// the wide build - 8 planes x a chunk of 8 slots, 64 fp64 accumulators, two waves per SIMD - and a pass of one or two
+// planes (the single filter whose coefficients are learnt) the narrow one - 2 planes x a chunk of 16 slots, 32
+// accumulators, four waves per SIMD and 17 or 18 loads in flight per lane where the wide build with one plane has 9:
+// the kernel is bound by the loads it keeps in flight (profiles/autograd.md).  fp32 panels whose rows split into pairs
+// take two columns per lane and half the chunk: the same accumulators, 8-byte loads.
+static const int CROSS_PASS = 8, CROSS_FEW = 2;
+static int cross_cs(int here, int vec) { return (here <= CROSS_FEW ? 16 : 8) / vec; }  // slots per chunk
+template <typename T> static int cross_vec(unsigned w, unsigned pitch, const T* z, unsigned ldz) {
+  return dots_vec<T>(w, pitch) == 2 && ldz % 2 == 0 && ((uintptr_t)z % (2 * sizeof(T))) == 0 ? 2 : 1;
+}
+static int cross_chunks(int M, int here, int vec) { return (M + cross_cs(here, vec) - 1) / cross_cs(here, vec); }  // grid.y
+// row groups of a k_slot_cross_dots launch of `here` planes: as dots_gx, with here M w doubles per row group
+static int cross_gx(const gspx_ctx* ctx, int N, unsigned w, int M, int here, int vec) {
+  const int cwl = sqnorm_cwl(w / vec);
+  const int64_t rows = 4 * (int64_t)(64 >> cwl);
+  const int64_t tiles = ((int64_t)N + rows - 1) / rows;
+  const int64_t others = (((int64_t)(w / vec) + (1 << cwl) - 1) >> cwl) * cross_chunks(M, here, vec);
+  const int64_t fit = ((int64_t)64 << 20) / ((int64_t)here * M * w * (int64_t)sizeof(double));
+  const int64_t want = (8 * (int64_t)ctx->cu_count + others - 1) / others;
+  return (int)std::max<int64_t>(1, std::min(std::min(tiles, want), fit));
+}
+static size_t cross_parts(const gspx_ctx* ctx, int N, unsigned w, int M, int nf) {  // (whichever build and pass)
+  size_t most = 0;
+  for (int here : {std::min(nf, CROSS_PASS), nf % CROSS_PASS})
+    for (int vec = 1; here > 0 && vec <= (w % 2 == 0 ? 2 : 1); ++vec)
+      most = std::max(most, (size_t)cross_gx(ctx, N, w, M, here, vec) * (size_t)here * M * w);
+  return most;
+}
+
+template <typename T>
+static int launch_slot_cross_dots(gspx_ctx* ctx, const T* slots, int M, size_t slot_stride, unsigned pitch, int N,
+                                  unsigned w, const int* perm, const CrossDots& cd, hipStream_t st) {
+  const T* z = (const T*)cd.z;
+  const int vec = cross_vec<T>(w, pitch, z, cd.ldz);
+  const int cwl = sqnorm_cwl(w / vec);
+  typedef void (*kern_t)(const T*, int, size_t, u32, const T*, int, size_t, u32, const int*, int, int, int, double*);
+  for (int f0 = 0; f0 < cd.nf; f0 += CROSS_PASS) {
+    const int here = std::min(CROSS_PASS, cd.nf - f0);
+    const bool few = here <= CROSS_FEW;
+    kern_t kern = few ? k_slot_cross_dots<T, 1, 16, CROSS_FEW> : k_slot_cross_dots<T, 1, 8, CROSS_PASS>;
+    if constexpr (sizeof(T) == 4) {
+      if (vec == 2) kern = few ? k_slot_cross_dots<T, 2, 8, CROSS_FEW> : k_slot_cross_dots<T, 2, 4, CROSS_PASS>;
+    }
+    const int gx = cross_gx(ctx, N, w, M, here, vec);
+    const dim3 grid((unsigned)gx, (unsigned)cross_chunks(M, here, vec), (w / vec + (1u << cwl) - 1) >> cwl);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, slots, M, slot_stride, (u32)pitch, z + (size_t)f0 * cd.zplane, here,
+                       cd.zplane, (u32)cd.ldz, perm, N, (int)w, cwl, cd.part);
+    const int64_t n = (int64_t)here * M * w;
+    hipLaunchKernelGGL(k_dots_reduce, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, cd.part, gx, n, (int)w,
+                       cd.out + (size_t)f0 * M * cd.ldo, cd.ldo);
+  }
+  return GSPX_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // the filter
 // ------------------------------------------------------------------------------------------------
@@ -656,7 +724,7 @@ template <typename T>
 static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp, const T* x,
                      unsigned ldx, T* y, unsigned ldy, unsigned ld, bool deferred,
                      bool acc_existing, bool final_to_y, size_t& ev_idx, const SqNorms* sq = nullptr,
-                     const SlotDots* sd = nullptr) {
+                     const SlotDots* sd = nullptr, const CrossDots* cd = nullptr) {
   gspx_ctx* ctx = g->ctx;
   const Options& opt = ctx->opt;
   hipStream_t st = ctx->stream;
@@ -793,6 +861,8 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
     CHK(launch_combine_sqnorm<T>(ctx, slots, M, SU, ldw, N, ld, *sq, st));
   } else if (deferred && sd) {  // the slots' inner products in place of the outputs (likewise)
     CHK(launch_slot_dots<T>(ctx, slots, M, SU, ldw, N, ld, *sd, st));
+  } else if (deferred && cd) {  // the slots' inner products with the caller's planes, read through the vertex order
+    CHK(launch_slot_cross_dots<T>(ctx, slots, M, SU, ldw, N, ld, perm, *cd, st));
   } else if (deferred) {
     launch_combine<T>(slots, M, SU, ctx->ws_w.as<T>(), M, nf, N, ld, y, ldy, (size_t)N * ldy, perm,
                       padded ? 1 : vec_cap(shape.vec, ldy, y), st, ldw);
@@ -1453,6 +1523,67 @@ extern "C" int gspx_cheby_moments_dev(gspx_graph* g, double lmax, int M, int64_t
   replay_reset(g->ctx);  // (the kept slots overwrite the panels a recorded filter call replays from)
   return device_call(g, Nsig, x_dev, out, kernel_ms, [&](auto x, auto, int64_t n) {
     return moments_dev_t(g, lmax, M, n, x, out);
+  });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Chebyshev cross-moments of device signals (the coefficient gradient of filters.cheby_op_vjp):
+//     out[f][k][j] = sum_n z[f][n][j] (T_k(Lt) x)[n][j],  k < M.
+// Per column batch the deferred plan of ONE filter with M kept slots - M - 1 plain recurrence steps; z is foreign, so
+// the doubling of the self-moments does not apply - then k_slot_cross_dots over the kept slots in place of k_combine,
+// CROSS_PASS planes per pass.  The workspaces are the M slots, the Nf x M x Nsig result and the workgroup partials.
+// out: HOST, Nf x M x Nsig.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+static int cross_moments_dev_t(gspx_graph* g, double lmax, int M, int64_t Nsig, const T* x, int Nf, const T* z,
+                               double* out) {
+  gspx_ctx* ctx = g->ctx;
+  const int64_t N = g->N;
+  for (int i = 0; i < 5; ++i) ctx->timing[i] = 0;
+  ctx->step_kinds[0] = ctx->step_kinds[1] = 0;
+  if (Nsig == 0) return GSPX_OK;
+  if (N == 0) {
+    std::fill(out, out + (size_t)Nf * M * Nsig, 0.0);
+    return GSPX_OK;
+  }
+  int64_t width = 0;
+  CHK(batch_width(g, sizeof(T), (size_t)M, Nsig, &width));
+  const std::vector<double> cp((size_t)M, 0.0);  // (the deferred plan uploads its filter's coefficients; none are read)
+  const size_t obytes = (size_t)Nf * M * Nsig * sizeof(double);
+  const int64_t first = std::min<int64_t>(width, Nsig), last = Nsig - (Nsig - 1) / width * width;
+  const size_t parts =
+      std::max(cross_parts(ctx, (int)N, (unsigned)first, M, Nf), cross_parts(ctx, (int)N, (unsigned)last, M, Nf));
+  CHK(ctx->ws_sq.ensure(obytes + 256));
+  CHK(ctx->ws_sqp.ensure(parts * sizeof(double) + 256));
+  hipStream_t st = ctx->stream;
+  CHK(ensure_factor<T>(g, lmax));
+  double* outd = ctx->ws_sq.as<double>();
+  CHK(run_batches(g, Nsig, width, M - 1, [&](int64_t c0, unsigned ld, size_t& ev_idx) -> int {
+    const CrossDots b{z + c0, (unsigned)Nsig, (size_t)N * (size_t)Nsig, Nf, outd + c0, (size_t)Nsig,
+                      ctx->ws_sqp.as<double>()};
+    return run_batch<T>(g, 1, M, cp, x + c0, (unsigned)Nsig, (T*)nullptr, ld, ld, true, false, false, ev_idx, nullptr,
+                        nullptr, &b);
+  }));
+  HIPCHK(hipMemcpyAsync(out, outd, obytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return GSPX_OK;
+}
+
+extern "C" int gspx_cheby_cross_moments_dev(gspx_graph* g, double lmax, int M, int64_t Nsig, const void* x_dev, int Nf,
+                                            const void* z_dev, double* out, double* kernel_ms) {
+  // (the scalar checks first: they need no graph, and so no device, to be exercised)
+  if (M < 2 || M > 256)
+    return set_err(GSPX_ERR_INVALID, "gspx_cheby_cross_moments_dev: 2 to 256 orders (got %d)", M);
+  if (Nf < 1) return set_err(GSPX_ERR_INVALID, "Nf must be >= 1");
+  if (Nsig < 0) return set_err(GSPX_ERR_INVALID, "negative number of signals");
+  if (!(lmax > 0.0) || !std::isfinite(lmax))
+    return set_err(GSPX_ERR_INVALID, "lmax must be positive and finite (got %g)", lmax);
+  if (!g) return set_err(GSPX_ERR_INVALID, "null graph");
+  if (Nsig > 0 && (!out || (g->N > 0 && (!x_dev || !z_dev)))) return set_err(GSPX_ERR_INVALID, "null signal pointer");
+  if (Nsig >= ((int64_t)1 << 31) / 16) return set_err(GSPX_ERR_INVALID, "too many signals");
+  replay_reset(g->ctx);  // (the kept slots overwrite the panels a recorded filter call replays from)
+  return device_call(g, Nsig, x_dev, out, kernel_ms, [&](auto x, auto, int64_t n) {
+    return cross_moments_dev_t(g, lmax, M, n, x, Nf, (decltype(x))z_dev, out);
   });
 }
 

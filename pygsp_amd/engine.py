@@ -1019,6 +1019,30 @@ class DeviceGraph:
                 bx.upload(x)
             return self.cheby_moments_dev(bx.ptr, x.shape[1], lmax, M)
 
+    def cheby_cross_moments_dev(self, x_ptr, z_ptr, nsig, nf, lmax, M):
+        """Chebyshev cross-moments of the device signals at x_ptr (N x nsig) with the nf planes at z_ptr
+        (nf x N x nsig): ((nf, M, nsig) float64 host array of sum_n z[f][n][j] (T_k(Lt) x)[n][j] for k < M, device
+        milliseconds of the call) from M - 1 recurrence steps (gspx_cheby_cross_moments_dev)."""
+        out = np.zeros((int(nf), int(M), int(nsig)))
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_cheby_cross_moments_dev, self._h, float(lmax), int(M), int(nsig),
+                      ctypes.c_void_p(x_ptr), int(nf), ctypes.c_void_p(z_ptr), _capi.ptr(out), ctypes.byref(ms))
+        return out, ms.value
+
+    def cheby_cross_moments(self, x, z, lmax, M):
+        """cheby_cross_moments_dev of host arrays x (N, nsig) and z (nf, N, nsig): uploaded in the graph's dtype,
+        freed afterwards."""
+        x = self._signals(x)
+        z = np.ascontiguousarray(z, dtype=self.dtype)
+        if z.ndim != 3 or z.shape[0] < 1 or z.shape[1:] != x.shape:
+            raise ValueError("z must be (Nf, N, Nsig) with x's N and Nsig, got {} for x {}".format(z.shape, x.shape))
+        with self.ctx._temporaries() as t:
+            bx, bz = t.alloc(x.nbytes), t.alloc(z.nbytes)
+            if x.nbytes:
+                bx.upload(x)
+                bz.upload(z)
+            return self.cheby_cross_moments_dev(bx.ptr, bz.ptr, x.shape[1], z.shape[0], lmax, M)
+
     def tune_placement(self, coeffs, x_ptr, y_ptr, nsig, lmax, candidates=6, stride_mb=0):
         """Draw `candidates` physical backings for the context's streamed workspaces and keep the one on which THIS call
         (the arguments of cheby_filter_dev, one filter) runs fastest (gspx_ctx_tune_placement; on MI355X the same call

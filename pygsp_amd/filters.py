@@ -565,6 +565,128 @@ def cheby_op(G, c, signal, **kwargs):
     return stacked[:, 0] if vector_in else stacked
 
 
+def _grad_coefficients(cross):
+    """(Nf, M) gradient of the coefficients from the (Nf, M, Nsig) cross-moments: summed over the signal columns in
+    fp64 on the host, column 0 halved (c_0 enters the polynomial as c_0 / 2, approximations.py:101)."""
+    grad = np.asarray(cross, dtype=np.float64).sum(axis=2)
+    grad[:, 0] *= 0.5
+    return grad
+
+
+def _vjp_host(dev, lmax, coeffs, x, cot, synthesis):
+    """Both halves of a vector-Jacobian product on host arrays, through the host-array calls of `dev` (an
+    engine.DeviceGraph, or a stand-in with its cheby_filter / cheby_cross_moments).  Analysis forward: x (N, Nsig),
+    cot (Nf, N, Nsig); d/dx = sum_f p_f(L) cot_f is the synthesis call (L symmetric), d/dc_fk = w_k <cot_f, T_k x>.
+    Synthesis forward: x (Nf, N, Nsig), cot (N, Nsig); d/dx_f = p_f(L) cot is the analysis call and
+    d/dc_fk = w_k <x_f, T_k cot>.  Returns (grad_x, (Nf, M) grad_c, device ms)."""
+    M = coeffs.shape[1]
+    if synthesis:
+        gx, ms1 = dev.cheby_filter(coeffs, cot, lmax, _capi.ANALYSIS)
+        cross, ms2 = dev.cheby_cross_moments(cot, x, lmax, M)
+    else:
+        gx, ms1 = dev.cheby_filter(coeffs, cot, lmax, _capi.SYNTHESIS)
+        cross, ms2 = dev.cheby_cross_moments(x, cot, lmax, M)
+    return np.asarray(gx, dtype=np.float64), _grad_coefficients(cross), ms1 + ms2
+
+
+def _vjp_device(dev, lmax, coeffs, x_ptr, cot_ptr, gx_ptr, nsig, synthesis, need_x=True, need_c=True):
+    """_vjp_host on device pointers (plane layouts as there); grad_x is written to gx_ptr.  need_x / need_c: which of
+    the two device calls run (a half that is not needed costs nothing).  Returns ((Nf, M) grad_c or None, device ms)."""
+    Nf, M = coeffs.shape
+    ms, grad_c = 0.0, None
+    if need_x:
+        ms += dev.cheby_filter_dev(coeffs, cot_ptr, gx_ptr, nsig, lmax, _capi.ANALYSIS if synthesis else _capi.SYNTHESIS)
+    if need_c:
+        a, b = (cot_ptr, x_ptr) if synthesis else (x_ptr, cot_ptr)
+        cross, ms2 = dev.cheby_cross_moments_dev(a, b, nsig, Nf, lmax, M)
+        grad_c, ms = _grad_coefficients(cross), ms + ms2
+    return grad_c, ms
+
+
+def cheby_op_vjp(G, c, signal, cotangent, **kwargs):
+    """Vector-Jacobian product of ``cheby_op(G, c, signal)``: for a cotangent of the shape cheby_op returns -
+    (Nf N,) or (Nf N, Nsig), block f = rows [f N, (f + 1) N) - the pair (grad_signal, grad_c) with
+
+        grad_signal = sum_f p_f(L) cotangent_f                       one synthesis call with `c` (L is symmetric)
+        grad_c[f, k] = w_k sum_{n, j} (T_k(Lt) signal)[n, j] cotangent_f[n, j],   w_0 = 1/2, w_k = 1 otherwise
+
+    grad_signal is a float64 array of signal's shape; grad_c a float64 array of c's shape, the cross-moments of the
+    recurrence (gspx_cheby_cross_moments_dev) summed over the signal columns in fp64 on the host.  Only the
+    recurrence evaluates the polynomial here: `evaluation` other than None / 'recurrence', and a device list, raise
+    ValueError."""
+    coeffs = _as_coeff_matrix(c)
+    if kwargs.get("evaluation") not in (None, "recurrence"):
+        raise ValueError("cheby_op_vjp differentiates the recurrence: evaluation must be None or 'recurrence'")
+    if kwargs.get("devices") is not None:
+        raise ValueError("cheby_op_vjp runs on one GPU: it takes no device list")
+    panel, cot = np.asanyarray(signal), np.asanyarray(cotangent)
+    if np.iscomplexobj(panel) or np.iscomplexobj(cot):
+        raise TypeError("complex signals are not supported by the Chebyshev path")
+    if panel.ndim not in (1, 2) or panel.shape[0] != G.N:
+        raise ValueError("First dimension must be the number of vertices "
+                         "G.N = {}, got {}.".format(G.N, panel.shape))
+    Nf = coeffs.shape[0]
+    if cot.shape != (Nf * G.N,) + panel.shape[1:]:
+        raise ValueError("the cotangent must have the shape cheby_op returns, {}, got {}"
+                         .format((Nf * G.N,) + panel.shape[1:], cot.shape))
+    x = panel.reshape(G.N, -1)
+    gx, grad_c, ms = _vjp_host(_device_graph_of(G), G.lmax, coeffs, x, cot.reshape(Nf, G.N, x.shape[1]), False)
+    _record_timing(G, ms)
+    return gx.reshape(panel.shape), grad_c.reshape(np.shape(c) if np.ndim(c) else coeffs.shape)
+
+
+def filter_signals_vjp(bank, s, cotangent, order=30, coefficients=None):
+    """Vector-Jacobian product of ``filter_signals(bank, s, 'chebyshev', order)``: (grad_s, grad_coefficients) for a
+    cotangent of the shape that call returns.  `s` goes through the shape rules of filter_signals; in synthesis the
+    roles swap (d/ds_f = p_f(L) cotangent is an analysis call, d/dc_fk = w_k <s_f, T_k cotangent>).  grad_s has the
+    shape of `s`; grad_coefficients is (Nf, order + 1) float64 on the host.  DeviceArrays in (both) give a DeviceArray
+    grad_s out: the panels never leave the device, only the cross-moments come back."""
+    from . import engine
+    coefficients = coefficients or compute_cheby_coeff
+    G, Nf = bank.G, bank.Nf
+    on_device = isinstance(s, engine.DeviceArray)
+    if on_device != isinstance(cotangent, engine.DeviceArray):
+        raise TypeError("the signal and the cotangent must both be host arrays or both be DeviceArrays")
+    if not on_device:
+        s = G._check_signal(s)
+    N, nsig, nfeat = _cube_shape(G, Nf, s.shape)
+    synthesis = nfeat != 1
+    nfout = 1 if synthesis else Nf
+    coeffs = _as_coeff_matrix(coefficients(bank, m=order))
+    dev = _device_graph_of(G)
+    if on_device:
+        for a in (s, cotangent):
+            if not hasattr(dev, "cheby_filter_dev") or a.ctx is not dev.ctx:
+                raise ValueError("the DeviceArray does not live on the context of this graph's device Laplacian")
+            if a.dtype != dev.dtype:
+                raise ValueError("the DeviceArray holds {} but the graph computes in {}".format(a.dtype, dev.dtype))
+        if cotangent.cube[0] != N or cotangent.size != N * nsig * nfout:
+            raise ValueError("the cotangent must have the shape the filter call returns, got {}".format(cotangent.shape))
+        x_ptr, keep_x = s.planes(nsig, nfeat)
+        g_ptr, keep_g = cotangent.planes(nsig, nfout)
+        out = engine.DeviceArray.empty(dev.ctx, (N, nsig, nfeat), dev.dtype)
+        out.shape = tuple(s.shape)
+        grad_c, ms = np.zeros(coeffs.shape), 0.0
+        if N * nsig:
+            grad_c, ms = _vjp_device(dev, G.lmax, coeffs, x_ptr, g_ptr, out.ptr, nsig, synthesis)
+        del keep_x, keep_g
+        _record_timing(G, ms)
+        return out, grad_c
+    cot = np.asanyarray(cotangent)
+    if np.iscomplexobj(s) or np.iscomplexobj(cot):
+        raise TypeError("complex signals are not supported by the Chebyshev path")
+    if cot.size != N * nsig * nfout or (cot.ndim and cot.shape[0] != N):
+        raise ValueError("the cotangent must have the shape the filter call returns, got {}".format(cot.shape))
+    cube, cot = s.reshape(N, nsig, nfeat), cot.reshape(N, nsig, nfout)
+    if synthesis:
+        gx, grad_c, ms = _vjp_host(dev, G.lmax, coeffs, np.ascontiguousarray(np.moveaxis(cube, 2, 0)), cot[:, :, 0], True)
+        gx = np.moveaxis(gx.reshape(Nf, N, nsig), 0, 2)
+    else:
+        gx, grad_c, ms = _vjp_host(dev, G.lmax, coeffs, cube[:, :, 0], np.ascontiguousarray(np.moveaxis(cot, 2, 0)), False)
+    _record_timing(G, ms)
+    return np.ascontiguousarray(gx).reshape(s.shape), grad_c
+
+
 def lanczos_op(f, s, order=30):
     """Lanczos approximation of the filter bank `f` applied to `s` (approximations.py:228-277), on the GPU.
 
@@ -972,6 +1094,12 @@ class Filter:
         analysis call (default: filters.EVALUATION, see set_evaluation and newton_guard).
         """
         return filter_signals(self, s, method, order, devices, evaluation=evaluation)
+
+    def filter_vjp(self, s, cotangent, order=30):
+        """(grad_s, grad_coefficients) of ``self.filter(s, 'chebyshev', order)`` for a cotangent of the shape that
+        call returns, in analysis and in synthesis (filter_signals_vjp): how a loss that reads the filtered signals
+        changes with `s` and with the bank's (Nf, order + 1) Chebyshev coefficients."""
+        return filter_signals_vjp(self, s, cotangent, order)
 
     def analyze(self, s, method="chebyshev", order=30, devices=None):
         shape = _shape_of(s)

@@ -1,0 +1,200 @@
+"""Differentiable Chebyshev filtering for PyTorch: ``cheby_filter`` (a torch.autograd.Function behind a plain
+function) and ``ChebyshevFilter`` (a torch.nn.Module whose parameter is the coefficient matrix) - ChebNet-style
+spectral graph convolutions, or fitting a filter to input / output pairs, on the engine's recurrence.
+
+Forward is one gspx_cheby_filter_dev call; backward is filters._vjp_device: one synthesis call with the same
+coefficients for the signal's gradient (L is symmetric) and one gspx_cheby_cross_moments_dev call for the
+coefficients' gradient.  No second derivatives, no gradient with respect to lmax or the graph's weights.
+
+IMPORT ORDER.  torch ships its own HIP runtime (libamdhip64.so) and libgspx links against the ROCm installation's copy
+of the same SONAME.  Whichever of the two is loaded first serves both libraries: this module imports torch at its
+top, before anything loads libgspx (pygsp_amd loads it lazily, at the first context or graph), so a process that
+imports ``pygsp_amd.nn`` before creating a context has ONE runtime, and a tensor's ``data_ptr()`` means the same thing
+to both.  A process that has already loaded libgspx when torch arrives holds TWO runtimes; a pointer of torch's is then
+unknown to libgspx's, gspx_ptr_device says so, and every call is staged through host arrays instead - correct, slower,
+with one warning per process.  A pointer the library's runtime does not know never reaches a kernel.
+(The order to avoid, seen on the card: libgspx LOADED but not yet used, then torch imported, then the first context -
+torch's bundled runtime had claimed the GPU by then and gspx_ctx_create found no device.  A process that wants both
+and cannot import this module first makes one libgspx call that touches HIP, e.g. ``_capi.device_count()``, before it
+imports torch; tests/test_autograd_host.py does.)
+
+No other module of the package imports torch."""
+import torch  # first: see IMPORT ORDER above
+
+import ctypes
+import warnings
+
+import numpy as np
+
+from . import _capi, filters
+
+_warned = False
+last_path = None  # "zero_copy" | "staged": how the most recent forward or backward pass reached the engine
+
+
+def _np_dtype(t):
+    if t.dtype == torch.float64:
+        return np.dtype(np.float64)
+    if t.dtype == torch.float32:
+        return np.dtype(np.float32)
+    raise TypeError("cheby_filter takes float64 or float32 signals, got {}".format(t.dtype))
+
+
+def ptr_device(pointer):
+    """The device ordinal of `pointer` (an int) as libgspx's HIP runtime sees it, or None when that runtime does not
+    know it as device memory (gspx_ptr_device: launches nothing, touches no memory)."""
+    dev = ctypes.c_int(-1)
+    rc = _capi.load().gspx_ptr_device(ctypes.c_void_p(int(pointer)), ctypes.byref(dev))
+    return dev.value if rc == _capi.OK else None
+
+
+def _zero_copy(dev, tensors):
+    """Whether the device entry points may read and write `tensors` (contiguous, on the GPU) in place: `dev` is a real
+    engine.DeviceGraph and libgspx's own runtime places every pointer on the context's device.  Warns once per process
+    when it does not."""
+    global _warned, last_path
+    last_path = "staged"
+    if not hasattr(dev, "cheby_filter_dev") or not hasattr(dev, "ctx"):
+        return False
+    bad = [t.data_ptr() for t in tensors if ptr_device(t.data_ptr()) != dev.ctx.device]
+    if not bad:
+        last_path = "zero_copy"
+        return True
+    if not _warned:
+        _warned = True
+        warnings.warn("pygsp_amd.nn: the HIP runtime of libgspx does not know torch's device pointer {:#x} as memory of "
+                      "device {} ({}) - the process holds two HIP runtimes because libgspx was loaded before torch, or "
+                      "the tensor lives elsewhere.  Calls are staged through host arrays: correct, but slow.  Import "
+                      "pygsp_amd.nn BEFORE creating a context or a device graph."
+                      .format(bad[0], dev.ctx.device, _capi.last_error()), RuntimeWarning, stacklevel=3)
+    return False
+
+
+def _device_of(G, x):
+    """The graph's device build for x's dtype; a GPU tensor must live on that build's GPU."""
+    dev = G.device_graph(_np_dtype(x))
+    if x.is_cuda and hasattr(dev, "ctx") and x.device.index != dev.ctx.device:
+        raise ValueError("the signal lives on {} but the graph on GPU {}".format(x.device, dev.ctx.device))
+    return dev
+
+
+def _host(t):
+    global last_path
+    last_path = "staged"
+    return np.ascontiguousarray(t.detach().cpu().numpy())
+
+
+class _ChebyFilter(torch.autograd.Function):
+    """y[n, j, f] = (p_f(L) x)[n, j],  p_f = c_f0 / 2 + sum_{k >= 1} c_fk T_k(Lt).
+
+    ORDERING of the zero-copy path.  Before a device call the tensor's producer stream (torch's current stream on that
+    GPU) is synchronised, so every input - and the freshly allocated output - is at rest.  After it nothing more is
+    needed: gspx_cheby_filter_dev and gspx_cheby_cross_moments_dev each end with their own hipStreamSynchronize of the
+    context's stream (run_batches, the replay branch of filter_dev_t, the download of the moments), so the call has
+    finished on the device when it returns and torch may read the output from any stream."""
+
+    @staticmethod
+    def forward(ctx, coeffs, x, G, lmax):
+        if coeffs.dim() not in (1, 2) or x.dim() not in (1, 2):
+            raise ValueError("coeffs must be (Nf, M) or (M,) and x (N,) or (N, Nsig), got {} and {}"
+                             .format(tuple(coeffs.shape), tuple(x.shape)))
+        dev = _device_of(G, x)
+        lmax = float(G.lmax if lmax is None else lmax)
+        c = np.ascontiguousarray(coeffs.detach().to("cpu", torch.float64).numpy()).reshape(-1, coeffs.shape[-1])
+        Nf, N = c.shape[0], x.shape[0]
+        xc = x.detach().reshape(N, -1).contiguous()
+        nsig = xc.shape[1]
+        ctx.save_for_backward(xc)
+        ctx.call = (G, dev, lmax, c, tuple(coeffs.shape), coeffs.dtype, coeffs.device, tuple(x.shape))
+        y = None
+        if xc.is_cuda and xc.numel():
+            y = torch.empty((Nf, N, nsig), dtype=xc.dtype, device=xc.device)
+            torch.cuda.current_stream(xc.device).synchronize()
+            if _zero_copy(dev, (xc, y)):
+                dev.cheby_filter_dev(c, xc.data_ptr(), y.data_ptr(), nsig, lmax, _capi.ANALYSIS)
+            else:
+                y = None
+        if y is None:
+            yh, _ = dev.cheby_filter(c, _host(xc), lmax, _capi.ANALYSIS)
+            y = torch.from_numpy(np.ascontiguousarray(yh).reshape(Nf, N, nsig)).to(device=xc.device, dtype=xc.dtype)
+        return y.permute(1, 2, 0)  # the planes the engine writes, viewed as (vertex, signal, filter): no copy
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        (xc,) = ctx.saved_tensors
+        G, dev, lmax, c, c_shape, c_dtype, c_device, x_shape = ctx.call
+        need_c, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        Nf, M = c.shape
+        N, nsig = xc.shape
+        g = grad_y.detach().to(xc.dtype).permute(2, 0, 1).contiguous()  # planes [filter][vertex][signal]
+        grad_c = grad_x = None
+        done = False
+        if xc.is_cuda and xc.numel():
+            gx = torch.empty((N, nsig), dtype=xc.dtype, device=xc.device) if need_x else None
+            torch.cuda.current_stream(xc.device).synchronize()
+            if _zero_copy(dev, [t for t in (xc, g, gx) if t is not None]):
+                grad_c, _ = filters._vjp_device(dev, lmax, c, xc.data_ptr(), g.data_ptr(),
+                                                gx.data_ptr() if need_x else 0, nsig, False, need_x, need_c)
+                grad_x, done = gx, True
+        if not done:
+            gh = _host(g)
+            if need_x:
+                gxh, _ = dev.cheby_filter(c, gh, lmax, _capi.SYNTHESIS)
+                grad_x = torch.from_numpy(np.ascontiguousarray(gxh).reshape(N, nsig)).to(device=xc.device, dtype=xc.dtype)
+            if need_c:
+                cross, _ = dev.cheby_cross_moments(_host(xc), gh, lmax, M)
+                grad_c = filters._grad_coefficients(cross)
+        if need_c:
+            grad_c = torch.from_numpy(np.ascontiguousarray(grad_c)).to(device=c_device, dtype=c_dtype).reshape(c_shape)
+        if need_x:
+            grad_x = grad_x.reshape(x_shape)
+        return (grad_c if need_c else None), (grad_x if need_x else None), None, None
+
+
+def cheby_filter(G, coeffs, x, lmax=None):
+    """The Chebyshev filters `coeffs` of the Laplacian of `G` applied to `x`, differentiable in both.
+
+    coeffs: tensor (Nf, M) or (M,), M >= 2, on any device (the engine reads coefficients from the host).  x: tensor
+    (N,) or (N, Nsig), float64 or float32, on the CPU or on the GPU of G's context; the graph's device build of that
+    dtype (``G.device_graph(dtype)``) computes.  lmax: G.lmax unless given.  Returns (N, Nsig, Nf) on x's device,
+    a permuted view of the planes the engine writes.
+
+    A GPU tensor goes in by ``data_ptr()`` and the result is written into a ``torch.empty`` tensor in place, if
+    libgspx's HIP runtime knows those pointers (see the module docstring); otherwise, and for CPU tensors, the call
+    is staged through host arrays.  ``backward`` (once differentiable) returns the gradient of `coeffs` in its dtype
+    and on its device and the gradient of `x`; only the device calls of the gradients that are needed run."""
+    return _ChebyFilter.apply(coeffs, x, G, lmax)
+
+
+class ChebyshevFilter(torch.nn.Module):
+    """A learnable bank of `n_filters` Chebyshev filters of order `order` on `G`: one float64 Parameter ``coeffs`` of
+    shape (n_filters, order + 1), ``forward(x)`` = ``cheby_filter(G, coeffs, x)``.  `init`: a filters.Filter bank of
+    n_filters kernels whose compute_cheby_coeff values start the coefficients; without it every filter starts as the
+    identity (c_0 = 2: the series reads c_0 / 2)."""
+
+    def __init__(self, G, n_filters=1, order=30, init=None):
+        super().__init__()
+        self.G, self.order = G, int(order)
+        if self.order < 1:
+            raise ValueError("order must be at least 1")
+        if init is None:
+            start = np.zeros((int(n_filters), self.order + 1))
+            start[:, 0] = 2.0
+        else:
+            start = filters._as_coeff_matrix(filters.compute_cheby_coeff(init, m=self.order))
+            if start.shape[0] != int(n_filters):
+                raise ValueError("init holds {} filters, n_filters is {}".format(start.shape[0], n_filters))
+        # float64 whatever torch's default dtype: the engine reads coefficients as float64 on the host for both compute
+        # dtypes, and an alternating Chebyshev series does not forgive rounding them (``.float()`` converts as usual)
+        self.coeffs = torch.nn.Parameter(torch.from_numpy(start))
+
+    @property
+    def n_filters(self):
+        return self.coeffs.shape[0]
+
+    def forward(self, x):
+        return cheby_filter(self.G, self.coeffs, x)
+
+    def extra_repr(self):
+        return "n_filters={}, order={}".format(self.n_filters, self.order)

@@ -38,6 +38,47 @@ def cheby_moments(G, x, order=30):
     return m[:, 0] if one else m
 
 
+def cheby_cross_moments(G, x, z, order=30):
+    """sum_n z_f[n, j] (T_k(Lt) x)[n, j] for k <= order: the recurrence on `x` dotted with the foreign panels `z`
+    (gspx_cheby_cross_moments_dev; the coefficient gradient of filters.cheby_op_vjp).  `x`: (N,) or (N, Nsig); `z`:
+    (N,), (N, Nsig) or (Nf, N, Nsig), N and Nsig those of `x`.  Both host arrays, or both engine.DeviceArrays of the
+    graph's compute dtype - a device `z` of Nf planes is one with Nf features, cube (N, Nsig, Nf).  Returns float64
+    (Nf, order + 1, Nsig), without the Nf axis for a `z` of fewer than three dimensions and without the Nsig axis
+    for a 1-D `x`.  Uses G.lmax."""
+    dev = filters._device_graph_of(G)
+    M = int(order) + 1
+    on_device = [isinstance(a, engine.DeviceArray) for a in (x, z)]
+    if any(on_device):
+        if not all(on_device):
+            raise TypeError("x and z must both be host arrays or both be DeviceArrays")
+        n, nsig, nfeat = x.cube
+        if nfeat != 1 or n != G.N:
+            raise ValueError("cheby_cross_moments takes (N,) or (N, Nsig) signals, got a device array of cube {}"
+                             .format(x.cube))
+        if z.cube[:2] != (n, nsig):
+            raise ValueError("z of cube {} does not match x of cube {}".format(z.cube, x.cube))
+        for a in (x, z):
+            if np.dtype(a.dtype) != np.dtype(dev.dtype):
+                raise TypeError("the device array holds {}, the graph computes in {}".format(a.dtype,
+                                                                                            np.dtype(dev.dtype)))
+        one, bank = len(x.shape) == 1, z.cube[2] != 1 or len(z.shape) == 3
+        m, ms = dev.cheby_cross_moments_dev(x.ptr, z.ptr, nsig, z.cube[2], G.lmax, M)
+    else:
+        x, z = np.asarray(x), np.asarray(z)
+        if x.ndim not in (1, 2) or x.shape[0] != G.N:
+            raise ValueError("cheby_cross_moments takes (N,) or (N, Nsig) signals, got {}".format(x.shape))
+        one, bank = x.ndim == 1, z.ndim == 3
+        x2 = x.reshape(G.N, -1)
+        if z.ndim not in (1, 2, 3) or (z.shape[1:] if bank else z.shape[:1] + (z.size // max(G.N, 1),)) != x2.shape:
+            raise ValueError("z must be (N,), (N, Nsig) or (Nf, N, Nsig) for x {}, got {}".format(x.shape, z.shape))
+        m, ms = dev.cheby_cross_moments(x2, z.reshape((-1,) + x2.shape), G.lmax, M)
+    filters._record_timing(G, ms)
+    m = np.asarray(m, dtype=np.float64)
+    if one:
+        m = m[:, :, 0]
+    return m if bank else m[0]
+
+
 def probes(n_vertices, n_vectors, seed):
     """The random +-1 (Rademacher) probe vectors of the trace estimate, (n_vertices, n_vectors) float64."""
     return np.random.default_rng(seed).integers(0, 2, size=(n_vertices, n_vectors)) * 2.0 - 1.0

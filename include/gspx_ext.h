@@ -422,6 +422,30 @@ int gspx_cheby_cross_moments_dev(gspx_graph* g, double lmax, int M, int64_t Nsig
  * Launches nothing and touches no memory: the gate a binding puts in front of pointers it did not allocate. */
 int gspx_ptr_device(const void* p, int* device);
 
+/* Chebyshev graph convolution of DEVICE signals (the ChebNet layer; pygsp_amd.filters.cheby_conv, pygsp_amd.nn.ChebConv):
+ *   y[n][b][:] = sum_{k < M} (T_k(Lt) x)[n][b][:] theta[k],   theta[k] a Fin x Fout matrix,
+ * a PLAIN sum: theta[0] is not halved (theta[k] = c_k I for k >= 1 and theta[0] = (c_0 / 2) I gives gspx_cheby_filter_dev
+ * of one filter c).  theta: HOST, M x Fin x Fout doubles, row-major, finite.  x_dev: N x B*Fin, y_dev: N x B*Fout;
+ * row-major, the graph's compute dtype, the CALLER's vertex order, the feature index fastest: element (n, b, i) at
+ * n*B*Fin + b*Fin + i.  M Clenshaw steps on panels of B*Fout columns - the steps of a synthesis call with one input
+ * panel - each fed by one dense product x theta[k] on the matrix cores (k_group_mix), in the compute dtype.  Column
+ * batches hold whole samples.  L is symmetric: the same call with every theta[k] transposed (Fin and Fout swapped) is
+ * the derivative with respect to x.
+ * GSPX_ERR_COEFF for M < 2; GSPX_ERR_INVALID for M > 256, Fin or Fout outside 1..128, B < 0, lmax not positive and
+ * finite (all checked before the graph is looked at), a null graph or pointer, x_dev == y_dev, a non-finite theta, or
+ * B*max(Fin, Fout) beyond the signal-count limit.  B == 0: nothing happens; N == 0: nothing is written. */
+int gspx_cheby_conv_dev(gspx_graph* g, double lmax, int M, int Fin, int Fout, const double* theta, int64_t B,
+                        const void* x_dev, void* y_dev, double* kernel_ms);
+/* The cross-Grams of the recurrence on x with a second signal z: out (HOST, M x Fin x Fout fp64, row-major)
+ *   out[k][i][o] = sum_{n, b} (T_k(Lt) x)[n][b][i] * z[n][b][o],   k < M,
+ * the derivative of gspx_cheby_conv_dev's output with respect to theta when z is the cotangent.  x_dev: N x B*Fin,
+ * z_dev: N x B*Fout, laid out as above.  M - 1 recurrence steps into M kept slots, then one Gram product per slot on the
+ * fp64 matrix cores (k_slot_cross_gram): every product and sum is fp64 for both graph dtypes, there are no atomics, and
+ * identical calls give identical bits.  Column batches hold whole samples; their Grams are added in batch order.
+ * Errors as gspx_cheby_conv_dev (no theta, and z_dev may be x_dev).  B == 0: nothing happens; N == 0: zeros. */
+int gspx_cheby_cross_grams_dev(gspx_graph* g, double lmax, int M, int Fin, int Fout, int64_t B, const void* x_dev,
+                               const void* z_dev, double* out, double* kernel_ms);
+
 /* PCI address ("0000:c1:00.0", NUL-terminated) of HIP device `device`: what a host driver needs to find the NUMA
  * node the GPU hangs off (/sys/bus/pci/devices/<address>/numa_node) and pin the thread - and the packing threads
  * libgspx starts from it - that feeds this GPU to the cores next to it (pygsp_amd.multi). */

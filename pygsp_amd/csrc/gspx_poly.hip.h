@@ -1,6 +1,7 @@
 // gspx_poly.hip.h - the polynomial-filter pipeline (replaces approximations.py:58-114 cheby_op and the synthesis loop of
 // filter.py:313-322): step plans, launch shapes and the launch_* family, the work panels of a batch, the column-batch
-// driver (batch_width, run_batches), the three batch runners (run_batch, run_synthesis_batch, run_program_batch),
+// driver (batch_width, run_batches), the three batch runners (run_batch, run_synthesis_batch, run_program_batch) and the
+// Clenshaw step the synthesis and the graph convolution (gspx_conv.hip.h) share (clenshaw_step),
 // filter_dev_t / program_dev_t / sqnorms_dev_t / moments_dev_t, device_call / host_call and the gspx_cheby_* /
 // gspx_newton_* / gspx_poly_program* entry points.
 // After gspx_graph.hip.h (ensure_factor, ensure_s1nat) and gspx_hostpipe.hip.h (host_call hands large calls to it).
@@ -449,6 +450,14 @@ static int launch_slot_cross_dots(gspx_ctx* ctx, const T* slots, int M, size_t s
   return GSPX_OK;
 }
 
+// What a header further down does with the kept slots of a deferred batch instead of its outputs (gspx_conv.hip.h: the
+// cross-Grams): fn(ctx, slots, M, slot stride, slot pitch, N, batch width, the internal row -> caller's row map, arg,
+// stream), launched where the combine would be.
+struct SlotsUse {
+  int (*fn)(gspx_ctx*, const void*, int, size_t, unsigned, int, unsigned, const int*, const void*, hipStream_t);
+  const void* arg;
+};
+
 // ------------------------------------------------------------------------------------------------
 // the filter
 // ------------------------------------------------------------------------------------------------
@@ -724,7 +733,7 @@ template <typename T>
 static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp, const T* x,
                      unsigned ldx, T* y, unsigned ldy, unsigned ld, bool deferred,
                      bool acc_existing, bool final_to_y, size_t& ev_idx, const SqNorms* sq = nullptr,
-                     const SlotDots* sd = nullptr, const CrossDots* cd = nullptr) {
+                     const SlotDots* sd = nullptr, const CrossDots* cd = nullptr, const SlotsUse* use = nullptr) {
   gspx_ctx* ctx = g->ctx;
   const Options& opt = ctx->opt;
   hipStream_t st = ctx->stream;
@@ -863,6 +872,8 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
     CHK(launch_slot_dots<T>(ctx, slots, M, SU, ldw, N, ld, *sd, st));
   } else if (deferred && cd) {  // the slots' inner products with the caller's planes, read through the vertex order
     CHK(launch_slot_cross_dots<T>(ctx, slots, M, SU, ldw, N, ld, perm, *cd, st));
+  } else if (deferred && use) {  // whatever the caller does with the kept slots
+    CHK(use->fn(ctx, slots, M, SU, ldw, N, ld, perm, use->arg, st));
   } else if (deferred) {
     launch_combine<T>(slots, M, SU, ctx->ws_w.as<T>(), M, nf, N, ld, y, ldy, (size_t)N * ldy, perm,
                       padded ? 1 : vec_cap(shape.vec, ldy, y), st, ldw);
@@ -874,6 +885,61 @@ static int run_batch(gspx_graph* g, int nf, int M, const std::vector<double>& cp
     HIPCHK(hipEventRecord(ev[3], st));
     HIPCHK(hipGetLastError());
   }
+  return GSPX_OK;
+}
+
+// One step of the vector-coefficient Clenshaw recurrence on a batch's work panels (run_synthesis_batch, and
+// run_conv_batch of gspx_conv.hip.h):  b_k = u_k + F b_{k+1} - b_{k+2}, out = u_0 + (F/2) b_1 - b_2, with
+// u_k = sum_f wts[f] inp[f] over nin input panels of the work panels' geometry.  `first` is the panel step K gathers
+// from with scale 0 (b_K = u_K needs no product: any valid panel).  B: the two recurrence panels; step 0 stores into y
+// on the tile_direct and plain routes and leaves b_0 in B[0] on the padded one.  a: step_base of the batch.
+template <typename T>
+static int clenshaw_step(gspx_graph* g, const Options& opt, const WorkPanels& wp, const Shape& shape, StepArgs<T>& a,
+                         int k, int K, const T* inp, const T* wts, int nin, const T* first, T* const B[2], T* y,
+                         unsigned ldy, hipStream_t st) {
+  gspx_ctx* ctx = g->ctx;
+  const bool has_b2 = (k + 2 <= K);
+  if (wp.tile_direct || wp.padded) {
+    TileArgs<T> t{};
+    t.cur = (k == K) ? first : B[(k + 1) & 1];
+    t.old = (k < K && has_b2) ? B[k & 1] : t.cur;
+    t.out = B[k & 1];
+    t.racc = B[0];  // unused (flush == 0)
+    t.y = y;
+    t.ldy = ldy;
+    t.perm = a.perm;
+    t.scale = (k == K) ? T(0) : (k == 0 ? T(0.5) : T(1));
+    t.gamma = (k < K && has_b2) ? T(-1) : T(0);
+    t.beta = T(0);
+    t.inp = inp;
+    t.wts = wts;
+    t.nin = nin;
+    t.flush = 0;
+    t.final = (k == 0 && !wp.padded) ? 1 : 0;  // padded rows: b_0 stays in B[0] and is copied out by the caller
+    t.reverse = (opt.alternate_sweep && (k & 1)) ? 1 : 0;
+    return launch_step_tile<T>(g, opt, t, wp.ldw, st);
+  }
+  a.nf = 1;
+  a.nin = nin;
+  a.racc = const_cast<T*>(inp);
+  a.wts = wts;
+  a.final = (k == 0) ? 1 : 0;
+  a.flush = 0;
+  if (k == K) {  // b_K = u_K : no product needed (scale 0 on any valid panel)
+    a.cur = first;
+    a.old = first;
+    a.out = B[k & 1];
+    a.scale = T(0);
+    a.gamma = T(0);
+  } else {
+    a.cur = B[(k + 1) & 1];
+    a.out = B[k & 1];
+    a.old = has_b2 ? B[k & 1] : a.cur;
+    a.gamma = has_b2 ? T(-1) : T(0);
+    a.scale = (k == 0) ? T(0.5) : T(1);
+  }
+  a.reverse = (opt.alternate_sweep && (k & 1)) ? 1 : 0;
+  launch_step<T>(ctx, a, shape, opt, st, g->coff.as<unsigned>());
   return GSPX_OK;
 }
 
@@ -930,54 +996,9 @@ static int run_synthesis_batch(gspx_graph* g, int nf, int M, const std::vector<d
 
   CHK(prepare_coff<T>(g, shape, ld, st));
   StepArgs<T> a = step_base<T>(g, ld, y, ldy);
-  a.nf = 1;
-  a.nin = nf;
-  a.racc = S;
   // (nf input panels: the buffer window of the tile kernel spans all of them)
-  const bool tile_ok = wp.tile_direct || padded;
-  for (int k = K; k >= 0; --k) {
-    if (tile_ok) {
-      TileArgs<T> t{};
-      const bool has_b2 = (k + 2 <= K);
-      t.cur = (k == K) ? S : B[(k + 1) & 1];
-      t.old = (k < K && has_b2) ? B[k & 1] : t.cur;
-      t.out = B[k & 1];
-      t.racc = B[0];  // unused (flush == 0)
-      t.y = y;
-      t.ldy = ldy;
-      t.perm = perm;
-      t.scale = (k == K) ? T(0) : (k == 0 ? T(0.5) : T(1));
-      t.gamma = (k < K && has_b2) ? T(-1) : T(0);
-      t.beta = T(0);
-      t.inp = S;
-      t.wts = ctx->ws_w.as<T>() + (size_t)k * nf;
-      t.nin = nf;
-      t.flush = 0;
-      t.final = (k == 0 && !padded) ? 1 : 0;  // padded rows: b_0 stays in B[0] and is copied out below
-      t.reverse = (opt.alternate_sweep && (k & 1)) ? 1 : 0;
-      CHK(launch_step_tile<T>(g, opt, t, ldw, st));
-      continue;
-    }
-    a.wts = ctx->ws_w.as<T>() + (size_t)k * nf;
-    a.final = (k == 0) ? 1 : 0;
-    a.flush = 0;
-    if (k == K) {  // b_K = u_K : no product needed (scale 0 on any valid panel)
-      a.cur = S;
-      a.old = S;
-      a.out = B[k & 1];
-      a.scale = T(0);
-      a.gamma = T(0);
-    } else {
-      a.cur = B[(k + 1) & 1];
-      a.out = B[k & 1];
-      const bool has_b2 = (k + 2 <= K);
-      a.old = has_b2 ? B[k & 1] : a.cur;
-      a.gamma = has_b2 ? T(-1) : T(0);
-      a.scale = (k == 0) ? T(0.5) : T(1);
-    }
-    a.reverse = (opt.alternate_sweep && (k & 1)) ? 1 : 0;
-    launch_step<T>(ctx, a, shape, opt, st, g->coff.as<unsigned>());
-  }
+  for (int k = K; k >= 0; --k)
+    CHK(clenshaw_step<T>(g, opt, wp, shape, a, k, K, S, ctx->ws_w.as<T>() + (size_t)k * nf, nf, S, B, y, ldy, st));
   HIPCHK(hipEventRecord(ev[2], st));
   if (padded) {
     const unsigned nbp = (unsigned)std::min<size_t>(((size_t)N * ld + 255) / 256, 65536);

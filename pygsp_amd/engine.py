@@ -552,6 +552,14 @@ def _lap_code(lap_type):
     return _capi.LAP_COMBINATORIAL if lap_type == "combinatorial" else _capi.LAP_NORMALIZED
 
 
+def _theta_stack(theta):
+    """(M, Fin, Fout) float64, contiguous: the matrix coefficients of a Chebyshev graph convolution."""
+    th = np.ascontiguousarray(theta, dtype=np.float64)
+    if th.ndim != 3:
+        raise ValueError("theta must be (M, Fin, Fout), got {}".format(th.shape))
+    return th
+
+
 def _coeff_matrix(coeffs):
     """Chebyshev coefficients as the contiguous float64 (Nf, M) matrix libgspx reads; a vector is one filter."""
     return np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
@@ -1042,6 +1050,61 @@ class DeviceGraph:
                 bx.upload(x)
                 bz.upload(z)
             return self.cheby_cross_moments_dev(bx.ptr, bz.ptr, x.shape[1], z.shape[0], lmax, M)
+
+    def cheby_conv_dev(self, theta, x_ptr, y_ptr, batch, lmax):
+        """The Chebyshev graph convolution y[n, b, :] = sum_k (T_k(Lt) x)[n, b, :] theta[k] of the device signals at
+        x_ptr (N x batch*Fin) into y_ptr (N x batch*Fout), theta (M, Fin, Fout) float64 on the host, a plain sum
+        (gspx_cheby_conv_dev).  Returns device milliseconds of the call."""
+        th = _theta_stack(theta)
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_cheby_conv_dev, self._h, float(lmax), th.shape[0], th.shape[1], th.shape[2],
+                      _capi.ptr(th), int(batch), ctypes.c_void_p(x_ptr), ctypes.c_void_p(y_ptr), ctypes.byref(ms))
+        return ms.value
+
+    def cheby_conv(self, theta, x, lmax):
+        """cheby_conv_dev of a host array x (N, B, Fin): ((N, B, Fout) array in the graph's dtype, device
+        milliseconds); uploaded in the graph's dtype, freed afterwards."""
+        th = _theta_stack(theta)
+        x = self._samples(x, th.shape[1])
+        y = np.zeros((self.N, x.shape[1], th.shape[2]), dtype=self.dtype)
+        with self.ctx._temporaries() as t:
+            bx, by = t.alloc(x.nbytes), t.alloc(y.nbytes)
+            if x.nbytes:
+                bx.upload(x)
+            ms = self.cheby_conv_dev(th, bx.ptr, by.ptr, x.shape[1], lmax)
+            if y.nbytes:
+                y = by.download(y.shape, self.dtype)
+        return y, ms
+
+    def cheby_cross_grams_dev(self, x_ptr, z_ptr, batch, fin, fout, lmax, M):
+        """The cross-Grams of the recurrence on the device signals at x_ptr (N x batch*fin) with those at z_ptr
+        (N x batch*fout): ((M, fin, fout) float64 host array of sum_{n, b} (T_k(Lt) x)[n, b, i] z[n, b, o], device
+        milliseconds of the call) from M - 1 recurrence steps (gspx_cheby_cross_grams_dev)."""
+        out = np.zeros((max(int(M), 0), max(int(fin), 0), max(int(fout), 0)))
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_cheby_cross_grams_dev, self._h, float(lmax), int(M), int(fin), int(fout),
+                      int(batch), ctypes.c_void_p(x_ptr), ctypes.c_void_p(z_ptr), _capi.ptr(out), ctypes.byref(ms))
+        return out, ms.value
+
+    def cheby_cross_grams(self, x, z, lmax, M):
+        """cheby_cross_grams_dev of host arrays x (N, B, Fin) and z (N, B, Fout): uploaded in the graph's dtype, freed
+        afterwards."""
+        x = self._samples(x)
+        z = self._samples(z)
+        if z.shape[1] != x.shape[1]:
+            raise ValueError("x and z must hold the same samples, got {} and {}".format(x.shape, z.shape))
+        with self.ctx._temporaries() as t:
+            bx, bz = t.alloc(x.nbytes), t.alloc(z.nbytes)
+            if x.nbytes:
+                bx.upload(x)
+                bz.upload(z)
+            return self.cheby_cross_grams_dev(bx.ptr, bz.ptr, x.shape[1], x.shape[2], z.shape[2], lmax, M)
+
+    def _samples(self, x, features=None):
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        if x.ndim != 3 or x.shape[0] != self.N or (features is not None and x.shape[2] != features):
+            raise ValueError("input must be (N, B, {}), got {}".format("F" if features is None else features, x.shape))
+        return x
 
     def tune_placement(self, coeffs, x_ptr, y_ptr, nsig, lmax, candidates=6, stride_mb=0):
         """Draw `candidates` physical backings for the context's streamed workspaces and keep the one on which THIS call

@@ -635,6 +635,65 @@ def cheby_op_vjp(G, c, signal, cotangent, **kwargs):
     return gx.reshape(panel.shape), grad_c.reshape(np.shape(c) if np.ndim(c) else coeffs.shape)
 
 
+def _conv_arguments(G, theta, signal):
+    """(theta (M, Fin, Fout) float64, the signal as an (N, B, Fin) cube, the signal's shape) of a cheby_conv call."""
+    from . import engine
+    if isinstance(signal, engine.DeviceArray):
+        raise TypeError("cheby_conv takes host arrays: a DeviceArray keeps its planes as [feature][vertex][signal], "
+                        "the convolution reads (vertex, sample, feature) with the feature index fastest")
+    th = np.asarray(theta, dtype=np.float64)
+    if th.ndim != 3:
+        raise ValueError("theta must be (M, Fin, Fout), got {}".format(th.shape))
+    if th.shape[0] < 2:
+        raise TypeError("The coefficients have an invalid shape")
+    panel = G._check_signal(signal)
+    if np.iscomplexobj(panel):
+        raise TypeError("complex signals are not supported by the Chebyshev path")
+    if panel.ndim not in (2, 3) or panel.shape[0] != G.N or panel.shape[-1] != th.shape[1]:
+        raise ValueError("the signal must be (N, Fin) or (N, B, Fin) with N = {} and Fin = {}, got {}"
+                         .format(G.N, th.shape[1], panel.shape))
+    return np.ascontiguousarray(th), panel.reshape(G.N, -1, th.shape[1]), panel.shape
+
+
+def cheby_conv(G, theta, signal):
+    """The Chebyshev graph convolution (the ChebNet layer of Defferrard et al.) of `signal` on `G`:
+
+        Y[n, b, :] = sum_{k < M} (T_k(Lt) X)[n, b, :] theta[k],      theta[k] a Fin x Fout matrix.
+
+    The sum is PLAIN: theta[0] is not halved (theta[k] = c_k I for k >= 1 and theta[0] = (c_0 / 2) I is
+    ``cheby_op(G, c, signal)``).  theta: (M, Fin, Fout), M >= 2, read as float64; signal: host array (N, Fin) or
+    (N, B, Fin), vertex first.  Returns float64 (N, Fout) or (N, B, Fout).  One gspx_cheby_conv_dev call: M Clenshaw
+    steps on B Fout columns, each fed by one dense product X theta[k] on the device.  An engine.DeviceArray is refused
+    (TypeError): its planes are laid out [feature][vertex][signal]."""
+    th, cube, shape = _conv_arguments(G, theta, signal)
+    y, ms = _device_graph_of(G).cheby_conv(th, cube, G.lmax)
+    _record_timing(G, ms)
+    return np.asarray(y, dtype=np.float64).reshape(shape[:-1] + (th.shape[2],))
+
+
+def cheby_conv_vjp(G, theta, signal, cotangent):
+    """Vector-Jacobian product of ``cheby_conv(G, theta, signal)`` for a cotangent of the shape that call returns: the
+    pair (grad_signal, grad_theta) with
+
+        grad_signal = cheby_conv(G, theta transposed per order, cotangent)       (L is symmetric: the same operator)
+        grad_theta[k, i, o] = sum_{n, b} (T_k(Lt) signal)[n, b, i] cotangent[n, b, o]     (gspx_cheby_cross_grams_dev)
+
+    both float64, of the shapes of `signal` and `theta`."""
+    th, cube, shape = _conv_arguments(G, theta, signal)
+    cot = np.asanyarray(cotangent)
+    if np.iscomplexobj(cot):
+        raise TypeError("complex signals are not supported by the Chebyshev path")
+    if cot.shape != shape[:-1] + (th.shape[2],):
+        raise ValueError("the cotangent must have the shape cheby_conv returns, {}, got {}"
+                         .format(shape[:-1] + (th.shape[2],), cot.shape))
+    cot = cot.reshape(G.N, -1, th.shape[2])
+    dev = _device_graph_of(G)
+    gx, ms1 = dev.cheby_conv(np.ascontiguousarray(th.transpose(0, 2, 1)), cot, G.lmax)
+    grams, ms2 = dev.cheby_cross_grams(cube, cot, G.lmax, th.shape[0])
+    _record_timing(G, ms1 + ms2)
+    return np.asarray(gx, dtype=np.float64).reshape(shape), np.asarray(grams, dtype=np.float64)
+
+
 def filter_signals_vjp(bank, s, cotangent, order=30, coefficients=None):
     """Vector-Jacobian product of ``filter_signals(bank, s, 'chebyshev', order)``: (grad_s, grad_coefficients) for a
     cotangent of the shape that call returns.  `s` goes through the shape rules of filter_signals; in synthesis the

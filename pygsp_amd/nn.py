@@ -1,10 +1,17 @@
-"""Differentiable Chebyshev filtering for PyTorch: ``cheby_filter`` (a torch.autograd.Function behind a plain
-function) and ``ChebyshevFilter`` (a torch.nn.Module whose parameter is the coefficient matrix) - ChebNet-style
-spectral graph convolutions, or fitting a filter to input / output pairs, on the engine's recurrence.
+"""Differentiable Chebyshev filtering and graph convolution for PyTorch, on the engine's recurrence.
 
-Forward is one gspx_cheby_filter_dev call; backward is filters._vjp_device: one synthesis call with the same
-coefficients for the signal's gradient (L is symmetric) and one gspx_cheby_cross_moments_dev call for the
-coefficients' gradient.  No second derivatives, no gradient with respect to lmax or the graph's weights.
+``cheby_filter`` (a torch.autograd.Function behind a plain function) and ``ChebyshevFilter`` (a torch.nn.Module whose
+parameter is the coefficient matrix) are PER-CHANNEL filtering: scalar coefficients c[f][k], every signal column
+filtered on its own, nothing mixes feature channels - fitting a filter to input / output pairs.  Forward is one
+gspx_cheby_filter_dev call; backward is filters._vjp_device: one synthesis call with the same coefficients for the
+signal's gradient (L is symmetric) and one gspx_cheby_cross_moments_dev call for the coefficients' gradient.
+
+``cheby_conv`` and ``ChebConv`` are the ChebNet layer (Defferrard et al.): matrix coefficients Theta_k (Fin x Fout),
+Y[n, b, :] = sum_k (T_k(Lt) X)[n, b, :] Theta_k, a plain sum.  Forward is one gspx_cheby_conv_dev call; backward is the
+same call with every Theta_k transposed for the signal's gradient and one gspx_cheby_cross_grams_dev call for Theta's.
+Only X is saved for backward, never the T_k X.
+
+No second derivatives, no gradient with respect to lmax or the graph's weights.
 
 IMPORT ORDER.  torch ships its own HIP runtime (libamdhip64.so) and libgspx links against the ROCm installation's copy
 of the same SONAME.  Whichever of the two is loaded first serves both libraries: this module imports torch at its
@@ -37,7 +44,7 @@ def _np_dtype(t):
         return np.dtype(np.float64)
     if t.dtype == torch.float32:
         return np.dtype(np.float32)
-    raise TypeError("cheby_filter takes float64 or float32 signals, got {}".format(t.dtype))
+    raise TypeError("the engine takes float64 or float32 signals, got {}".format(t.dtype))
 
 
 def ptr_device(pointer):
@@ -198,3 +205,120 @@ class ChebyshevFilter(torch.nn.Module):
 
     def extra_repr(self):
         return "n_filters={}, order={}".format(self.n_filters, self.order)
+
+
+class _ChebyConv(torch.autograd.Function):
+    """y[n, b, :] = sum_k (T_k(Lt) x)[n, b, :] theta[k].  The zero-copy gate, the synchronisation of the producer
+    stream before a device call and the staged fallback are _ChebyFilter's (see ORDERING there): both entry points end
+    with their own hipStreamSynchronize of the context's stream."""
+
+    @staticmethod
+    def forward(ctx, theta, x, G, lmax):
+        if theta.dim() != 3 or x.dim() not in (2, 3) or x.shape[-1] != theta.shape[1]:
+            raise ValueError("theta must be (M, Fin, Fout) and x (N, Fin) or (N, B, Fin), got {} and {}"
+                             .format(tuple(theta.shape), tuple(x.shape)))
+        dev = _device_of(G, x)
+        lmax = float(G.lmax if lmax is None else lmax)
+        th = np.ascontiguousarray(theta.detach().to("cpu", torch.float64).numpy())
+        M, fin, fout = th.shape
+        N = x.shape[0]
+        xc = x.detach().reshape(N, -1, fin).contiguous()
+        batch = xc.shape[1]
+        ctx.save_for_backward(xc)
+        ctx.call = (dev, lmax, th, theta.dtype, theta.device, tuple(x.shape))
+        y = None
+        if xc.is_cuda and xc.numel():
+            y = torch.empty((N, batch, fout), dtype=xc.dtype, device=xc.device)
+            torch.cuda.current_stream(xc.device).synchronize()
+            if _zero_copy(dev, (xc, y)):
+                dev.cheby_conv_dev(th, xc.data_ptr(), y.data_ptr(), batch, lmax)
+            else:
+                y = None
+        if y is None:
+            yh, _ = dev.cheby_conv(th, _host(xc), lmax)
+            y = torch.from_numpy(np.ascontiguousarray(yh).reshape(N, batch, fout)).to(device=xc.device, dtype=xc.dtype)
+        return y.reshape(tuple(x.shape[:-1]) + (fout,))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        (xc,) = ctx.saved_tensors
+        dev, lmax, th, th_dtype, th_device, x_shape = ctx.call
+        need_th, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        M, fin, fout = th.shape
+        N, batch = xc.shape[0], xc.shape[1]
+        g = grad_y.detach().to(xc.dtype).reshape(N, batch, fout).contiguous()
+        tht = np.ascontiguousarray(th.transpose(0, 2, 1))
+        grad_th = grad_x = None
+        done = False
+        if xc.is_cuda and xc.numel():
+            gx = torch.empty((N, batch, fin), dtype=xc.dtype, device=xc.device) if need_x else None
+            torch.cuda.current_stream(xc.device).synchronize()
+            if _zero_copy(dev, [t for t in (xc, g, gx) if t is not None]):
+                if need_x:
+                    dev.cheby_conv_dev(tht, g.data_ptr(), gx.data_ptr(), batch, lmax)
+                if need_th:
+                    grad_th, _ = dev.cheby_cross_grams_dev(xc.data_ptr(), g.data_ptr(), batch, fin, fout, lmax, M)
+                grad_x, done = gx, True
+        if not done:
+            gh = _host(g)
+            if need_x:
+                gxh, _ = dev.cheby_conv(tht, gh, lmax)
+                grad_x = torch.from_numpy(np.ascontiguousarray(gxh).reshape(N, batch, fin)).to(device=xc.device,
+                                                                                                dtype=xc.dtype)
+            if need_th:
+                grad_th, _ = dev.cheby_cross_grams(_host(xc), gh, lmax, M)
+        if need_th:
+            grad_th = torch.from_numpy(np.ascontiguousarray(grad_th, dtype=np.float64)).to(device=th_device, dtype=th_dtype)
+        if need_x:
+            grad_x = grad_x.reshape(x_shape)
+        return (grad_th if need_th else None), (grad_x if need_x else None), None, None
+
+
+def cheby_conv(G, theta, x, lmax=None):
+    """The Chebyshev graph convolution of `x` on `G` with the matrix coefficients `theta`, differentiable in both:
+    y[n, b, :] = sum_k (T_k(Lt) x)[n, b, :] theta[k], a plain sum (theta[0] is not halved).
+
+    theta: tensor (M, Fin, Fout), M >= 2, 1 <= Fin, Fout <= 128, on any device (the engine reads it from the host as
+    float64).  x: tensor (N, Fin) or (N, B, Fin) - VERTEX first, the engine's layout - float64 or float32, on the CPU
+    or on the GPU of G's context.  lmax: G.lmax unless given.  Returns (N, Fout) or (N, B, Fout) on x's device and in
+    x's dtype.  GPU tensors go in by ``data_ptr()`` when libgspx's HIP runtime knows them, through host arrays
+    otherwise (see the module docstring).  ``backward`` (once differentiable) returns the gradient of `theta` in its
+    dtype and on its device and the gradient of `x`; only the device calls of the gradients that are needed run."""
+    return _ChebyConv.apply(theta, x, G, lmax)
+
+
+class ChebConv(torch.nn.Module):
+    """The ChebNet layer on `G`: ``forward(x)`` = ``cheby_conv(G, theta, x) + bias`` with ``theta`` a float64 Parameter
+    of shape (order + 1, in_features, out_features) and ``bias`` an (out_features,) Parameter added by torch (none with
+    ``bias=False``).  theta starts Glorot-uniform over a fan-in of (order + 1) in_features (and a fan-out of
+    out_features), bias at zero.
+
+    LAYOUT: vertex first.  x is (N, in_features) or (N, B, in_features) and the result (N, out_features) or
+    (N, B, out_features), on x's device and in x's dtype - the engine's layout, NOT the batch-first one of PyTorch
+    Geometric; ``x.transpose(0, 1)`` of a batch-first tensor goes in (the call makes it contiguous).
+
+    theta is float64 whatever torch's default dtype, for the reason given for ChebyshevFilter.coeffs: the engine reads
+    coefficients as float64 on the host for both compute dtypes."""
+
+    def __init__(self, G, in_features, out_features, order, bias=True):
+        super().__init__()
+        self.G, self.order = G, int(order)
+        self.in_features, self.out_features = int(in_features), int(out_features)
+        if self.order < 1:
+            raise ValueError("order must be at least 1")
+        if self.in_features < 1 or self.out_features < 1:
+            raise ValueError("in_features and out_features must be at least 1")
+        fan_in = (self.order + 1) * self.in_features
+        bound = float(np.sqrt(6.0 / (fan_in + self.out_features)))
+        theta = torch.empty((self.order + 1, self.in_features, self.out_features), dtype=torch.float64)
+        self.theta = torch.nn.Parameter(theta.uniform_(-bound, bound))
+        self.bias = torch.nn.Parameter(torch.zeros(self.out_features)) if bias else None
+
+    def forward(self, x):
+        y = cheby_conv(self.G, self.theta, x)
+        return y if self.bias is None else y + self.bias.to(y.dtype)
+
+    def extra_repr(self):
+        return "in_features={}, out_features={}, order={}, bias={}".format(self.in_features, self.out_features, self.order,
+                                                                          self.bias is not None)

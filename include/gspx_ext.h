@@ -275,6 +275,40 @@ int gspx_schur_cg_dev(gspx_graph* g, double shift, const void* mask_dev, int64_t
 int gspx_kron_build(gspx_graph* g, double shift, const int32_t* ind_host, int64_t nk, double rtol, int64_t maxiter,
                     double* lnew_dev, gspx_knn** w_out, int32_t* iterations, double* kernel_ms);
 
+/* Learning the weights of a graph from smooth signals (pygsp_amd.graph_learning; the log-degree model of Kalofolias
+ * 2016 on a fixed pattern as in Kalofolias & Perraudin 2019; the definition is tests/graphlearn_helpers.py).
+ * Both calls take an fp64 graph created from W that carries its default edge list - edge e = (s, t), s < t, is edge e
+ * of Graph.get_edge_list, caller's vertex order; only the pattern is read.  A float32 graph, a graph created from L and a
+ * graph carrying a caller's edge list (a directed graph, self-loops) are GSPX_ERR_INVALID with the reason in the message.
+ * edge_sqdist: z_dev[e] = ||x_s - x_t||^2 (n_edges fp64, DEVICE) for x_dev an N x F fp64 row-major panel (DEVICE,
+ * caller's vertex order), 1 <= F <= 4096.  A group of lanes per edge (a power of two, at most a wavefront) walks the
+ * two rows with 16-byte loads where F is even and x_dev 16-byte aligned; every lane sums its columns in ascending
+ * order in fp64 and the lanes are combined by a fixed tree: every entry is within F eps of the exact sum, the same
+ * bits on every call.
+ * learn_log_degrees: argmin over w >= 0 (n_edges values) of 2 z^T w - a sum_i log (S w)_i + b ||w||^2, (S w)_i the sum
+ * of w over the edges at vertex i (vertices without edges take no part), by forward-backward-forward primal-dual
+ * iterations with the fixed step step_gamma (valid below 1 / (2 b + sqrt(2 dmax)), dmax the largest vertex degree), from
+ * w_0 = w0_dev (NULL: zeros) and v_0 = S w_0:
+ *   Y = w - g (2 b w + S^T v), y = v + g S w;  P = max(0, Y - 2 g z), p = prox(y);  Q = P - g (2 b P + S^T p),
+ *   q = p + g S P;  w <- w - Y + Q, v <- v - y + q;  prox(y) = (y - r) / 2 for y <= 0, -2 a g / (y + r) for y > 0,
+ *   r = sqrt(y^2 + 4 a g).
+ * Stops after iteration k when ||w_k - w_{k-1}|| <= tol ||w_k|| and ||v_k - v_{k-1}|| <= tol ||v_k|| (*crit = 1; a
+ * negative tol disables it) or k >= maxit (*crit = 5).  p_dev (n_edges fp64, DEVICE) receives P of the last iteration:
+ * non-negative with exact zeros; w_dev (may be NULL) the last w, for warm starts.  w_out (may be NULL): P as a symmetric
+ * adjacency, a handle of the kind gspx_linegraph_build returns under gspx_kron_build's contract - canonical CSR in the
+ * caller's vertex order, sorted columns, no diagonal, no stored zero, equal to its transpose bit for bit; no handle is
+ * left behind by a failing call.  HOST outputs: niter, crit, history_host (room for 4 maxit doubles): ||w_k - w_{k-1}||,
+ * ||w_k||, ||v_k - v_{k-1}||, ||v_k|| for k = 1 .. niter.  kernel_ms (may be NULL): the iterations, without the adjacency.
+ * GSPX_ERR_INVALID: a not positive or not finite, b negative, step_gamma not positive, maxit outside 1..1e7, NaN tol,
+ * null pointers with n_edges > 0, and - after one small device pass - a NaN or negative entry of z.  n_edges = 0
+ * returns at once with niter 0 (and an empty adjacency).  Three launches per iteration (edge pass, vertex pass, a
+ * one-workgroup rule kernel), the done flag read by the host every 4 iterations, no atomics: the same inputs give the
+ * same bits on every call. */
+int gspx_edge_sqdist_dev(gspx_graph* g, int64_t F, const void* x_dev, void* z_dev, double* kernel_ms);
+int gspx_learn_log_degrees_dev(gspx_graph* g, const void* z_dev, double a, double b, double step_gamma, double tol,
+                               int64_t maxit, const void* w0_dev, void* p_dev, void* w_dev, gspx_knn** w_out,
+                               int64_t* niter, int32_t* crit, double* history_host, double* kernel_ms);
+
 /* Space-filling-curve keys of N points (coords: N x d doubles on the HOST, d >= 2; the first two /
  * three axes are used): curve 0 = Morton, 1 = Hilbert (2-D).  The engine's internal vertex order
  * for graphs with coordinates is the stable argsort of these keys (pygsp_amd.engine.locality_order). */

@@ -4,6 +4,6 @@ Scope: ``pygsp.filters.Filter.filter(method='chebyshev')`` and the Laplacian it 
 ``pygsp_amd.graphs`` / ``pygsp_amd.filters`` mirror the reference's classes for that path;
 ``pygsp_amd.plugin.install()`` patches a real pygsp installation in place.
 """
-from . import _capi, engine, filters, graphs, optimization, plugin, reduction  # noqa: F401
+from . import _capi, engine, filters, graph_learning, graphs, optimization, plugin, reduction  # noqa: F401
 
 __version__ = "0.1.0"

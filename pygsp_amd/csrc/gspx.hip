@@ -91,6 +91,7 @@ extern "C" const char* gspx_version(void) { return "gspx 0.1 (gfx950)"; }
 #include "gspx_lanczos.hip.h"     // Lanczos filtering: Krylov stack and combine                      (on poly, ops)
 #include "gspx_conv.hip.h"        // Chebyshev graph convolution: k_group_mix, k_slot_cross_gram      (on poly, ops)
 #include "gspx_fista.hip.h"       // the FISTA driver: stopping rule, argument check, host loop       (on ops)
+#include "gspx_graphlearn.hip.h"  // graph learning: edge distances, the log-degree model, its adjacency (on ops, knn, fista)
 #include "gspx_learning.hip.h"    // classification_tikhonov_simplex                                  (on ops, fista)
 #include "gspx_optim.hip.h"       // prox_tv: the graph total-variation proximal operator             (on ops, fista)
 #include "gspx_layout.hip.h"      // spring layout: all-pairs repulsion, attraction and update        (on ops)

@@ -1440,6 +1440,66 @@ class DeviceGraph:
             z = bz.download(x2.shape, np.float64)
         return (z[:, 0] if one_d else z), info
 
+    # ---- graph learning (pygsp_amd/graph_learning.py) -----------------------------------------------
+    def _device_panel(self, x, rows, what, temporaries):
+        """Device pointer and column count of a (rows[, cols]) float64 panel: a DeviceArray of this context as it lies,
+        a host array uploaded into `temporaries`."""
+        if isinstance(x, DeviceArray):
+            if x.dtype != np.float64 or x.ctx is not self.ctx or x.cube[0] != rows or x.cube[2] != 1:
+                raise ValueError("{}: a device array must be ({}[, columns]) float64 on the graph's context".format(
+                    what, rows))
+            return x.ptr, x.cube[1]
+        x2 = np.asarray(x, dtype=np.float64)
+        if x2.ndim not in (1, 2) or x2.shape[0] != rows:
+            raise ValueError("{}: first dimension must be {}, got {}".format(what, rows, x2.shape))
+        x2 = np.ascontiguousarray(x2.reshape(rows, 1) if x2.ndim == 1 else x2)
+        return (temporaries.upload(x2).ptr if x2.size else None), x2.shape[1]
+
+    def edge_sqdist(self, X):
+        """z_e = ||X_s - X_t||^2 for every edge (s, t) of this float64 graph's default edge list, in
+        Graph.get_edge_list order (gspx_edge_sqdist_dev).  X: (N, F) or (N,), 1 <= F <= 4096, a numpy array or a
+        float64 DeviceArray of this context; z comes back as the same kind, (n_edges,)."""
+        E, ms = self.n_edges(), ctypes.c_double(0)
+        z = DeviceArray.empty(self.ctx, (E, 1, 1), np.float64)
+        z.shape = (E,)  # (also for E = 1)
+        with self.ctx._temporaries() as t:
+            x_ptr, F = self._device_panel(X, self.N, "edge_sqdist", t)
+            self.ctx.call(_capi.load().gspx_edge_sqdist_dev, self._h, F, ctypes.c_void_p(x_ptr), ctypes.c_void_p(z.ptr),
+                          ctypes.byref(ms))
+        return z if isinstance(X, DeviceArray) else z.numpy()
+
+    def learn_log_degrees(self, z, a, b, gamma, tol=1e-5, maxit=10000, w0=None, adjacency=False):
+        """Weights of the log-degree model on this float64 graph's pattern (gspx_learn_log_degrees_dev): argmin over
+        w >= 0 of 2 z^T w - a sum log(S w) + b ||w||^2 by primal-dual iterations with the fixed step `gamma`, stopped
+        when both relative residuals are <= tol (None or negative: off) or after maxit iterations.  z, w0: (n_edges,)
+        in Graph.get_edge_list order, numpy arrays or float64 DeviceArrays of this context.  Returns (P, w, W, info): P the
+        result (non-negative, exact zeros) and w the last iterate (for warm starts), of the kind z is; W the adjacency
+        of P as a DeviceAdjacency (None unless `adjacency`); info = {'niter', 'crit' ('TOL' or 'MAXIT'), 'history'
+        (niter, 4): ||dw||, ||w||, ||dv||, ||v||, 'ms' (device time of the iterations)}."""
+        E, maxit = self.n_edges(), int(maxit)
+        hist = np.zeros((max(maxit, 1), 4), dtype=np.float64)
+        niter, crit, ms, h = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_void_p()
+        P, w = (DeviceArray.empty(self.ctx, (E, 1, 1), np.float64) for _ in range(2))
+        P.shape = w.shape = (E,)  # (also for E = 1)
+        with self.ctx._temporaries() as t:
+            z_ptr, cols = self._device_panel(z, E, "learn_log_degrees: z", t)
+            w0_ptr = None
+            if w0 is not None:
+                w0_ptr, c0 = self._device_panel(w0, E, "learn_log_degrees: w0", t)
+                cols = max(cols, c0)
+            if cols != 1:
+                raise ValueError("learn_log_degrees: z and w0 hold one value per edge")
+            self.ctx.call(_capi.load().gspx_learn_log_degrees_dev, self._h, ctypes.c_void_p(z_ptr), float(a), float(b),
+                          float(gamma), -1.0 if tol is None else float(tol), maxit, ctypes.c_void_p(w0_ptr),
+                          ctypes.c_void_p(P.ptr), ctypes.c_void_p(w.ptr), ctypes.byref(h) if adjacency else None,
+                          ctypes.byref(niter), ctypes.byref(crit), _capi.ptr(hist), ctypes.byref(ms))
+        W = _adjacency(h, self.ctx, self.N, True)[0] if adjacency else None
+        n = int(niter.value)
+        info = {"niter": n, "crit": {1: "TOL", 5: "MAXIT"}.get(crit.value), "history": hist[:n].copy(), "ms": ms.value}
+        if not isinstance(z, DeviceArray):
+            P, w = P.numpy(), w.numpy()
+        return P, w, W, info
+
     # ---- layout (Graph.set_coordinates('spring')) ---------------------------------------------------
     def layout_splits(self):
         """Ways gspx_layout_spring_dev splits the all-pairs sum for this graph (from N and the CU count, or the

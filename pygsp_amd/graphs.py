@@ -1121,3 +1121,11 @@ class ErdosRenyi(StochasticBlockModel):
                  seed=None, **kwargs):
         StochasticBlockModel.__init__(self, N=N, k=1, p=p, directed=directed, self_loops=self_loops,
                                       connected=connected, n_try=n_try, seed=seed, **kwargs)
+
+
+def __getattr__(name):
+    """``graphs.LearnedGraph`` lives in pygsp_amd/graph_learning.py, which builds on this module: resolved on first use."""
+    if name == "LearnedGraph":
+        from .graph_learning import LearnedGraph
+        return LearnedGraph
+    raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))

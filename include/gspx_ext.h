@@ -480,6 +480,30 @@ int gspx_cheby_conv_dev(gspx_graph* g, double lmax, int M, int Fin, int Fout, co
 int gspx_cheby_cross_grams_dev(gspx_graph* g, double lmax, int M, int Fin, int Fout, int64_t B, const void* x_dev,
                                const void* z_dev, double* out, double* kernel_ms);
 
+/* The derivative of a Chebyshev filter's output with respect to the entries of the Laplacian, at FIXED lmax and with
+ * the entries taken as independent (pygsp_amd.filters.cheby_op_vjp_weights, pygsp_amd.nn.WeightedGraph).  For
+ *   y_f = c_f0/2 x + sum_{k >= 1} c_fk T_k(Lt) x,  Lt = (2/lmax) L - I,  and cotangent planes z_f = dl/dy_f:
+ *   Gbar = dl/dL = (2/lmax) sum_{k=1}^{M-1} phi_k b_k t_{k-1}^T,   phi_1 = 1, phi_k = 2 otherwise,
+ * t_k = T_k(Lt) x and b_k the Clenshaw sequence of the cotangent (b_k = sum_f c_fk z_f + 2 Lt b_{k+1} - b_{k+2}).  Two
+ * restrictions of Gbar are written, both summed over the signal columns:
+ *   gdiag_dev[i] = Gbar_ii (N doubles);   goff_dev[p] = Gbar_st + Gbar_ts for vertex couple p = (s, t) of a list.
+ * coeffs: HOST, Nf x M, as for gspx_cheby_filter_dev, 2 <= M <= 256.  x_dev: N x Nsig; z_dev: Nf planes [f][n][s] as
+ * for gspx_cheby_cross_moments_dev; both the graph's compute dtype, the CALLER's vertex order.  src_dev / dst_dev:
+ * DEVICE int32 arrays of n_pairs vertices each, the caller's vertex order, either orientation, repeats allowed, edges
+ * of the graph or not (for a non-edge: the derivative with respect to giving it weight).  src_dev == NULL (then
+ * dst_dev must be NULL and n_pairs is ignored): the graph's own edge list, the order of Graph.get_edge_list, goff_dev
+ * of gspx_graph_n_edges entries.  gdiag_dev and goff_dev are DEVICE fp64 buffers for both graph dtypes, OVERWRITTEN;
+ * either may be NULL.  Per column batch: M - 2 recurrence steps into M - 1 kept slots, M - 1 Clenshaw steps, and after
+ * each the two bandwidth kernels k_pair_cross / k_row_cross; products and sums are fp64, there are no atomics, later
+ * batches add in batch order on one stream, and identical calls give identical bits.
+ * GSPX_ERR_INVALID for what gspx_cheby_cross_moments_dev refuses, sources without targets (or the reverse), a negative
+ * n_pairs, null or non-finite coefficients (all checked before the graph is looked at), a graph whose edge list cannot
+ * be built when it is asked for, and - found by one device pass before anything is written - a vertex outside
+ * 0 .. N-1 or a couple with s == t.  Nsig == 0 or N == 0: zeros. */
+int gspx_cheby_laplacian_grad_dev(gspx_graph* g, double lmax, int Nf, int M, const double* coeffs, int64_t Nsig,
+                                  const void* x_dev, const void* z_dev, int64_t n_pairs, const int32_t* src_dev,
+                                  const int32_t* dst_dev, double* gdiag_dev, double* goff_dev, double* kernel_ms);
+
 /* PCI address ("0000:c1:00.0", NUL-terminated) of HIP device `device`: what a host driver needs to find the NUMA
  * node the GPU hangs off (/sys/bus/pci/devices/<address>/numa_node) and pin the thread - and the packing threads
  * libgspx starts from it - that feeds this GPU to the cores next to it (pygsp_amd.multi). */

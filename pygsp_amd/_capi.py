@@ -174,6 +174,8 @@ SIGNATURES = {
                                        _c.POINTER(_c.c_double)]),
     "gspx_cheby_cross_grams_dev": (_c.c_int, [_P, _c.c_double, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _P, _P, _P,
                                               _c.POINTER(_c.c_double)]),
+    "gspx_cheby_laplacian_grad_dev": (_c.c_int, [_P, _c.c_double, _c.c_int, _c.c_int, _P, _c.c_int64, _P, _P, _c.c_int64,
+                                                 _P, _P, _P, _P, _c.POINTER(_c.c_double)]),
     "gspx_planes_pack_dev": (_c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _c.c_int]),
     "gspx_device_pci_bus_id": (_c.c_int, [_c.c_int, _c.c_char_p, _c.c_int]),
     "gspx_comm_available": (_c.c_int, []),

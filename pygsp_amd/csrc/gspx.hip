@@ -90,6 +90,7 @@ extern "C" const char* gspx_version(void) { return "gspx 0.1 (gfx950)"; }
 #include "gspx_eig.hip.h"         // the full Fourier basis: dense symmetric eigensolver by block Jacobi   (on spectral)
 #include "gspx_lanczos.hip.h"     // Lanczos filtering: Krylov stack and combine                      (on poly, ops)
 #include "gspx_conv.hip.h"        // Chebyshev graph convolution: k_group_mix, k_slot_cross_gram      (on poly, ops)
+#include "gspx_wgrad.hip.h"       // the filter's gradient in the Laplacian: k_pair_cross, k_row_cross (on poly, ops)
 #include "gspx_fista.hip.h"       // the FISTA driver: stopping rule, argument check, host loop       (on ops)
 #include "gspx_graphlearn.hip.h"  // graph learning: edge distances, the log-degree model, its adjacency (on ops, knn, fista)
 #include "gspx_learning.hip.h"    // classification_tikhonov_simplex                                  (on ops, fista)

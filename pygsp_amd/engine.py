@@ -1100,6 +1100,51 @@ class DeviceGraph:
                 bz.upload(z)
             return self.cheby_cross_grams_dev(bx.ptr, bz.ptr, x.shape[1], x.shape[2], z.shape[2], lmax, M)
 
+    def cheby_laplacian_grad_dev(self, coeffs, x_ptr, z_ptr, nsig, lmax, src_ptr=None, dst_ptr=None, n_pairs=0,
+                                 gdiag_ptr=None, goff_ptr=None):
+        """The derivative of a Chebyshev filter's output with respect to the Laplacian's entries, on device pointers
+        (gspx_cheby_laplacian_grad_dev): coeffs (Nf, M) float64 on the host, the signals at x_ptr (N x nsig), the Nf
+        cotangent planes at z_ptr (Nf x N x nsig); src_ptr / dst_ptr: device int32 arrays of n_pairs vertices, None
+        for the graph's own edge list; gdiag_ptr (N doubles) and goff_ptr (one double per pair) are device buffers that
+        are overwritten, either may be None.  Returns device milliseconds of the call."""
+        c = _coeff_matrix(coeffs)
+        ms = ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_cheby_laplacian_grad_dev, self._h, float(lmax), c.shape[0], c.shape[1],
+                      _capi.ptr(c), int(nsig), ctypes.c_void_p(x_ptr), ctypes.c_void_p(z_ptr), int(n_pairs),
+                      ctypes.c_void_p(src_ptr), ctypes.c_void_p(dst_ptr), ctypes.c_void_p(gdiag_ptr),
+                      ctypes.c_void_p(goff_ptr), ctypes.byref(ms))
+        return ms.value
+
+    def cheby_laplacian_grad(self, coeffs, x, z, lmax, pairs=None, need_diag=True):
+        """cheby_laplacian_grad_dev of host arrays x (N, nsig) and z (Nf, N, nsig), uploaded in the graph's dtype and
+        freed afterwards.  pairs: a (2, P) integer array of vertex pairs, or None for the graph's own edge list.
+        Returns (gdiag (N,) float64 or None without need_diag, goff (P,) float64, device milliseconds)."""
+        c = _coeff_matrix(coeffs)
+        x = self._signals(x)
+        z = np.ascontiguousarray(z, dtype=self.dtype)
+        if z.ndim != 3 or z.shape[0] != c.shape[0] or z.shape[1:] != x.shape:
+            raise ValueError("z must be (Nf, N, Nsig) with the coefficients' Nf and x's N and Nsig, got {} for x {}"
+                             .format(z.shape, x.shape))
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+            if pairs.ndim != 2 or pairs.shape[0] != 2:
+                raise ValueError("pairs must be (2, P), got {}".format(pairs.shape))
+        P = self.n_edges() if pairs is None else pairs.shape[1]
+        with self.ctx._temporaries() as t:
+            bx, bz = t.alloc(x.nbytes), t.alloc(z.nbytes)
+            if x.nbytes:
+                bx.upload(x)
+                bz.upload(z)
+            bp = t.upload(pairs) if pairs is not None and P else None
+            bd = t.alloc(8 * self.N) if need_diag else None
+            bo = t.alloc(8 * P)
+            ms = self.cheby_laplacian_grad_dev(
+                c, bx.ptr, bz.ptr, x.shape[1], lmax, None if pairs is None else (bp.ptr if bp else bo.ptr),
+                None if pairs is None else (bp.ptr + 4 * P if bp else bo.ptr), P, bd.ptr if bd else None, bo.ptr)
+            gdiag = bd.download((self.N,), np.float64) if need_diag and self.N else (np.zeros(0) if need_diag else None)
+            goff = bo.download((P,), np.float64) if P else np.zeros(0)
+        return gdiag, goff, ms
+
     def _samples(self, x, features=None):
         x = np.ascontiguousarray(x, dtype=self.dtype)
         if x.ndim != 3 or x.shape[0] != self.N or (features is not None and x.shape[2] != features):

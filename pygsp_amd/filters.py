@@ -614,11 +614,20 @@ def cheby_op_vjp(G, c, signal, cotangent, **kwargs):
     recurrence (gspx_cheby_cross_moments_dev) summed over the signal columns in fp64 on the host.  Only the
     recurrence evaluates the polynomial here: `evaluation` other than None / 'recurrence', and a device list, raise
     ValueError."""
+    coeffs, x, planes = _vjp_arguments("cheby_op_vjp", G, c, signal, cotangent, kwargs)
+    gx, grad_c, ms = _vjp_host(_device_graph_of(G), G.lmax, coeffs, x, planes, False)
+    _record_timing(G, ms)
+    return gx.reshape(np.shape(signal)), grad_c.reshape(np.shape(c) if np.ndim(c) else coeffs.shape)
+
+
+def _vjp_arguments(who, G, c, signal, cotangent, kwargs):
+    """The argument checks cheby_op_vjp and the calls that differentiate with respect to the graph share (`who` names
+    the caller in the messages): ((Nf, M) coefficients, the signal as (N, Nsig), the cotangent as (Nf, N, Nsig) planes)."""
     coeffs = _as_coeff_matrix(c)
     if kwargs.get("evaluation") not in (None, "recurrence"):
-        raise ValueError("cheby_op_vjp differentiates the recurrence: evaluation must be None or 'recurrence'")
+        raise ValueError("{} differentiates the recurrence: evaluation must be None or 'recurrence'".format(who))
     if kwargs.get("devices") is not None:
-        raise ValueError("cheby_op_vjp runs on one GPU: it takes no device list")
+        raise ValueError("{} runs on one GPU: it takes no device list".format(who))
     panel, cot = np.asanyarray(signal), np.asanyarray(cotangent)
     if np.iscomplexobj(panel) or np.iscomplexobj(cot):
         raise TypeError("complex signals are not supported by the Chebyshev path")
@@ -630,9 +639,129 @@ def cheby_op_vjp(G, c, signal, cotangent, **kwargs):
         raise ValueError("the cotangent must have the shape cheby_op returns, {}, got {}"
                          .format((Nf * G.N,) + panel.shape[1:], cot.shape))
     x = panel.reshape(G.N, -1)
-    gx, grad_c, ms = _vjp_host(_device_graph_of(G), G.lmax, coeffs, x, cot.reshape(Nf, G.N, x.shape[1]), False)
+    return coeffs, x, cot.reshape(Nf, G.N, x.shape[1])
+
+
+def _pair_list(G, pairs):
+    """`pairs` as a contiguous (2, P) int32 array, every pair inside the graph and s != t; None stays None (the graph's
+    own edge list)."""
+    if pairs is None:
+        return None
+    p = np.asarray(pairs)
+    if p.dtype.kind not in "iu":
+        raise TypeError("pairs must be an integer array, got {}".format(p.dtype))
+    if p.ndim != 2 or p.shape[0] != 2:
+        raise ValueError("pairs must be (2, P), got {}".format(p.shape))
+    if p.size and (p.min() < 0 or p.max() >= G.N):
+        raise ValueError("pairs name a vertex outside 0 .. N - 1 = {}".format(G.N - 1))
+    if np.any(p[0] == p[1]):
+        raise ValueError("pairs must join two different vertices (s != t)")
+    return np.ascontiguousarray(p, dtype=np.int32)
+
+
+def cheby_op_vjp_laplacian(G, c, signal, cotangent, pairs=None, **kwargs):
+    """How a loss that reads ``cheby_op(G, c, signal)`` changes with the ENTRIES of the Laplacian, at fixed G.lmax and
+    with the entries taken as independent: with Gbar = dl/dL for the cotangent dl/dy (shape as cheby_op returns),
+
+        gdiag[i] = Gbar_ii   for every vertex,          goff[p] = Gbar_st + Gbar_ts   for every pair p = (s, t),
+
+    both float64, (N,) and (P,), summed over the signal columns (gspx_cheby_laplacian_grad_dev).  `pairs`: a (2, P)
+    integer array of any pairs s != t - edges or not, either orientation, repeats allowed - or None for
+    ``G.get_edge_list()``.  Argument checks and shapes are cheby_op_vjp's.  cheby_op_vjp_weights turns the two into the
+    gradient of the edge weights."""
+    coeffs, x, cot = _vjp_arguments("cheby_op_vjp_laplacian", G, c, signal, cotangent, kwargs)
+    gdiag, goff, ms = _device_graph_of(G).cheby_laplacian_grad(coeffs, x, cot, G.lmax, _pair_list(G, pairs), True)
     _record_timing(G, ms)
-    return gx.reshape(panel.shape), grad_c.reshape(np.shape(c) if np.ndim(c) else coeffs.shape)
+    return np.asarray(gdiag, dtype=np.float64), np.asarray(goff, dtype=np.float64)
+
+
+def _laplacian_call(G, coeffs, x, cot):
+    """The host-array device call of _weight_gradient on G's device graph (looked up when the call is made)."""
+    return lambda pairs, need_diag: _device_graph_of(G).cheby_laplacian_grad(coeffs, x, cot, G.lmax, pairs, need_diag)
+
+
+def _weight_gradient(G, pairs, call):
+    """(dl/dw (P,), device ms): the chain rule from the entries of L to the weights of the pairs, for G.lap_type.
+    pairs: a checked (2, P) int32 array or None; call(pairs or None, need_diag) -> (gdiag, goff, ms) is the ONE
+    device call (engine.DeviceGraph.cheby_laplacian_grad with the signals bound).  Every refusal comes before it."""
+    if G.is_directed():
+        raise ValueError("the weight gradient is defined for undirected graphs (one weight per unordered pair)")
+    if G.lap_type not in ("combinatorial", "normalized"):
+        raise ValueError("unknown Laplacian type {}".format(G.lap_type))
+    loops = bool(np.any(G.W.diagonal() != 0))
+    if loops and (pairs is None or G.lap_type == "normalized"):
+        raise ValueError("the graph has self-loops: its own edge list is not a list of pairs s != t")
+    es, et, ew = G.get_edge_list()
+    s, t = (es, et) if pairs is None else pairs
+    if G.lap_type == "combinatorial":  # L = D - W: dL_ss = dL_tt = 1, dL_st = dL_ts = -1
+        gdiag, goff, ms = call(pairs, True)
+        return gdiag[s] + gdiag[t] - goff, ms
+    # L = I - S W S, S = diag(d^-1/2): the entry itself, and the degrees of both endpoints through every own edge
+    d = np.ravel(np.asarray(G.W.sum(axis=1), dtype=np.float64))
+    if np.any(d[s] == 0) or np.any(d[t] == 0):
+        raise ValueError("the normalized Laplacian's weight gradient needs endpoints of positive degree")
+    E = es.size
+    if pairs is None:
+        _, ge, ms = call(None, False)
+        gp = ge
+    else:  # own edges and pairs in ONE device call
+        both = np.ascontiguousarray(np.concatenate([np.stack([es, et]).astype(np.int32), pairs], axis=1))
+        _, goff, ms = call(both, False)
+        ge, gp = goff[:E], goff[E:]
+    sigma, delta = np.zeros(G.N), np.zeros(G.N)
+    sigma[d > 0] = d[d > 0] ** -0.5
+    flow = ge * ew * sigma[es] * sigma[et]
+    R = np.bincount(es, weights=flow, minlength=G.N) + np.bincount(et, weights=flow, minlength=G.N)
+    delta[d > 0] = R[d > 0] / (2.0 * d[d > 0])
+    return -gp * sigma[s] * sigma[t] + delta[s] + delta[t], ms
+
+
+def cheby_op_vjp_weights(G, c, signal, cotangent, pairs=None, **kwargs):
+    """The gradient of a loss that reads ``cheby_op(G, c, signal)`` with respect to the EDGE WEIGHTS of `G`, for the
+    cotangent dl/dy of the shape cheby_op returns: float64 (P,), one entry per pair of `pairs` ((2, P) integers, any
+    pairs s != t) or per edge of ``G.get_edge_list()`` when `pairs` is None.  For a pair that is no edge it is the
+    derivative with respect to giving that pair weight.
+
+    The gradient is taken AT FIXED ``G.lmax``: the scaling of the Laplacian into [-1, 1] is a constant of the call, the
+    dependence of lmax on the weights is not followed.  G.lap_type decides the chain rule: combinatorial
+    (dl/dw = gdiag[s] + gdiag[t] - goff) or normalized (the entry -w / sqrt(d_s d_t) and both degrees; with `pairs`
+    given, the graph's own edges and the pairs are evaluated in one device call).  Raises ValueError for a directed
+    graph, for a graph with self-loops when its own list is asked for (normalized: always), for a normalized Laplacian
+    with an endpoint of degree 0, and for `evaluation` other than None / 'recurrence' or a device list."""
+    coeffs, x, cot = _vjp_arguments("cheby_op_vjp_weights", G, c, signal, cotangent, kwargs)
+    grad, ms = _weight_gradient(G, _pair_list(G, pairs), _laplacian_call(G, coeffs, x, cot))
+    _record_timing(G, ms)
+    return grad
+
+
+def filter_signals_vjp_weights(bank, s, cotangent, order=30, pairs=None, coefficients=None):
+    """cheby_op_vjp_weights for ``filter_signals(bank, s, 'chebyshev', order)``: `s` goes through the shape rules of
+    filter_signals and the cotangent has the shape that call returns.  In synthesis (y = sum_f p_f(L) s_f) the roles
+    swap: p_f(L) is symmetric, so the same function of L is the analysis call with signal `cotangent` and cotangent
+    planes s_f.  Host arrays only."""
+    from . import engine
+    coefficients = coefficients or compute_cheby_coeff
+    G, Nf = bank.G, bank.Nf
+    if isinstance(s, engine.DeviceArray) or isinstance(cotangent, engine.DeviceArray):
+        raise TypeError("filter_vjp_weights takes host arrays")
+    s = G._check_signal(s)
+    N, nsig, nfeat = _cube_shape(G, Nf, s.shape)
+    synthesis = nfeat != 1
+    nfout = 1 if synthesis else Nf
+    coeffs = _as_coeff_matrix(coefficients(bank, m=order))
+    cot = np.asanyarray(cotangent)
+    if np.iscomplexobj(s) or np.iscomplexobj(cot):
+        raise TypeError("complex signals are not supported by the Chebyshev path")
+    if cot.size != N * nsig * nfout or (cot.ndim and cot.shape[0] != N):
+        raise ValueError("the cotangent must have the shape the filter call returns, got {}".format(cot.shape))
+    cube, cot = s.reshape(N, nsig, nfeat), cot.reshape(N, nsig, nfout)
+    if synthesis:
+        x, planes = cot[:, :, 0], np.ascontiguousarray(np.moveaxis(cube, 2, 0))
+    else:
+        x, planes = cube[:, :, 0], np.ascontiguousarray(np.moveaxis(cot, 2, 0))
+    grad, ms = _weight_gradient(G, _pair_list(G, pairs), _laplacian_call(G, coeffs, x, planes))
+    _record_timing(G, ms)
+    return grad
 
 
 def _conv_arguments(G, theta, signal):
@@ -1159,6 +1288,13 @@ class Filter:
         call returns, in analysis and in synthesis (filter_signals_vjp): how a loss that reads the filtered signals
         changes with `s` and with the bank's (Nf, order + 1) Chebyshev coefficients."""
         return filter_signals_vjp(self, s, cotangent, order)
+
+    def filter_vjp_weights(self, s, cotangent, order=30, pairs=None):
+        """The gradient of a loss that reads ``self.filter(s, 'chebyshev', order)`` with respect to the graph's edge
+        weights, at fixed G.lmax, for a cotangent of the shape that call returns, in analysis and in synthesis
+        (filter_signals_vjp_weights, cheby_op_vjp_weights): (P,) float64, one entry per pair of `pairs` ((2, P),
+        edges or not) or per edge of ``G.get_edge_list()``."""
+        return filter_signals_vjp_weights(self, s, cotangent, order, pairs)
 
     def analyze(self, s, method="chebyshev", order=30, devices=None):
         shape = _shape_of(s)

@@ -11,7 +11,10 @@ Y[n, b, :] = sum_k (T_k(Lt) X)[n, b, :] Theta_k, a plain sum.  Forward is one gs
 same call with every Theta_k transposed for the signal's gradient and one gspx_cheby_cross_grams_dev call for Theta's.
 Only X is saved for backward, never the T_k X.
 
-No second derivatives, no gradient with respect to lmax or the graph's weights.
+``WeightedGraph`` makes the graph's edge weights a parameter on a fixed pattern; ``cheby_filter`` on it has the
+weights as a third differentiable input (one gspx_cheby_laplacian_grad_dev call in backward, at fixed lmax).
+
+No second derivatives, no gradient with respect to lmax; ``cheby_conv`` has no gradient in the graph's weights.
 
 IMPORT ORDER.  torch ships its own HIP runtime (libamdhip64.so) and libgspx links against the ROCm installation's copy
 of the same SONAME.  Whichever of the two is loaded first serves both libraries: this module imports torch at its
@@ -101,7 +104,10 @@ class _ChebyFilter(torch.autograd.Function):
     finished on the device when it returns and torch may read the output from any stream."""
 
     @staticmethod
-    def forward(ctx, coeffs, x, G, lmax):
+    def forward(ctx, coeffs, x, G, lmax, weight=None, pattern=None):
+        # (weight, pattern: the Parameter and the module of a WeightedGraph whose present graph G is - the third
+        # differentiable input; None for a plain graph)
+        ctx.pattern = pattern
         if coeffs.dim() not in (1, 2) or x.dim() not in (1, 2):
             raise ValueError("coeffs must be (Nf, M) or (M,) and x (N,) or (N, Nsig), got {} and {}"
                              .format(tuple(coeffs.shape), tuple(x.shape)))
@@ -132,10 +138,12 @@ class _ChebyFilter(torch.autograd.Function):
         (xc,) = ctx.saved_tensors
         G, dev, lmax, c, c_shape, c_dtype, c_device, x_shape = ctx.call
         need_c, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_w = ctx.pattern is not None and ctx.needs_input_grad[4]
         Nf, M = c.shape
         N, nsig = xc.shape
         g = grad_y.detach().to(xc.dtype).permute(2, 0, 1).contiguous()  # planes [filter][vertex][signal]
         grad_c = grad_x = None
+        grad_w = _weight_grad(ctx.pattern, G, dev, lmax, c, xc, g) if need_w else None
         done = False
         if xc.is_cuda and xc.numel():
             gx = torch.empty((N, nsig), dtype=xc.dtype, device=xc.device) if need_x else None
@@ -156,7 +164,36 @@ class _ChebyFilter(torch.autograd.Function):
             grad_c = torch.from_numpy(np.ascontiguousarray(grad_c)).to(device=c_device, dtype=c_dtype).reshape(c_shape)
         if need_x:
             grad_x = grad_x.reshape(x_shape)
-        return (grad_c if need_c else None), (grad_x if need_x else None), None, None
+        return (grad_c if need_c else None), (grad_x if need_x else None), None, None, grad_w, None
+
+
+def _weight_grad(pattern, G, dev, lmax, c, xc, g):
+    """The gradient of the weights of a WeightedGraph's pattern (filters._weight_gradient over its pairs, so that pairs
+    at weight 0 receive theirs too), as a tensor like ``pattern.weight``.  xc (N, nsig) and the cotangent planes g
+    (Nf, N, nsig) as in _ChebyFilter.backward: GPU tensors go to gspx_cheby_laplacian_grad_dev by pointer when libgspx's
+    runtime knows them, with the pair list and the two outputs in tensors of their own; otherwise the call is staged
+    through host arrays."""
+    N, nsig = xc.shape
+
+    def call(pairs, need_diag):
+        P = pairs.shape[1]
+        if P == 0:  # (an empty list by pointer would read as "the graph's own edges": nothing to ask the device for)
+            return (np.zeros(N) if need_diag else None), np.zeros(0), 0.0
+        if xc.is_cuda and xc.numel():
+            pt = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32)).to(xc.device)
+            gdiag = torch.empty(N if need_diag else 0, dtype=torch.float64, device=xc.device)
+            goff = torch.empty(max(P, 1), dtype=torch.float64, device=xc.device)
+            torch.cuda.current_stream(xc.device).synchronize()
+            if _zero_copy(dev, (xc, g, pt, goff) + ((gdiag,) if need_diag else ())):
+                ms = dev.cheby_laplacian_grad_dev(c, xc.data_ptr(), g.data_ptr(), nsig, lmax, pt.data_ptr(),
+                                                  pt.data_ptr() + 4 * P, P, gdiag.data_ptr() if need_diag else None,
+                                                  goff.data_ptr())
+                return (gdiag.cpu().numpy() if need_diag else None), goff[:P].cpu().numpy(), ms
+        return dev.cheby_laplacian_grad(c, _host(xc), _host(g), lmax, pairs, need_diag)
+
+    grad, _ = filters._weight_gradient(G, pattern.pairs, call)
+    w = pattern.weight
+    return torch.from_numpy(np.ascontiguousarray(grad)).to(device=w.device, dtype=w.dtype)
 
 
 def cheby_filter(G, coeffs, x, lmax=None):
@@ -170,8 +207,74 @@ def cheby_filter(G, coeffs, x, lmax=None):
     A GPU tensor goes in by ``data_ptr()`` and the result is written into a ``torch.empty`` tensor in place, if
     libgspx's HIP runtime knows those pointers (see the module docstring); otherwise, and for CPU tensors, the call
     is staged through host arrays.  ``backward`` (once differentiable) returns the gradient of `coeffs` in its dtype
-    and on its device and the gradient of `x`; only the device calls of the gradients that are needed run."""
+    and on its device and the gradient of `x`; only the device calls of the gradients that are needed run.
+
+    `G` may be a WeightedGraph: its ``weight`` is then a third differentiable input.  The forward pass filters on
+    ``G.graph()``; backward adds one gspx_cheby_laplacian_grad_dev call on the module's pattern (when ``weight``
+    requires a gradient) and the chain rule of filters.cheby_op_vjp_weights, at fixed lmax."""
+    if isinstance(G, WeightedGraph):
+        return _ChebyFilter.apply(coeffs, x, G.graph(), lmax, G.weight, G)
     return _ChebyFilter.apply(coeffs, x, G, lmax)
+
+
+class WeightedGraph(torch.nn.Module):
+    """The edge weights of a graph as a parameter on a fixed pattern: ``weight`` is a float64 Parameter of shape (P,),
+    one entry per pair of the pattern - `G`'s edge list (``G.get_edge_list()``) or the (2, P) integer array `pairs` of
+    unique unordered pairs s != t - initialised from G's weights, 0 where a pair is no edge of G.  ``graph()`` is the
+    graphs.Graph of the present values, with G's lap_type, coordinates and compute dtype; ``cheby_filter(module, c, x)``
+    filters on it and differentiates with respect to ``weight`` too.
+
+    ``graph()`` rebuilds only after ``weight`` has changed (its ``_version`` counter); the rebuild goes through the
+    host: P doubles down, a scipy CSR, the one-call device set-up.  Pairs at weight 0 are not stored in W but stay in the
+    pattern and receive their gradient.  A negative or non-finite weight raises ValueError: clamp after the optimiser
+    step (``with torch.no_grad(): module.weight.clamp_(min=0)``)."""
+
+    def __init__(self, G, pairs=None):
+        super().__init__()
+        if G.is_directed():
+            raise ValueError("WeightedGraph needs an undirected graph (one weight per unordered pair)")
+        self.G = G
+        W = G.W.tocsr()
+        if pairs is None:
+            if np.any(W.diagonal() != 0):
+                raise ValueError("the graph has self-loops: its own edge list is not a list of pairs s != t")
+            s, t, _ = G.get_edge_list()
+            p = np.stack([np.asarray(s), np.asarray(t)])
+        else:
+            p = filters._pair_list(G, pairs)
+        lo, hi = np.minimum(p[0], p[1]).astype(np.int64), np.maximum(p[0], p[1]).astype(np.int64)
+        if np.unique(lo * G.N + hi).size != lo.size:
+            raise ValueError("the pairs of a WeightedGraph must be unique as unordered pairs")
+        self.pairs = np.ascontiguousarray(p, dtype=np.int32)
+        start = np.asarray(W[self.pairs[0], self.pairs[1]], dtype=np.float64).ravel() if lo.size else np.zeros(0)
+        self.weight = torch.nn.Parameter(torch.from_numpy(np.ascontiguousarray(start)))
+        self._graph, self._built = None, None
+
+    def _build(self, W):
+        """The graph of adjacency W (scipy CSR), like self.G in everything but its weights."""
+        from . import graphs
+        G = self.G
+        return graphs.Graph(W, lap_type=G.lap_type, coords=getattr(G, "coords", None), compute_dtype=G.compute_dtype,
+                            device=G.device, reorder=G.reorder, tiles=G.tiles, ctx=G._ctx)
+
+    def graph(self):
+        """The graph of the present weights; rebuilt only when ``weight`` has changed since the last call."""
+        version = (self.weight._version, id(self.weight))
+        if self._graph is None or self._built != version:
+            from scipy import sparse
+            w = self.weight.detach().to("cpu", torch.float64).numpy()
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError("WeightedGraph: a weight is negative or not finite (clamp after the optimiser step)")
+            N, keep = self.G.N, w != 0
+            s, t, w = self.pairs[0][keep], self.pairs[1][keep], w[keep]
+            W = sparse.coo_matrix((np.concatenate([w, w]), (np.concatenate([s, t]), np.concatenate([t, s]))),
+                                  shape=(N, N)).tocsr()
+            W.sort_indices()
+            self._graph, self._built = self._build(W), version
+        return self._graph
+
+    def extra_repr(self):
+        return "pairs={}, lap_type={}".format(self.pairs.shape[1], self.G.lap_type)
 
 
 class ChebyshevFilter(torch.nn.Module):

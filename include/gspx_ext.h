@@ -275,6 +275,39 @@ int gspx_schur_cg_dev(gspx_graph* g, double shift, const void* mask_dev, int64_t
 int gspx_kron_build(gspx_graph* g, double shift, const int32_t* ind_host, int64_t nk, double rtol, int64_t maxiter,
                     double* lnew_dev, gspx_knn** w_out, int32_t* iterations, double* kernel_ms);
 
+/* Multilevel coarsening by heavy-edge matching and pooling over the resulting partitions (pygsp_amd.reduction.coarsen,
+ * pygsp_amd.nn.GraphPool; DESIGN.md "Coarsening and pooling").  match and build take an fp64 graph created from W with
+ * the combinatorial Laplacian; they read its canonical Laplacian (caller's vertex order: w_ij = -L_ij off the
+ * diagonal, so a self-loop is never seen) and its weighted degrees, never the internal order.
+ * match_heavy_edges: handshake rounds.  Every unmatched vertex proposes to its unmatched neighbour of largest score -
+ * metric 0: w_ij (1 / d_i + 1 / d_j), metric 1: w_ij, fp64 - ties to the smaller vertex index; mutual proposals are
+ * matched.  While an edge joins two unmatched vertices a round matches at least one pair; the loop ends at the first
+ * round that matches nothing (the matching is then maximal) or after max_rounds productive rounds (max_rounds < 0:
+ * no limit; a path with monotone weights needs N / 2).  mate_host (N int32, HOST): the partner, mate[i] == i for a
+ * singleton; rounds: the rounds that matched something; pairs; kernel_ms (each may be NULL but mate_host).
+ * coarsen_build: Wc = P^T W P without its diagonal for the cluster map parent_host (N int32 in [0, n_clusters), HOST;
+ * every cluster has a member, any size).  An entry above the diagonal is the sum of its fine entries in ascending
+ * (fine row, fine column) order; the entry below is a copy of it.  out: a handle of the kind gspx_linegraph_build
+ * returns under gspx_kron_build's contract - canonical CSR, sorted columns, no diagonal, no stored zero, equal to its
+ * transpose bit for bit.  No atomics; identical calls give identical bits.
+ * segment_pool: y[c][:] = max | mean | sum (mode 0 | 1 | 2) of x[idx[m]][:] over ptr[c] <= m < ptr[c + 1], row-major
+ * panels N x width -> Nc x width of dtype GSPX_F32 / GSPX_F64, all DEVICE pointers; ptr / idx a partition of the N rows
+ * (every row in exactly one segment, no empty segment - not checked here), members visited in the order of idx: mean is
+ * that sum divided by the size, max keeps the first maximum.  16-byte accesses when width is a multiple of 16 bytes and
+ * the panels are aligned.  segment_pool_vjp: gx[idx[m]][:] from g[c][:] - sum: a copy (this is unpooling), mean:
+ * g / size, max: g at the first member that attains the maximum of x_dev (read for max only, else may be NULL), zero
+ * at the others.  Writes are disjoint: no atomics. */
+int gspx_match_heavy_edges(gspx_graph* g, int metric, int64_t max_rounds, int32_t* mate_host, int32_t* rounds,
+                           int64_t* pairs, double* kernel_ms);
+int gspx_coarsen_build(gspx_graph* g, const int32_t* parent_host, int64_t n_clusters, gspx_knn** out,
+                       double* kernel_ms);
+int gspx_segment_pool_dev(gspx_ctx* ctx, int dtype, int mode, int64_t N, int64_t Nc, int64_t width,
+                          const int32_t* ptr_dev, const int32_t* idx_dev, const void* x_dev, void* y_dev,
+                          double* kernel_ms);
+int gspx_segment_pool_vjp_dev(gspx_ctx* ctx, int dtype, int mode, int64_t N, int64_t Nc, int64_t width,
+                              const int32_t* ptr_dev, const int32_t* idx_dev, const void* x_dev, const void* g_dev,
+                              void* gx_dev, double* kernel_ms);
+
 /* Learning the weights of a graph from smooth signals (pygsp_amd.graph_learning; the log-degree model of Kalofolias
  * 2016 on a fixed pattern as in Kalofolias & Perraudin 2019; the definition is tests/graphlearn_helpers.py).
  * Both calls take an fp64 graph created from W that carries its default edge list - edge e = (s, t), s < t, is edge e

@@ -146,6 +146,14 @@ SIGNATURES = {
                                      _P, _P]),
     "gspx_kron_build": (_c.c_int, [_P, _c.c_double, _P, _c.c_int64, _c.c_double, _c.c_int64, _P, _c.POINTER(_P), _P,
                                    _c.POINTER(_c.c_double)]),
+    # coarsening and pooling (pygsp_amd/reduction.py: coarsen; pygsp_amd/nn.py: GraphPool)
+    "gspx_match_heavy_edges": (_c.c_int, [_P, _c.c_int, _c.c_int64, _P, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int64),
+                                          _c.POINTER(_c.c_double)]),
+    "gspx_coarsen_build": (_c.c_int, [_P, _P, _c.c_int64, _c.POINTER(_P), _c.POINTER(_c.c_double)]),
+    "gspx_segment_pool_dev": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _P,
+                                         _c.POINTER(_c.c_double)]),
+    "gspx_segment_pool_vjp_dev": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _P,
+                                             _P, _c.POINTER(_c.c_double)]),
     # graph learning (pygsp_amd/graph_learning.py)
     "gspx_edge_sqdist_dev": (_c.c_int, [_P, _c.c_int64, _P, _P, _c.POINTER(_c.c_double)]),
     "gspx_learn_log_degrees_dev": (_c.c_int, [_P, _P, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_int64,

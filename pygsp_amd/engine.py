@@ -1434,6 +1434,44 @@ class DeviceGraph:
         _capi.check(_capi.load().gspx_last_timing(self.ctx._h, parts))
         return lnew, W, iters, {"kernel_ms": ms.value, "solve_ms": parts[0], "rows_ms": parts[1], "finalise_ms": parts[2]}
 
+    MATCH_METRICS = {"normalized_cut": 0, "weight": 1}
+
+    def match_heavy_edges(self, metric="normalized_cut", max_rounds=None):
+        """A maximal matching of heavy edges by handshake rounds on the device (gspx_match_heavy_edges; float64 graphs
+        with the combinatorial Laplacian).  Every unmatched vertex proposes to its unmatched neighbour of largest score
+        - 'normalized_cut': w_ij (1 / d_i + 1 / d_j), 'weight': w_ij - ties to the smaller vertex index (the caller's
+        indices: the internal order plays no part), and mutual proposals are matched.  `max_rounds`: None runs until a
+        round matches nothing (a path with monotone weights needs N / 2 rounds); otherwise at most that many rounds,
+        the rest stay singletons.  Returns (mate, info): mate int32 (N,), mate[i] == i for a singleton; info =
+        {'rounds' (the rounds that matched something), 'pairs', 'singletons', 'kernel_ms'}."""
+        if self.dtype != np.float64:
+            raise ValueError("match_heavy_edges runs on the float64 device graph")
+        if metric not in self.MATCH_METRICS:
+            raise ValueError("Unknown metric {!r}: 'normalized_cut' or 'weight'".format(metric))
+        if max_rounds is not None and int(max_rounds) < 0:
+            raise ValueError("max_rounds must be None or non-negative")
+        mate = np.empty(self.N, dtype=np.int32)
+        rounds, pairs, ms = ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_match_heavy_edges, self._h, self.MATCH_METRICS[metric],
+                      -1 if max_rounds is None else int(max_rounds), _capi.ptr(mate), ctypes.byref(rounds),
+                      ctypes.byref(pairs), ctypes.byref(ms))
+        return mate, {"rounds": int(rounds.value), "pairs": int(pairs.value),
+                      "singletons": self.N - 2 * int(pairs.value), "kernel_ms": ms.value}
+
+    def coarsen(self, parent, n_clusters):
+        """The coarse adjacency P^T W P without its diagonal for the cluster map `parent` (N ints in [0, n_clusters),
+        every cluster non-empty), assembled on the device (gspx_coarsen_build).  Returns (W, info): W a
+        DeviceAdjacency under gspx_kron_build's contract (canonical CSR, sorted columns, no diagonal, its transpose
+        bit for bit), info = {'kernel_ms', 'build_ms'}.  ValueError for a `parent` of wrong length or out of range."""
+        if self.dtype != np.float64:
+            raise ValueError("coarsen runs on the float64 device graph")
+        parent, n_clusters = check_parent(parent, self.N, n_clusters), int(n_clusters)
+        h, ms = ctypes.c_void_p(), ctypes.c_double(0)
+        self.ctx.call(_capi.load().gspx_coarsen_build, self._h, _capi.ptr(parent), n_clusters, ctypes.byref(h),
+                      ctypes.byref(ms))
+        W, _, build_ms = _adjacency(h, self.ctx, n_clusters, True)
+        return W, {"kernel_ms": ms.value, "build_ms": build_ms}
+
     def tikhonov_simplex(self, tau, step, labels, n_classes, rtol=1e-3, atol=None, dtol=None, xtol=None, maxit=200):
         """FISTA on the simplex-constrained Tikhonov problem of learning.classification_tikhonov_simplex
         (gspx_tikhonov_simplex_dev), on this float64 graph.  labels: N ints in the graph's vertex order, the class
@@ -1800,6 +1838,149 @@ def check_kept(ind, n_vertices):
     if np.unique(a).size != a.size:
         raise ValueError("ind holds a vertex more than once")
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def check_parent(parent, n_vertices, n_clusters):
+    """A cluster map as a contiguous int32 array: ValueError unless `parent` holds one integer in [0, n_clusters) per
+    vertex and every cluster has a member (host only)."""
+    a = np.asarray(parent)
+    if a.ndim != 1 or a.size != n_vertices:
+        raise ValueError("parent must hold one cluster per vertex ({}), got shape {}".format(n_vertices, a.shape))
+    if a.dtype == bool or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("parent must hold integer cluster indices, got {}".format(a.dtype))
+    n_clusters = int(n_clusters)
+    if n_clusters < 0 or (a.size and (a.min() < 0 or a.max() >= n_clusters)):
+        raise ValueError("parent must lie in [0, {})".format(n_clusters))
+    if np.unique(a).size != n_clusters:
+        raise ValueError("every one of the {} clusters needs a member".format(n_clusters))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+POOL_MODES = {"max": 0, "mean": 1, "sum": 2}
+
+
+class Segments:
+    """A partition of N fine rows into Nc segments as CSR (ptr (Nc + 1,), idx (N,)), checked on the host and uploaded
+    once: every row in exactly one segment, no empty segment, members ascending inside a segment - what the pooling
+    kernels rely on for their bounds and their summation order.  ``from_parent`` builds it from a cluster map."""
+
+    def __init__(self, ctx, ptr, idx):
+        ptr, idx = np.asarray(ptr), np.asarray(idx)
+        if ptr.ndim != 1 or idx.ndim != 1 or ptr.size < 1 or ptr[0] != 0 or ptr[-1] != idx.size:
+            raise ValueError("segments: ptr must run from 0 to len(idx)")
+        if np.any(np.diff(ptr) < 1):
+            raise ValueError("segments: every segment needs a member")
+        if idx.size and not np.array_equal(np.sort(idx), np.arange(idx.size)):
+            raise ValueError("segments: idx must hold every fine row exactly once")
+        inner = np.ones(idx.size, dtype=bool)
+        inner[ptr[:-1][ptr[:-1] < idx.size]] = False
+        if np.any(np.diff(idx)[inner[1:]] <= 0):
+            raise ValueError("segments: members must ascend inside a segment")
+        self.ctx, self.n_fine, self.n_coarse = ctx, int(idx.size), int(ptr.size - 1)
+        self.ptr = np.ascontiguousarray(ptr, dtype=np.int32)
+        self.idx = np.ascontiguousarray(idx, dtype=np.int32)
+        self._ptr_dev, self._idx_dev = ctx.upload(self.ptr), ctx.upload(self.idx if idx.size else np.zeros(1, np.int32))
+
+    @classmethod
+    def from_parent(cls, ctx, parent, n_clusters):
+        parent = check_parent(parent, np.size(parent), n_clusters)
+        idx = np.argsort(parent, kind="stable")
+        ptr = np.concatenate([[0], np.cumsum(np.bincount(parent, minlength=int(n_clusters)))])
+        return cls(ctx, ptr, idx)
+
+    @property
+    def sizes(self):
+        return np.diff(self.ptr)
+
+
+def _pool_call(ctx, seg, mode, dtype, width, x_ptr, g_ptr, out_ptr, vjp):
+    lib, ms = _capi.load(), ctypes.c_double(0)
+    head = (ctx._h, _capi.dtype_code(dtype), POOL_MODES[mode], seg.n_fine, seg.n_coarse, int(width),
+            ctypes.c_void_p(seg._ptr_dev.ptr), ctypes.c_void_p(seg._idx_dev.ptr), ctypes.c_void_p(x_ptr))
+    if vjp:
+        ctx.call(lib.gspx_segment_pool_vjp_dev, *head, ctypes.c_void_p(g_ptr), ctypes.c_void_p(out_ptr), ctypes.byref(ms))
+    else:
+        ctx.call(lib.gspx_segment_pool_dev, *head, ctypes.c_void_p(out_ptr), ctypes.byref(ms))
+    return ms.value
+
+
+def segment_pool_dev(ctx, seg, mode, dtype, width, x_ptr, y_ptr):
+    """gspx_segment_pool_dev on device pointers: the row-major (n_fine, width) panel at x_ptr pooled over the Segments
+    `seg` into the (n_coarse, width) panel at y_ptr.  Returns kernel_ms."""
+    return _pool_call(ctx, seg, mode, dtype, width, x_ptr, None, y_ptr, False)
+
+
+def segment_pool_vjp_dev(ctx, seg, mode, dtype, width, x_ptr, g_ptr, gx_ptr):
+    """gspx_segment_pool_vjp_dev on device pointers: the (n_coarse, width) cotangent at g_ptr spread to the (n_fine,
+    width) panel at gx_ptr; x_ptr (the pooled input) is read for 'max' only and may be None otherwise."""
+    return _pool_call(ctx, seg, mode, dtype, width, x_ptr, g_ptr, gx_ptr, True)
+
+
+def _pool_any(ctx, seg, mode, a, x, rows_in, rows_out, vjp):
+    """The shared frame of segment_pool and segment_pool_vjp: `a` ((rows_in, ...), numpy or DeviceArray) is the panel
+    that sets kind, dtype and trailing shape; `x` the pooled input of a 'max' vjp (same kind) or None."""
+    if mode not in POOL_MODES:
+        raise ValueError("Unknown pooling mode {!r}: 'max', 'mean' or 'sum'".format(mode))
+    need_x = vjp and mode == "max"
+    if need_x and x is None:
+        raise ValueError("the vjp of 'max' pooling needs the pooled input x")
+    if isinstance(a, DeviceArray):
+        if a.cube[0] != rows_in:
+            raise ValueError("expected {} rows, got {}".format(rows_in, a.cube[0]))
+        _, S, F = a.cube
+        if need_x and (not isinstance(x, DeviceArray) or x.cube != (rows_out, S, F) or x.dtype != a.dtype):
+            raise ValueError("x must be a DeviceArray like the cotangent, with {} rows".format(rows_out))
+        out = DeviceArray.empty(ctx, (rows_out, S, F), a.dtype)
+        out.shape = (rows_out,) + tuple(a.shape[1:])
+        item = a.dtype.itemsize
+        for f in range(F if S else 0):  # one (rows, S) row-major panel per feature plane
+            xp = x.ptr + f * rows_out * S * item if need_x else None
+            if vjp:
+                segment_pool_vjp_dev(ctx, seg, mode, a.dtype, S, xp, a.ptr + f * rows_in * S * item,
+                                     out.ptr + f * rows_out * S * item)
+            else:
+                segment_pool_dev(ctx, seg, mode, a.dtype, S, a.ptr + f * rows_in * S * item,
+                                 out.ptr + f * rows_out * S * item)
+        return out
+    a = np.asarray(a)
+    if a.ndim < 1 or a.shape[0] != rows_in:
+        raise ValueError("expected {} rows, got shape {}".format(rows_in, a.shape))
+    dtype = np.dtype(np.float32 if a.dtype == np.float32 else np.float64)
+    panel = np.ascontiguousarray(a.reshape(rows_in, -1), dtype=dtype)
+    width, shape = panel.shape[1], (rows_out,) + a.shape[1:]
+    if width == 0 or rows_in == 0:
+        return np.zeros(shape, dtype=dtype)
+    with ctx._temporaries() as t:
+        ba, bo, bx = t.upload(panel), t.alloc(rows_out * width * dtype.itemsize), None
+        if need_x:
+            xh = np.asarray(x)
+            if xh.shape != (rows_out,) + a.shape[1:]:
+                raise ValueError("x must have shape {}, got {}".format((rows_out,) + a.shape[1:], xh.shape))
+            bx = t.upload(np.ascontiguousarray(xh.reshape(rows_out, -1), dtype=dtype))
+        if vjp:
+            segment_pool_vjp_dev(ctx, seg, mode, dtype, width, bx.ptr if need_x else None, ba.ptr, bo.ptr)
+        else:
+            segment_pool_dev(ctx, seg, mode, dtype, width, ba.ptr, bo.ptr)
+        return bo.download((rows_out, width), dtype).reshape(shape)
+
+
+def segment_pool(ctx, seg, x, mode="max"):
+    """Pool the vertex signal `x` ((n_fine, ...) numpy array, or a DeviceArray) over the Segments `seg`: 'max', 'mean'
+    (the ascending-order sum divided by the size) or 'sum' of every segment's rows.  Returns the same kind with
+    n_coarse rows; float32 stays float32, anything else computes in float64.  No atomics: bit-reproducible."""
+    return _pool_any(ctx, seg, mode, x, None, seg.n_fine, seg.n_coarse, False)
+
+
+def segment_pool_vjp(ctx, seg, g, x=None, mode="max"):
+    """The vector-Jacobian product of segment_pool: `g` ((n_coarse, ...)) spread to the fine rows - 'sum': a copy of
+    the segment's row (unpooling), 'mean': g / size, 'max': g at the first member that attains the maximum of `x`
+    (the pooled input, needed for 'max' only), zero at the others."""
+    return _pool_any(ctx, seg, mode, g, x, seg.n_coarse, seg.n_fine, True)
+
+
+def segment_unpool(ctx, seg, y):
+    """Copy every segment's row of `y` ((n_coarse, ...)) to all of its members: the 'sum' vjp under its other name."""
+    return segment_pool_vjp(ctx, seg, y, None, "sum")
 
 
 def line_graph_size(dev):

@@ -14,6 +14,11 @@ Only X is saved for backward, never the T_k X.
 ``WeightedGraph`` makes the graph's edge weights a parameter on a fixed pattern; ``cheby_filter`` on it has the
 weights as a third differentiable input (one gspx_cheby_laplacian_grad_dev call in backward, at fixed lmax).
 
+``graph_pool`` / ``graph_unpool`` and ``GraphPool`` / ``GraphUnpool`` move vertex signals between the levels of a
+``reduction.Coarsening`` (max, mean or sum over every cluster): one gspx_segment_pool_dev call forward, one
+gspx_segment_pool_vjp_dev call backward (the argmax of max pooling is recomputed from the saved input, no index tensor
+is kept); no atomics, so a training step gives the same bits every time.
+
 No second derivatives, no gradient with respect to lmax; ``cheby_conv`` has no gradient in the graph's weights.
 
 IMPORT ORDER.  torch ships its own HIP runtime (libamdhip64.so) and libgspx links against the ROCm installation's copy
@@ -36,7 +41,7 @@ import warnings
 
 import numpy as np
 
-from . import _capi, filters
+from . import _capi, engine, filters
 
 _warned = False
 last_path = None  # "zero_copy" | "staged": how the most recent forward or backward pass reached the engine
@@ -425,3 +430,117 @@ class ChebConv(torch.nn.Module):
     def extra_repr(self):
         return "in_features={}, out_features={}, order={}, bias={}".format(self.in_features, self.out_features, self.order,
                                                                           self.bias is not None)
+
+
+class _SegmentPool(torch.autograd.Function):
+    """y = pool of x over the Segments `seg` (unpool=False) or the copy of every segment's row to its members
+    (unpool=True: the 'sum' vjp; its own backward is then the 'sum' pooling).  The zero-copy gate, the synchronisation of
+    the producer stream before a device call and the staged fallback are _ChebyFilter's (see ORDERING there): both
+    entry points end with their own hipStreamSynchronize of the context's stream."""
+
+    @staticmethod
+    def _run(dev, seg, mode, vjp, a, x):
+        """One pooling (vjp=False: a is the fine panel) or vjp call (a the cotangent, x the pooled input for 'max') on
+        contiguous 2-D tensors; returns the result on a's device."""
+        rows_out = seg.n_fine if vjp else seg.n_coarse
+        width, dtype = a.shape[1], _np_dtype(a)
+        need_x = vjp and mode == "max"
+        if a.is_cuda and a.numel():
+            out = torch.empty((rows_out, width), dtype=a.dtype, device=a.device)
+            torch.cuda.current_stream(a.device).synchronize()
+            if _zero_copy(dev, (a, out) + ((x,) if need_x else ())):
+                if vjp:
+                    engine.segment_pool_vjp_dev(seg.ctx, seg, mode, dtype, width, x.data_ptr() if need_x else None,
+                                                a.data_ptr(), out.data_ptr())
+                else:
+                    engine.segment_pool_dev(seg.ctx, seg, mode, dtype, width, a.data_ptr(), out.data_ptr())
+                return out
+        if vjp:
+            oh = engine.segment_pool_vjp(seg.ctx, seg, _host(a), _host(x) if need_x else None, mode)
+        else:
+            oh = engine.segment_pool(seg.ctx, seg, _host(a), mode)
+        return torch.from_numpy(np.ascontiguousarray(oh).reshape(rows_out, width)).to(device=a.device, dtype=a.dtype)
+
+    @staticmethod
+    def forward(ctx, x, coarsening, lo, hi, mode, unpool):
+        if mode not in engine.POOL_MODES:
+            raise ValueError("Unknown pooling mode {!r}: 'max', 'mean' or 'sum'".format(mode))
+        seg = coarsening.segments(lo, hi)
+        rows = seg.n_coarse if unpool else seg.n_fine
+        if x.dim() not in (2, 3) or x.shape[0] != rows:
+            raise ValueError("x must be ({0}, F) or ({0}, B, F), got {1}".format(rows, tuple(x.shape)))
+        _np_dtype(x)
+        dev = engine._float64_device_graph(coarsening.graphs[0])  # (the gate's device; pooling reads no graph)
+        if x.is_cuda and x.device.index != seg.ctx.device:
+            raise ValueError("the signal lives on {} but the coarsening on GPU {}".format(x.device, seg.ctx.device))
+        xc = x.detach().reshape(rows, -1).contiguous()
+        ctx.call = (dev, seg, mode, unpool, tuple(x.shape))
+        ctx.save_for_backward(*((xc,) if mode == "max" and not unpool else ()))
+        y = _SegmentPool._run(dev, seg, "sum" if unpool else mode, unpool, xc, None)
+        return y.reshape((y.shape[0],) + tuple(x.shape[1:]))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        dev, seg, mode, unpool, x_shape = ctx.call
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        g = grad_y.detach().reshape(grad_y.shape[0], -1).contiguous()
+        if unpool:
+            gx = _SegmentPool._run(dev, seg, "sum", False, g, None)
+        else:
+            xc = ctx.saved_tensors[0].to(g.dtype) if mode == "max" else None
+            gx = _SegmentPool._run(dev, seg, mode, True, g, xc)
+        return gx.reshape(x_shape), None, None, None, None, None
+
+
+def graph_pool(coarsening, x, lo=0, hi=None, mode="max"):
+    """`x` on the vertices of level `lo` of the ``reduction.Coarsening`` pooled to level `hi` (default: the coarsest),
+    differentiable in x: 'max', 'mean' or 'sum' over every cluster, members in ascending order.
+
+    x: tensor (N_lo, F) or (N_lo, B, F) - VERTEX first, as ``cheby_conv`` - float64 or float32, on the CPU or on the GPU
+    of the coarsening's context.  Returns (N_hi, F) or (N_hi, B, F) on x's device and in x's dtype.  GPU tensors go in
+    by ``data_ptr()`` when libgspx's HIP runtime knows them, through host arrays otherwise (see the module docstring).
+    ``backward`` (once differentiable) is one gspx_segment_pool_vjp_dev call: a copy for 'sum', g / size for 'mean', and
+    for 'max' the cotangent goes to the first member that attains the maximum (recomputed from x, which is the only
+    thing saved)."""
+    return _SegmentPool.apply(x, coarsening, lo, hi, mode, False)
+
+
+def graph_unpool(coarsening, y, lo=0, hi=None):
+    """`y` on the vertices of level `hi` copied to every member on level `lo`, differentiable in y (backward is the
+    'sum' pooling).  Shapes, dtypes and devices as ``graph_pool``."""
+    return _SegmentPool.apply(y, coarsening, lo, hi, "sum", True)
+
+
+class GraphPool(torch.nn.Module):
+    """``forward(x)`` = ``graph_pool(coarsening, x, lo, hi, mode)``: the pooling layer between two ChebConv layers on
+    ``coarsening.graphs[lo]`` and ``coarsening.graphs[hi]`` (Defferrard et al.).  Vertex first, no parameters."""
+
+    def __init__(self, coarsening, lo=0, hi=None, mode="max"):
+        super().__init__()
+        if mode not in engine.POOL_MODES:
+            raise ValueError("Unknown pooling mode {!r}: 'max', 'mean' or 'sum'".format(mode))
+        self.coarsening, self.mode = coarsening, mode
+        self.lo, self.hi = coarsening._span(lo, hi)
+
+    def forward(self, x):
+        return graph_pool(self.coarsening, x, self.lo, self.hi, self.mode)
+
+    def extra_repr(self):
+        return "lo={}, hi={}, mode={}".format(self.lo, self.hi, self.mode)
+
+
+class GraphUnpool(torch.nn.Module):
+    """``forward(y)`` = ``graph_unpool(coarsening, y, lo, hi)``: every cluster's row copied to its members."""
+
+    def __init__(self, coarsening, lo=0, hi=None):
+        super().__init__()
+        self.coarsening = coarsening
+        self.lo, self.hi = coarsening._span(lo, hi)
+
+    def forward(self, y):
+        return graph_unpool(self.coarsening, y, self.lo, self.hi)
+
+    def extra_repr(self):
+        return "lo={}, hi={}".format(self.lo, self.hi)

@@ -9,6 +9,13 @@ device (gspx_schur_cg_dev, gspx_kron_build; DESIGN.md "Graph reduction").
 ``interpolate`` needs no dense K_reg: K_reg f is rows k of A x with x the shifted extension of f - one solve per signal
 column - and with an exact Green's kernel the interpolated signal is x itself (``method='exact'``).
 
+``coarsen`` - an extension, the reference has no counterpart - is multilevel coarsening by heavy-edge matching (the
+Graclus / METIS family) for pooling layers: handshake rounds on the device (gspx_match_heavy_edges), the coarse graphs
+P^T W P assembled on the device (gspx_coarsen_build) and the vertex-to-cluster maps through which ``Coarsening.pool`` /
+``unpool`` and ``pygsp_amd.nn.GraphPool`` move signals (gspx_segment_pool_dev; DESIGN.md "Coarsening and pooling").
+``heavy_edge_matching_host`` and ``coarsen_host`` restate the two device algorithms in numpy, round for round and sum
+for sum.
+
 Not provided: graph_sparsify (and so ``graph_multiresolution(sparsify=True)``), tree_multiresolution, least-squares
 pyramid synthesis.
 """
@@ -252,3 +259,219 @@ def pyramid_synthesis(Gs, cap, pe, order=30, **kwargs):
         ca.append(s_pred + _as_columns(pe[levels - i - 1], fine.N))
     ca.reverse()
     return ca[0], ca
+
+
+# ---- multilevel coarsening by heavy-edge matching -------------------------------------------------------------------
+MATCH_METRICS = ("normalized_cut", "weight")
+
+
+def _undirected_csr(W):
+    W = sparse.csr_matrix(W, dtype=np.float64)
+    if W.shape[0] != W.shape[1]:
+        raise ValueError("the adjacency must be square")
+    if (W != W.T).nnz:
+        raise ValueError("coarsening needs an undirected graph (a symmetric adjacency)")
+    W.sum_duplicates()
+    W.sort_indices()
+    return W
+
+
+def heavy_edge_matching_host(W, d=None, metric="normalized_cut", max_rounds=None):
+    """The device matching (gspx_match_heavy_edges) restated in numpy: the same rounds, the same scores and the same
+    tie-break.  W: symmetric sparse adjacency (its diagonal is ignored: a self-loop is no candidate); d: the weighted
+    degrees the scores use (default: the row sums of W without its diagonal; hand over ``download_dw()`` to score the
+    device's own bits).  score(i, j) = w_ij (1 / d_i + 1 / d_j) for 'normalized_cut', w_ij for 'weight'.  Per round every
+    unmatched vertex proposes to its unmatched neighbour of largest score, ties to the smaller index, and mutual
+    proposals are matched; the loop ends at the first round that matches nothing or after `max_rounds` rounds.  A path
+    with monotone weights matches one pair per round: N / 2 rounds.
+    Returns (mate int32 with mate[i] == i for a singleton, rounds that matched something, pairs)."""
+    if metric not in MATCH_METRICS:
+        raise ValueError("Unknown metric {!r}: 'normalized_cut' or 'weight'".format(metric))
+    if max_rounds is not None and int(max_rounds) < 0:
+        raise ValueError("max_rounds must be None or non-negative")
+    W = _undirected_csr(W)
+    N = W.shape[0]
+    C = W.tocoo()
+    off = C.row != C.col
+    rows, cols, w = C.row[off], C.col[off], C.data[off]
+    if d is None:
+        d = np.bincount(rows, weights=w, minlength=N)
+    d = np.asarray(d, dtype=np.float64)
+    if d.shape != (N,):
+        raise ValueError("d must hold one degree per vertex")
+    with np.errstate(divide="ignore"):
+        inv = 1.0 / d
+    score = w if metric == "weight" else w * (inv[rows] + inv[cols])
+    mate = np.full(N, -1, dtype=np.int64)
+    rounds = 0
+    while max_rounds is None or rounds < int(max_rounds):
+        live = (mate[rows] < 0) & (mate[cols] < 0)
+        r, c, s = rows[live], cols[live], score[live]
+        order = np.lexsort((c, -s, r))  # per row: largest score first, then the smaller column
+        r, c = r[order], c[order]
+        first = np.ones(r.size, dtype=bool)
+        first[1:] = r[1:] != r[:-1]
+        prop = np.full(N, -1, dtype=np.int64)
+        prop[r[first]] = c[first]
+        i = np.flatnonzero(prop >= 0)
+        i = i[prop[prop[i]] == i]
+        if i.size == 0:
+            break
+        mate[i] = prop[i]
+        rounds += 1
+    single = mate < 0
+    mate[single] = np.flatnonzero(single)
+    return mate.astype(np.int32), rounds, int(np.count_nonzero(mate > np.arange(N)))
+
+
+def parent_of(mate):
+    """(parent int32, n_clusters) of a matching: cluster c is the rank of its smaller member among all cluster
+    representatives in ascending order, so `parent` is monotone in the representative."""
+    mate = np.asarray(mate)
+    rep = np.minimum(mate, np.arange(mate.size))
+    is_rep = rep == np.arange(mate.size)
+    rank = np.cumsum(is_rep) - 1
+    return rank[rep].astype(np.int32), int(np.count_nonzero(is_rep))
+
+
+def coarsen_host(W, parent):
+    """The device build (gspx_coarsen_build) restated in numpy: Wc = P^T W P without its diagonal, P the N x Nc cluster
+    indicator of `parent` (Nc = max(parent) + 1, every cluster non-empty).  An entry above the diagonal is the sum of
+    its fine entries in ascending (fine row, fine column) order, one term at a time; the entry below the diagonal is
+    its copy, so the result equals its transpose bit for bit.  Returns a canonical CSR matrix (float64)."""
+    W = _undirected_csr(W)
+    N = W.shape[0]
+    parent = np.asarray(parent)
+    if parent.ndim != 1 or parent.size != N:
+        raise ValueError("parent must hold one cluster per vertex ({}), got shape {}".format(N, parent.shape))
+    nc = int(parent.max()) + 1 if N else 0
+    parent = engine.check_parent(parent, N, nc).astype(np.int64)
+    C = W.tocoo()  # (canonical CSR: row-major, columns ascending)
+    cr, cd = parent[C.row], parent[C.col]
+    up = cr < cd
+    cr, cd, v = cr[up], cd[up], C.data[up]
+    order = np.lexsort((np.arange(v.size), cd, cr))  # stable: (fine row, fine column) order survives inside a group
+    cr, cd, v = cr[order], cd[order], v[order]
+    head = np.ones(v.size, dtype=bool)
+    head[1:] = (cr[1:] != cr[:-1]) | (cd[1:] != cd[:-1])
+    group = np.cumsum(head) - 1
+    start = np.flatnonzero(head)
+    place = np.arange(v.size) - start[group] if v.size else np.zeros(0, dtype=np.int64)
+    acc = np.zeros(start.size)
+    for t in range(int(place.max()) + 1 if v.size else 0):  # term t of every group: one addition each, in order
+        sel = place == t
+        acc[group[sel]] = acc[group[sel]] + v[sel] if t else v[sel]
+    U = sparse.coo_matrix((acc, (cr[head], cd[head])), shape=(nc, nc))
+    Wc = sparse.csr_matrix(U + U.T)
+    Wc.sort_indices()
+    return Wc
+
+
+class Coarsening:
+    """What ``coarsen`` returns: ``graphs`` [G_0 = G, ..., G_levels], ``parents`` (per level the int32 map of a
+    vertex of G_l to its cluster in G_{l+1}) and ``info`` (per level 'rounds', 'pairs', 'singletons', 'kernel_ms' of
+    the matching and 'build_kernel_ms' of the coarse graph).  ``segments(lo, hi)`` is the composed partition of the
+    vertices of G_lo into those of G_hi as an engine.Segments, uploaded once and cached; ``pool`` / ``unpool`` move
+    signals through it on the device."""
+
+    def __init__(self, graphs_, parents, info):
+        self.graphs, self.parents, self.info = list(graphs_), list(parents), list(info)
+        self._segments = {}
+
+    @property
+    def levels(self):
+        return len(self.parents)
+
+    def _span(self, lo, hi):
+        hi = self.levels if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo < hi <= self.levels:
+            raise ValueError("need 0 <= lo < hi <= {}, got lo = {}, hi = {}".format(self.levels, lo, hi))
+        return lo, hi
+
+    def parent(self, lo=0, hi=None):
+        """The composed cluster map from level `lo` to level `hi` (host)."""
+        lo, hi = self._span(lo, hi)
+        p = self.parents[lo]
+        for level in range(lo + 1, hi):
+            p = self.parents[level][p]
+        return p
+
+    def segments(self, lo=0, hi=None):
+        lo, hi = self._span(lo, hi)
+        if (lo, hi) not in self._segments:
+            # (the coarse graphs are this package's own and live on the context that coarsened G_0)
+            self._segments[lo, hi] = engine.Segments.from_parent(self.graphs[-1].context, self.parent(lo, hi),
+                                                                 self.graphs[hi].N)
+        return self._segments[lo, hi]
+
+    def pool(self, x, lo=0, hi=None, mode="max"):
+        """`x` on the vertices of G_lo ((N_lo, ...) numpy array or engine.DeviceArray) pooled to those of G_hi (default:
+        the coarsest): 'max', 'mean' or 'sum' over every cluster, members in ascending order.  Returns the same kind."""
+        seg = self.segments(lo, hi)
+        return engine.segment_pool(seg.ctx, seg, x, mode)
+
+    def pool_vjp(self, g, x=None, lo=0, hi=None, mode="max"):
+        """The vector-Jacobian product of ``pool`` (engine.segment_pool_vjp): `g` on G_hi back to G_lo."""
+        seg = self.segments(lo, hi)
+        return engine.segment_pool_vjp(seg.ctx, seg, g, x, mode)
+
+    def unpool(self, y, lo=0, hi=None):
+        """`y` on the vertices of G_hi copied to every member on G_lo (the 'sum' vjp).  Returns the same kind."""
+        seg = self.segments(lo, hi)
+        return engine.segment_unpool(seg.ctx, seg, y)
+
+
+def _matching_device_graph(G):
+    """The float64 device graph the matching and the build read: G's own when its Laplacian is combinatorial (the
+    weights are its off-diagonals), else a combinatorial one made from G.W for the call.  Returns (dev, temporary)."""
+    if G.lap_type == "combinatorial":
+        return engine._float64_device_graph(G), False
+    return engine.DeviceGraph.from_w(G.W, "combinatorial", dtype=np.float64, ctx=getattr(G, "context", None)), True
+
+
+def coarsen(G, levels=1, metric="normalized_cut", max_rounds=None):
+    """Multilevel coarsening of G by heavy-edge matching: per level a maximal matching by handshake rounds
+    (engine.DeviceGraph.match_heavy_edges; `metric` 'normalized_cut' - Graclus' w_ij (1 / d_i + 1 / d_j) - or
+    'weight'; `max_rounds` None runs to maximality, and a path with monotone weights needs N / 2 rounds), matched pairs
+    merged, and the coarse graph Wc = P^T W P without its diagonal assembled on the device
+    (engine.DeviceGraph.coarsen) and set up there without a host round trip.  Cluster c is the rank of its smaller
+    member among the representatives, so a local vertex order stays local.  ``lap_type``, ``compute_dtype`` and
+    ``plotting`` are carried over; ``coords`` are the mean of the members' coordinates when G has them.  A level that
+    matches nothing (no edges left) returns the same graph one level up.  Returns a ``Coarsening``.
+    ValueError for a directed graph."""
+    if not _is_graph(G):
+        raise TypeError("coarsen takes a Graph")
+    if G.is_directed():
+        raise ValueError("coarsening needs an undirected graph")
+    if metric not in MATCH_METRICS:
+        raise ValueError("Unknown metric {!r}: 'normalized_cut' or 'weight'".format(metric))
+    if int(levels) < 1:
+        raise ValueError("levels must be at least 1")
+    Gs, parents, infos = [G], [], []
+    for _ in range(int(levels)):
+        fine = Gs[-1]
+        dev, temporary = _matching_device_graph(fine)
+        try:
+            mate, info = dev.match_heavy_edges(metric, max_rounds)
+            parent, nc = parent_of(mate)
+            W, build = dev.coarsen(parent, nc)
+        finally:
+            if temporary:
+                dev.destroy()
+        if W.nnz == 0:
+            W = W.download()
+        coords = getattr(fine, "coords", None)
+        if coords is not None and np.ndim(coords) == 2 and np.shape(coords)[0] == fine.N:
+            sums = np.zeros((nc, np.shape(coords)[1]))
+            np.add.at(sums, parent, np.asarray(coords, dtype=np.float64))
+            coords = sums / np.bincount(parent, minlength=nc)[:, None]
+        else:
+            coords = None
+        kwargs = {"compute_dtype": fine.compute_dtype} if hasattr(fine, "compute_dtype") else {}
+        if getattr(fine, "_ctx", None) is not None:
+            kwargs["ctx"] = fine._ctx
+        Gs.append(graphs.Graph(W, coords=coords, lap_type=fine.lap_type, plotting=fine.plotting, **kwargs))
+        parents.append(parent)
+        infos.append(dict(info, build_kernel_ms=build["kernel_ms"], build_ms=build["build_ms"]))
+    return Coarsening(Gs, parents, infos)

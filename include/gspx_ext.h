@@ -196,7 +196,10 @@ int gspx_div_dev(gspx_graph* g, int64_t Nsig, const void* y_dev, void* z_dev, do
  * 1 'maximum' (= 'fill' for a k-NN matrix), 2 'tril', 3 'triu' (utils.symmetrize, utils.py:247-275).  Neighbours and distances
  * equal scipy's KD-tree bit for bit (ties ordered by vertex index); a point is never its own neighbour.  Context option "knn_f32": the candidate sweep beyond three
  * dimensions on the fp32 matrix cores - 1 (default) when its rounding margin is small against the bounds, 0 never,
- * 2 always; the selection is exact either way. */
+ * 2 always; the selection is exact either way.
+ * The handle is the device adjacency (CSR weight matrix) of EVERY builder declared below that hands out a gspx_knn -
+ * radius, block model, line graph, Kron reduction, learned graph, coarse graph - and gspx_knn_destroy / _info /
+ * _download_w serve them all; the name is historical (the k-NN builder came first). */
 typedef struct gspx_knn gspx_knn;
 int gspx_knn_build(gspx_ctx* ctx, int64_t N, int d, const double* coords, int k, double sigma,
                    int metric, int symmetrize, gspx_knn** out);

@@ -73,18 +73,19 @@ extern "C" const char* gspx_version(void) { return "gspx 0.1 (gfx950)"; }
 #include "gspx_mem.hip.h"         // DevMem, PinMem, CopyStage, HostPipe                              (needs only the above)
 #include "gspx_ctx.hip.h"         // Options and their table, the handles, contexts, buffers, timings (on mem)
 #include "gspx_comm.hip.h"        // RCCL gather, gspx_comm_*, gspx_gather                            (on ctx)
-#include "gspx_graph.hip.h"       // graph construction and its kernels, scan_exclusive, ensure_factor (on ctx)
+#include "gspx_adjacency.hip.h"   // scan_exclusive, the gspx_knn handle of every device builder and its frame (on ctx)
+#include "gspx_graph.hip.h"       // graph construction and its kernels, ensure_factor              (on ctx, adjacency)
 #include "gspx_hostpipe.hip.h"    // host-pointer calls pipelined over column batches                 (on ctx)
 #include "gspx_poly.hip.h"        // plans, launchers, batch runners, cheby / newton / program calls  (on graph, hostpipe)
 #include "gspx_lmax.hip.h"        // lambda_max by Lanczos and its vector kernels                     (on poly)
 #include "gspx_calib.hip.h"       // bandwidth / gather / mix calibrations, the placement tuner       (on poly)
 #include "gspx_ops.hip.h"         // L x, Dirichlet energy, Tikhonov CG, grad / div, panel primitives; brings
                                   // gspx_reduce.hip.h and gspx_ops_kernels.hip.h                     (on poly)
-#include "gspx_knn.hip.h"         // k-NN / radius graphs on the device, the gspx_knn handle; brings gspx_knn_bf.hip.h (on graph)
-#include "gspx_sbm.hip.h"         // stochastic block model / Erdos-Renyi sampler                     (on graph, knn)
-#include "gspx_setup.hip.h"       // graph set-up in one call, curve keys and orders                  (on graph, knn)
-#include "gspx_linegraph.hip.h"   // line graphs from the edge tables of grad / div                   (on ops, knn)
-#include "gspx_schur.hip.h"       // Schur complements of L + shift I: schur_cg, Kron reduction     (on ops, knn)
+#include "gspx_knn.hip.h"         // k-NN / radius graphs on the device; brings gspx_knn_bf.hip.h     (on adjacency)
+#include "gspx_sbm.hip.h"         // stochastic block model / Erdos-Renyi sampler                     (on adjacency, knn's row sort)
+#include "gspx_setup.hip.h"       // graph set-up in one call, curve keys and orders                  (on graph, adjacency)
+#include "gspx_linegraph.hip.h"   // line graphs from the edge tables of grad / div                   (on ops, adjacency)
+#include "gspx_schur.hip.h"       // Schur complements of L + shift I: schur_cg, Kron reduction     (on ops, adjacency)
 #include "gspx_components.hip.h"  // connected components                                             (on graph)
 #include "gspx_spectral.hip.h"    // panel Gram / combine / residual norms of the Fourier basis       (on ops)
 #include "gspx_eig.hip.h"         // the full Fourier basis: dense symmetric eigensolver by block Jacobi   (on spectral)
@@ -92,8 +93,8 @@ extern "C" const char* gspx_version(void) { return "gspx 0.1 (gfx950)"; }
 #include "gspx_conv.hip.h"        // Chebyshev graph convolution: k_group_mix, k_slot_cross_gram      (on poly, ops)
 #include "gspx_wgrad.hip.h"       // the filter's gradient in the Laplacian: k_pair_cross, k_row_cross (on poly, ops)
 #include "gspx_fista.hip.h"       // the FISTA driver: stopping rule, argument check, host loop       (on ops)
-#include "gspx_graphlearn.hip.h"  // graph learning: edge distances, the log-degree model, its adjacency (on ops, knn, fista)
+#include "gspx_graphlearn.hip.h"  // graph learning: edge distances, the log-degree model, its adjacency (on ops, adjacency, fista)
 #include "gspx_learning.hip.h"    // classification_tikhonov_simplex                                  (on ops, fista)
 #include "gspx_optim.hip.h"       // prox_tv: the graph total-variation proximal operator             (on ops, fista)
 #include "gspx_layout.hip.h"      // spring layout: all-pairs repulsion, attraction and update        (on ops)
-#include "gspx_coarsen.hip.h"     // heavy-edge matching, coarse graphs, segment pooling and its vjp     (on graph, knn)
+#include "gspx_coarsen.hip.h"     // heavy-edge matching, coarse graphs, segment pooling and its vjp     (on graph, adjacency)

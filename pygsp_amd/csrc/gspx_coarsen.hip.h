@@ -1,7 +1,8 @@
 // gspx_coarsen.hip.h - multilevel coarsening and pooling on the device: heavy-edge matching by handshake rounds
 // (gspx_match_heavy_edges), the coarse graph Wc = P^T W P without its diagonal (gspx_coarsen_build) and segment
 // pooling of row-major panels with its vector-Jacobian product (gspx_segment_pool_dev, gspx_segment_pool_vjp_dev).
-// gfx950 only.  Included by gspx.hip last (uses scan_exclusive, gspx_knn, DevMem, finish_timed, HIPCHK, CHK).
+// gfx950 only.  Included by gspx.hip last (uses the adjacency frame and scan_exclusive of gspx_adjacency.hip.h, DevMem,
+// finish_timed, HIPCHK, CHK).
 //
 // Everything reads the graph's canonical Laplacian (lptr / lcol / lval, the CALLER's vertex order) and its weighted
 // degrees dw: for the combinatorial Laplacian w_ij = -L_ij off the diagonal, the bits of W.  The internal (curve)
@@ -515,11 +516,8 @@ extern "C" int gspx_coarsen_build(gspx_graph* g, const int32_t* parent_host, int
   replay_reset(ctx);
   HIPCHK(hipSetDevice(ctx->device));
   const auto t0 = std::chrono::steady_clock::now();
-  std::unique_ptr<gspx_knn> h(new gspx_knn());
-  h->ctx = ctx;
-  h->N = Nc;
-  CHK(h->rowptr.alloc(((size_t)Nc + 1) * sizeof(int)));
-  HIPCHK(hipMemsetAsync(h->rowptr.p, 0, ((size_t)Nc + 1) * sizeof(int), st));
+  std::unique_ptr<gspx_knn> h;
+  CHK(adjacency_open(ctx, Nc, h));
   const int64_t total = g->nnz_l;  // every Laplacian entry lands in exactly one scratch row
   if (Nc > 0 && total > 0) {
     DevMem par, cp, ci, toff, cc, wv, head, pmax;
@@ -556,9 +554,7 @@ extern "C" int gspx_coarsen_build(gspx_graph* g, const int32_t* parent_host, int
       HIPCHK(hipMemsetAsync(place.p, 0, ((size_t)Nc + 1) * sizeof(int), st));
       hipLaunchKernelGGL(gspx::k_co_long_flag, dim3(nbc), dim3(256), 0, st, toff.as<int>(), (int)Nc, long_row,
                          place.as<int>());
-      CHK(scan_exclusive(ctx, place.as<int>(), place.as<int>(), (int)Nc + 1));
-      HIPCHK(hipMemcpyAsync(&nlong, place.as<int>() + Nc, sizeof(int), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+      CHK(scan_exclusive(ctx, place.as<int>(), place.as<int>(), (int)Nc + 1, &nlong));
       CHK(lrow.alloc((size_t)nlong * sizeof(int)));
       CHK(llen.alloc((size_t)nlong * sizeof(int)));
       CHK(koff.alloc(((size_t)nlong + 1) * sizeof(int)));
@@ -587,14 +583,9 @@ extern "C" int gspx_coarsen_build(gspx_graph* g, const int32_t* parent_host, int
     if (nlong > 0)
       hipLaunchKernelGGL(gspx::k_co_long_sort, dim3((unsigned)nlong), dim3(256), 0, st, toff.as<int>(), cc.as<int>(),
                          lrow.as<int>(), koff.as<int>(), keys.as<unsigned long long>(), h->rowptr.as<int>());
-    CHK(scan_exclusive(ctx, h->rowptr.as<int>(), h->rowptr.as<int>(), (int)Nc + 1));
-    int nnz = 0;
-    HIPCHK(hipMemcpyAsync(&nnz, h->rowptr.as<int>() + Nc, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    h->nnz = nnz;
+    CHK(adjacency_offsets(h.get(), h->rowptr.as<int>(), "coarsen_build"));  // lengths -> offsets, in place
+    const int nnz = (int)h->nnz;
     if (nnz > 0) {
-      CHK(h->col.alloc((size_t)nnz * sizeof(int)));
-      CHK(h->val.alloc((size_t)nnz * sizeof(double)));
       hipLaunchKernelGGL(gspx::k_co_fill, dim3(nbr), dim3(256), 0, st, toff.as<int>(), cc.as<int>(), wv.as<double>(),
                          head.as<unsigned char>(), h->rowptr.as<int>(), (int)Nc, gs, long_row, h->col.as<int>(),
                          h->val.as<double>());
@@ -610,8 +601,7 @@ extern "C" int gspx_coarsen_build(gspx_graph* g, const int32_t* parent_host, int
   } else {
     HIPCHK(hipStreamSynchronize(st));
   }
-  h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h.release();
+  adjacency_close(h, t0, out);
   return GSPX_OK;
 }
 

@@ -139,10 +139,9 @@ extern "C" int gspx_graph_components_dev(gspx_graph* g, int32_t* labels_dev, int
   // par is free now: it takes the marks, then their scan
   hipLaunchKernelGGL(k_cc_mark, grid, block, 0, st, lab.as<int>(), N, par.as<int>());
   HIPCHK(hipGetLastError());
-  CHK(scan_exclusive(ctx, par.as<int>(), par.as<int>(), N + 1));
-  if (labels_dev) hipLaunchKernelGGL(k_cc_rename, grid, block, 0, st, lab.as<int>(), par.as<int>(), N, labels_dev);
   int count = 0;
-  HIPCHK(hipMemcpyAsync(&count, par.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost, st));
+  CHK(scan_exclusive(ctx, par.as<int>(), par.as<int>(), N + 1, &count));
+  if (labels_dev) hipLaunchKernelGGL(k_cc_rename, grid, block, 0, st, lab.as<int>(), par.as<int>(), N, labels_dev);
   HIPCHK(hipEventRecord(ctx->ev[1], st));
   CHK(finish_timed(ctx, kernel_ms));
   *n_components = count;

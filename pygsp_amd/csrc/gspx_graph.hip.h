@@ -1,81 +1,12 @@
-// gspx_graph.hip.h - building a gspx_graph (replaces graph.py:510-630, 830-838): the int32 exclusive scan, CSR
-// validation, the Laplacian from W (or L as given), the internal padded CSR in the engine's vertex order, the gather
-// tiles of the LDS-staged step, the download entry points, and what is derived from a built graph on first use: the
+// gspx_graph.hip.h - building a gspx_graph (replaces graph.py:510-630, 830-838): CSR validation, the Laplacian from W
+// (or L as given), the internal padded CSR in the engine's vertex order, the gather tiles of the LDS-staged step, the
+// download entry points, and what is derived from a built graph on first use: the
 // scaled operator F of a given lmax (ensure_factor) and the gather lists as rows of an unpermuted panel (ensure_s1nat).
-// The kernels only these use come first.  After gspx_ctx.hip.h and the kernel headers (k_fill, gspx_tile_kernels.hip.h's
-// tile builders); gspx_ops / gspx_knn / gspx_setup / gspx_components use scan_exclusive and k_inverse_perm from here.
+// The kernels only these use come first.  After gspx_adjacency.hip.h (scan_exclusive) and the kernel headers (k_fill,
+// gspx_tile_kernels.hip.h's tile builders); gspx_setup uses k_inverse_perm from here.
 #pragma once
 
 namespace gspx {
-
-// ---------------------------------------------------------------------------------------------
-// exclusive scan of int32 (three small kernels; tile = 1024 elements)
-// ---------------------------------------------------------------------------------------------
-#define GSPX_SCAN_TILE 1024
-// (in and out may be the same array - radix_argsort scans its histogram in place: every thread reads its four
-// inputs before it writes its four outputs, and no thread touches another's - so neither is __restrict__)
-__global__ __launch_bounds__(256) void k_scan_tiles(const int* in, int n, int* out, int* __restrict__ tile_sums) {
-  __shared__ int wsum[4];
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int base = blockIdx.x * GSPX_SCAN_TILE + t * 4;
-  int v[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) v[k] = (base + k < n) ? in[base + k] : 0;
-  const int mine = v[0] + v[1] + v[2] + v[3];
-  int incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(incl, off);
-    if (lane >= off) incl += o;
-  }
-  if (lane == 63) wsum[wv] = incl;
-  __syncthreads();
-  int wbase = 0;
-  for (int k = 0; k < wv; ++k) wbase += wsum[k];
-  int run = wbase + incl - mine;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (base + k < n) out[base + k] = run;
-    run += v[k];
-  }
-  if (t == 255) tile_sums[blockIdx.x] = wbase + incl;
-}
-
-__global__ __launch_bounds__(256) void k_scan_sums(int* tile_sums, int ntiles) {
-  // single workgroup: serial over 256-element strips with a carry
-  __shared__ int wsum[4];
-  __shared__ int carry_s;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  if (t == 0) carry_s = 0;
-  __syncthreads();
-  for (int base = 0; base < ntiles; base += 256) {
-    const int i = base + t;
-    const int mine = i < ntiles ? tile_sums[i] : 0;
-    int incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off);
-      if (lane >= off) incl += o;
-    }
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    int wbase = carry_s;
-    for (int k = 0; k < wv; ++k) wbase += wsum[k];
-    if (i < ntiles) tile_sums[i] = wbase + incl - mine;
-    __syncthreads();
-    if (t == 255) carry_s = wbase + incl;
-    __syncthreads();
-  }
-}
-
-__global__ __launch_bounds__(256) void k_scan_add(int* __restrict__ out, int n,
-                                                  const int* __restrict__ tile_sums) {
-  const int add = tile_sums[blockIdx.x];
-  const int base = blockIdx.x * GSPX_SCAN_TILE + threadIdx.x * 4;
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (base + k < n) out[base + k] += add;
-}
 
 // ---------------------------------------------------------------------------------------------
 // graph build kernels (replace graph.py:618-628, 830-838)
@@ -330,23 +261,6 @@ __global__ void k_factor(const int* __restrict__ rptr, const int* __restrict__ r
 }  // namespace gspx
 
 // ------------------------------------------------------------------------------------------------
-// device exclusive scan of n int32 (in-place safe: out may equal in)
-// ------------------------------------------------------------------------------------------------
-static int scan_exclusive(gspx_ctx* ctx, const int* in, int* out, int n) {
-  if (n <= 0) return GSPX_OK;
-  const int ntiles = (n + GSPX_SCAN_TILE - 1) / GSPX_SCAN_TILE;
-  DevMem sums;
-  CHK(sums.alloc((size_t)ntiles * sizeof(int)));
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(256), 0, ctx->stream, in, n, out,
-                     sums.as<int>());
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, ctx->stream, sums.as<int>(), ntiles);
-  hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(256), 0, ctx->stream, out, n, sums.as<int>());
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return GSPX_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
 // graph construction
 // ------------------------------------------------------------------------------------------------
 static int validate_csr(int64_t N, int64_t nnz, const int32_t* indptr, const int32_t* indices) {
@@ -431,9 +345,8 @@ template <typename T> static int build_internal(gspx_graph* g) {
                        cnt.as<int>(), (int*)nullptr, (int*)nullptr, (T*)nullptr);
     HIPCHK(hipGetLastError());
   }
-  CHK(scan_exclusive(ctx, cnt.as<int>(), g->rptr.as<int>(), N + 1));
   int total = 0;
-  HIPCHK(hipMemcpy(&total, g->rptr.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost));
+  CHK(scan_exclusive(ctx, cnt.as<int>(), g->rptr.as<int>(), N + 1, &total));
   g->nnz_int = total;
   // rows past N read as empty: rowptr[N+1 .. N+16] = total
   hipLaunchKernelGGL((k_fill<int>), dim3(1), dim3(64), 0, ctx->stream, g->rptr.as<int>() + N + 1,
@@ -480,9 +393,8 @@ static int create_from_w_dev(gspx_graph* g, int64_t nnz, const int* wptr, const 
                        g->dw.as<T>(), N, lap_type, cnt.as<int>(), (int*)nullptr, (int*)nullptr, (T*)nullptr);
     HIPCHK(hipGetLastError());
   }
-  CHK(scan_exclusive(ctx, cnt.as<int>(), g->lptr.as<int>(), N + 1));
   int total = 0;
-  HIPCHK(hipMemcpy(&total, g->lptr.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost));
+  CHK(scan_exclusive(ctx, cnt.as<int>(), g->lptr.as<int>(), N + 1, &total));
   g->nnz_l = total;
   CHK(g->lcol.alloc((size_t)total * sizeof(int)));
   CHK(g->lval.alloc((size_t)total * sizeof(T)));
@@ -789,10 +701,8 @@ static int build_tiles_dev(gspx_graph* g, size_t lds, DevMem& hdr, DevMem& s1row
                      tmp.as<int>(), n1.as<int>());
   hipLaunchKernelGGL(k_tiles_keep, dim3((nb + 1 + 255) / 256), dim3(256), 0, st, n1.as<int>(), nb,
                      keep.as<int>());
-  CHK(scan_exclusive(ctx, keep.as<int>(), s1lo.as<int>(), nb + 1));
   int n_s1 = 0;
-  HIPCHK(hipMemcpyAsync(&n_s1, s1lo.as<int>() + nb, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  CHK(scan_exclusive(ctx, keep.as<int>(), s1lo.as<int>(), nb + 1, &n_s1));
   CHK(hdr.alloc((size_t)nb * 4 * sizeof(int) + 64));
   CHK(s1rows.alloc((size_t)std::max(n_s1, 1) * 4 + 64));
   CHK(lidx.alloc((size_t)g->nnz_int + 128));

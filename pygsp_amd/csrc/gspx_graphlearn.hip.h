@@ -39,7 +39,8 @@
 // The adjacency (w_out): count, scan, fill - one wavefront per vertex walks I(i) 64 entries at a time and keeps the
 // edges with P > 0 in place by ballot; tedge sources ascend and lie below i, the eoff targets ascend above it, so the
 // row is sorted as written, and both (s, t) and (t, s) carry the same P_e.
-// After gspx_fista.hip.h (FistaState, fista_totals; block_sums, finish_timed, edges_for, scan_exclusive, gspx_knn).
+// After gspx_fista.hip.h (FistaState, fista_totals; block_sums, finish_timed, edges_for, the adjacency frame of
+// gspx_adjacency.hip.h).
 #pragma once
 
 namespace gspx {
@@ -367,31 +368,21 @@ static int graphlearn_adjacency(gspx_graph* g, const gspx::GlTables& t, const gs
   hipStream_t st = ctx->stream;
   const int64_t N = g->N;
   const auto t0 = std::chrono::steady_clock::now();
-  std::unique_ptr<gspx_knn> h(new gspx_knn());
-  h->ctx = ctx;
-  h->N = N;
-  CHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
-  HIPCHK(hipMemsetAsync(h->rowptr.p, 0, ((size_t)N + 1) * sizeof(int), st));
+  std::unique_ptr<gspx_knn> h;
+  CHK(adjacency_open(ctx, N, h));
   if (N > 0 && t.E > 0) {
     const unsigned nbw = (unsigned)((N + 3) / 4);
     hipLaunchKernelGGL(gspx::k_gl_adjacency, dim3(nbw), dim3(256), 0, st, t, wP, h->rowptr.as<int>(), (const int*)nullptr,
                        (int*)nullptr, (double*)nullptr);
-    CHK(scan_exclusive(ctx, h->rowptr.as<int>(), h->rowptr.as<int>(), (int)N + 1));  // lengths -> offsets, in place
-    int total = 0;
-    HIPCHK(hipMemcpyAsync(&total, h->rowptr.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    h->nnz = total;
-    if (total > 0) {
-      CHK(h->col.alloc((size_t)total * sizeof(int)));
-      CHK(h->val.alloc((size_t)total * sizeof(double)));
+    CHK(adjacency_offsets(h.get(), h->rowptr.as<int>(), "learn_log_degrees"));  // lengths -> offsets, in place
+    if (h->nnz > 0) {
       hipLaunchKernelGGL(gspx::k_gl_adjacency, dim3(nbw), dim3(256), 0, st, t, wP, (int*)nullptr,
                          (const int*)h->rowptr.as<int>(), h->col.as<int>(), h->val.as<double>());
       HIPCHK(hipGetLastError());
     }
   }
   HIPCHK(hipStreamSynchronize(st));  // wP is the caller's to free after this
-  h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h.release();
+  adjacency_close(h, t0, out);
   return GSPX_OK;
 }
 

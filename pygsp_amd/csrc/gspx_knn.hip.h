@@ -1,7 +1,6 @@
 // gspx_knn.hip.h - neighbour graphs on the device: k nearest neighbours and, at the end of the file, the radius
-// search.  After gspx_graph.hip.h (scan_exclusive).  gfx950 only.  Also defines the handle
-// gspx_knn, which stands for any adjacency a device builder leaves on the device (the block-model sampler and the
-// line-graph builder make such handles too).
+// search.  After gspx_adjacency.hip.h (the handle gspx_knn and the builder's frame,
+// scan_exclusive).  gfx950 only.
 //
 // Replaces, for NNtype='knn' (1 <= d <= 3 by the grid search below; 4 <= d <= 4096 by the tiled brute force on the
 // matrix cores of gspx_knn_bf.hip.h; the weights / symmetrisation / CSR stages are shared):
@@ -368,17 +367,6 @@ __global__ void k_knn_row_sort(const int* __restrict__ rowptr, int N, int* __res
 
 }  // namespace gspx
 
-struct gspx_knn {
-  gspx_ctx* ctx = nullptr;
-  int64_t N = 0;
-  int d = 0, k = 0;
-  double sigma = 0.0;
-  int64_t nnz = 0;
-  double build_ms = 0.0;
-  double search_stats[4] = {0, 0, 0, 0};  // brute-force search (d > 3): sample, capacity, mean candidates, exact scans
-  DevMem nn, dist, rowptr, col, val;
-};
-
 #include "gspx_knn_bf.hip.h"
 
 // ---- what gspx_knn_build and gspx_radius_build share ------------------------------------------------------------
@@ -499,9 +487,8 @@ extern "C" int gspx_knn_build(gspx_ctx* ctx, int64_t N, int d, const double* coo
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   auto t0 = std::chrono::steady_clock::now();
-  std::unique_ptr<gspx_knn> h(new gspx_knn());
-  h->ctx = ctx;
-  h->N = N;
+  std::unique_ptr<gspx_knn> h;
+  CHK(adjacency_open(ctx, N, h));
   h->d = d;
   h->k = k;
   const int n = (int)N;
@@ -532,19 +519,12 @@ extern "C" int gspx_knn_build(gspx_ctx* ctx, int64_t N, int d, const double* coo
   CHK(w.alloc(nk * sizeof(double)));
   CHK(mutual.alloc(nk));
   CHK(len.alloc(((size_t)N + 1) * sizeof(int)));
-  CHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
   const int nbN = (n + 255) / 256;
   const unsigned nbE = (unsigned)((nk + 255) / 256);
   HIPCHK(hipMemsetAsync(len.p, 0, ((size_t)N + 1) * sizeof(int), st));
   hipLaunchKernelGGL(k_knn_weights, dim3(nbE), dim3(256), 0, st, h->nn.as<int>(), h->dist.as<double>(), n, k,
                      sigma, symmetrize, w.as<double>(), mutual.as<unsigned char>(), len.as<int>());
-  CHK(scan_exclusive(ctx, len.as<int>(), h->rowptr.as<int>(), n + 1));
-  int nnz = 0;
-  HIPCHK(hipMemcpyAsync(&nnz, h->rowptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  h->nnz = nnz;
-  CHK(h->col.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
-  CHK(h->val.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
+  CHK(adjacency_offsets(h.get(), len.as<int>(), "gspx_knn_build"));
   // (the row lengths are scanned: cleared again, their N + 1 counters are the rows' fill cursors)
   HIPCHK(hipMemsetAsync(len.p, 0, ((size_t)N + 1) * sizeof(int), st));
   hipLaunchKernelGGL(k_knn_fill, dim3(nbE), dim3(256), 0, st, h->nn.as<int>(), w.as<double>(),
@@ -552,8 +532,8 @@ extern "C" int gspx_knn_build(gspx_ctx* ctx, int64_t N, int d, const double* coo
                      h->val.as<double>());
   {
     DevMem col2, val2;
-    CHK(col2.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
-    CHK(val2.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
+    CHK(col2.alloc((size_t)h->nnz * sizeof(int)));
+    CHK(val2.alloc((size_t)h->nnz * sizeof(double)));
     hipLaunchKernelGGL(k_knn_row_rank, dim3(nbN), dim3(256), 0, st, h->rowptr.as<int>(), n, h->col.as<int>(),
                        h->val.as<double>(), col2.as<int>(), val2.as<double>());
     hipLaunchKernelGGL(k_knn_row_rank_long, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, h->rowptr.as<int>(), n,
@@ -565,41 +545,13 @@ extern "C" int gspx_knn_build(gspx_ctx* ctx, int64_t N, int d, const double* coo
     std::swap(h->val.p, val2.p);
     std::swap(h->val.bytes, val2.bytes);
   }
-  h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h.release();
-  return GSPX_OK;
-}
-
-extern "C" int gspx_knn_destroy(gspx_knn* h) {
-  if (!h) return GSPX_OK;
-  (void)hipSetDevice(h->ctx->device);
-  delete h;
-  return GSPX_OK;
-}
-
-extern "C" int gspx_knn_info(gspx_knn* h, int64_t* nnz, double* sigma, double* build_ms) {
-  if (!h) return set_err(GSPX_ERR_INVALID, "null handle");
-  if (nnz) *nnz = h->nnz;
-  if (sigma) *sigma = h->sigma;
-  if (build_ms) *build_ms = h->build_ms;
+  adjacency_close(h, t0, out);
   return GSPX_OK;
 }
 
 extern "C" int gspx_knn_search_stats(gspx_knn* h, double out[4]) {
   if (!h || !out) return set_err(GSPX_ERR_INVALID, "null argument");
   for (int i = 0; i < 4; ++i) out[i] = h->search_stats[i];
-  return GSPX_OK;
-}
-
-extern "C" int gspx_knn_download_w(gspx_knn* h, int32_t* indptr, int32_t* indices, double* data) {
-  if (!h || !indptr) return set_err(GSPX_ERR_INVALID, "null argument");
-  if (h->nnz > 0 && (!indices || !data)) return set_err(GSPX_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->ctx->device));
-  HIPCHK(hipMemcpy(indptr, h->rowptr.p, ((size_t)h->N + 1) * sizeof(int), hipMemcpyDeviceToHost));
-  if (h->nnz > 0) {
-    HIPCHK(hipMemcpy(indices, h->col.p, (size_t)h->nnz * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(data, h->val.p, (size_t)h->nnz * sizeof(double), hipMemcpyDeviceToHost));
-  }
   return GSPX_OK;
 }
 
@@ -704,9 +656,8 @@ extern "C" int gspx_radius_build(gspx_ctx* ctx, int64_t N, int d, const double* 
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   auto t0 = std::chrono::steady_clock::now();
-  std::unique_ptr<gspx_knn> h(new gspx_knn());
-  h->ctx = ctx;
-  h->N = N;
+  std::unique_ptr<gspx_knn> h;
+  CHK(adjacency_open(ctx, N, h));
   h->d = d;
   const int n = (int)N;
   DevMem x, cnt, partial;
@@ -715,7 +666,6 @@ extern "C" int gspx_radius_build(gspx_ctx* ctx, int64_t N, int d, const double* 
   CHK(x.alloc((size_t)N * d * sizeof(double)));
   if (grid_search) CHK(index.alloc(n, g));
   CHK(cnt.alloc(((size_t)N + 1) * sizeof(int)));
-  CHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
   HIPCHK(hipMemcpyAsync(x.p, coords, (size_t)N * d * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(cnt.p, 0, ((size_t)N + 1) * sizeof(int), st));
   const double eps2 = metric == 0 ? epsilon * epsilon : epsilon;  // threshold on the comparison key
@@ -732,15 +682,9 @@ extern "C" int gspx_radius_build(gspx_ctx* ctx, int64_t N, int d, const double* 
                        index.start.as<int>(), n, g, eps2, cnt.as<int>(), (const int*)nullptr, (int*)nullptr,
                        (double*)nullptr);
   }
-  CHK(scan_exclusive(ctx, cnt.as<int>(), h->rowptr.as<int>(), n + 1));
-  int nnz = 0;
-  HIPCHK(hipMemcpyAsync(&nnz, h->rowptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (nnz < 0) return set_err(GSPX_ERR_INVALID, "gspx_radius_build: more than 2^31 neighbour pairs");
-  h->nnz = nnz;
-  CHK(h->col.alloc((size_t)std::max(nnz, 1) * sizeof(int)));
-  CHK(h->val.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
-  CHK(h->dist.alloc((size_t)std::max(nnz, 1) * sizeof(double)));
+  CHK(adjacency_offsets(h.get(), cnt.as<int>(), "gspx_radius_build"));
+  const int nnz = (int)h->nnz;
+  CHK(h->dist.alloc((size_t)nnz * sizeof(double)));
   if (nnz > 0) {
     if (!grid_search)
       launch_bf_radius<1>(ctx, x.as<double>(), n, d, metric, eps2, swept ? c_off.as<int>() : nullptr,
@@ -764,7 +708,6 @@ extern "C" int gspx_radius_build(gspx_ctx* ctx, int64_t N, int d, const double* 
   h->sigma = sigma;
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
-  h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h.release();
+  adjacency_close(h, t0, out);
   return GSPX_OK;
 }

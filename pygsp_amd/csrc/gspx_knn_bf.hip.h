@@ -809,10 +809,8 @@ static int radius_candidates(gspx_ctx* ctx, const double* x, int N, int d, doubl
       return set_err(GSPX_ERR_INVALID, "gspx_radius_build: %lld candidate pairs, more than 2^31 (epsilon too large)",
                      (long long)total64);
   }
-  CHK(scan_exclusive(ctx, cnt.as<int>(), off.as<int>(), N + 1));
   int total_c = 0;
-  HIPCHK(hipMemcpyAsync(&total_c, off.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  CHK(scan_exclusive(ctx, cnt.as<int>(), off.as<int>(), N + 1, &total_c));
   if (total_c < 0) return set_err(GSPX_ERR_INVALID, "gspx_radius_build: more than 2^31 candidate pairs (epsilon too large)");
   CHK(buf.alloc((size_t)std::max(total_c, 1) * sizeof(int)));
   HIPCHK(hipMemsetAsync(cnt.p, 0, ((size_t)N + 1) * sizeof(int), st));

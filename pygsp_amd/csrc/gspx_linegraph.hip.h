@@ -1,6 +1,7 @@
 // gspx_linegraph.hip.h - the line graph of an undirected graph without self-loops, built on the device from the edge
 // tables of gspx_ops.hip.h (pygsp/graphs/linegraph.py forms B^T B - I with scipy on the host).  gfx950 only.
-// Included by gspx.hip after gspx_setup.hip.h (uses edges_for, scan_exclusive, gspx_knn, DevMem, HIPCHK, CHK).
+// Included by gspx.hip after gspx_setup.hip.h (uses edges_for, the adjacency frame and scan_exclusive of
+// gspx_adjacency.hip.h, DevMem, HIPCHK, CHK).
 //
 // Line-graph vertex e is edge e of Graph.get_edge_list(): the upper triangle of W in row-major order, in the caller's
 // vertex order.  For a vertex v, I(v) is the ascending list of the edges incident to v: the edges that END in v
@@ -174,12 +175,9 @@ extern "C" int gspx_linegraph_build(gspx_graph* g, gspx_knn** out, double* kerne
   hipStream_t st = ctx->stream;
   replay_reset(ctx);
   const auto t0 = std::chrono::steady_clock::now();
-  std::unique_ptr<gspx_knn> h(new gspx_knn());
-  h->ctx = ctx;
-  h->N = E;
-  h->nnz = nnz;
-  CHK(h->rowptr.alloc(((size_t)E + 1) * sizeof(int)));
-  HIPCHK(hipMemsetAsync(h->rowptr.p, 0, ((size_t)E + 1) * sizeof(int), st));
+  std::unique_ptr<gspx_knn> h;
+  CHK(adjacency_open(ctx, E, h));
+  h->nnz = nnz;  // known beforehand: col and val are allocated here, outside the timed bracket, not by adjacency_offsets
   if (nnz > 0) {
     DevMem partial;
     const unsigned nb = linegraph_len_blocks(E);
@@ -197,7 +195,6 @@ extern "C" int gspx_linegraph_build(gspx_graph* g, gspx_knn** out, double* kerne
   } else {
     HIPCHK(hipStreamSynchronize(st));
   }
-  h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h.release();
+  adjacency_close(h, t0, out);
   return GSPX_OK;
 }

@@ -443,12 +443,9 @@ template <typename T> static int ensure_edges(gspx_graph* g) {
   const int nb = (N + 255) / 256;
   hipLaunchKernelGGL(k_edge_count, dim3(nb), dim3(256), 0, st, g->lptr.as<int>(), g->lcol.as<int>(), N,
                      up.as<int>(), low.as<int>());
-  CHK(scan_exclusive(ctx, up.as<int>(), g->e_off.as<int>(), N + 1));
-  CHK(scan_exclusive(ctx, low.as<int>(), g->e_toff.as<int>(), N + 1));
   int E = 0, El = 0;
-  HIPCHK(hipMemcpyAsync(&E, g->e_off.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&El, g->e_toff.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  CHK(scan_exclusive(ctx, up.as<int>(), g->e_off.as<int>(), N + 1, &E));
+  CHK(scan_exclusive(ctx, low.as<int>(), g->e_toff.as<int>(), N + 1, &El));
   if (E != El) return set_err(GSPX_ERR_INVALID, "differential operator: the Laplacian pattern is not symmetric");
   const size_t e = (size_t)std::max(E, 1);
   CHK(g->e_src.alloc(e * sizeof(int)));

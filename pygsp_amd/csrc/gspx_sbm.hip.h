@@ -1,5 +1,6 @@
 // gspx_sbm.hip.h - stochastic block model / Erdos-Renyi sampler on the device (second half).
-// Included by gspx.hip after gspx_knn.hip.h (the result is a gspx_knn handle; uses k_knn_row_sort, scan_exclusive).
+// Included by gspx.hip after gspx_knn.hip.h (k_knn_row_sort); the result is an adjacency handle, built on the frame of
+// gspx_adjacency.hip.h (adjacency_open / _offsets / _close, scan_exclusive).
 //
 // The reference visits all N^2 ordered pairs in a Python loop and keeps pair (r > c) with probability
 // M[z_r][z_c] (pygsp/graphs/stochasticblockmodel.py:125-144; erdosrenyi.py is the one-block case).
@@ -171,12 +172,10 @@ extern "C" int gspx_sbm_build_ex(gspx_ctx* ctx, int64_t N, int k, const int32_t*
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   auto t0 = std::chrono::steady_clock::now();
-  std::unique_ptr<gspx_knn> h(new gspx_knn());
-  h->ctx = ctx;
-  h->N = N;
+  std::unique_ptr<gspx_knn> h;
+  CHK(adjacency_open(ctx, N, h));
   const int n = (int)N;
   DevMem dseg, dorder, cnt, off, er, ec, deg, cursor;
-  CHK(h->rowptr.alloc(((size_t)N + 1) * sizeof(int)));
   CHK(deg.alloc(((size_t)N + 1) * sizeof(int)));
   HIPCHK(hipMemsetAsync(deg.p, 0, ((size_t)N + 1) * sizeof(int), st));
   long long m = 0;
@@ -192,10 +191,8 @@ extern "C" int gspx_sbm_build_ex(gspx_ctx* ctx, int64_t N, int k, const int32_t*
     hipLaunchKernelGGL((k_sbm_chunks<0>), dim3(nbc), dim3(256), 0, st, dseg.as<SbmSeg>(), (int)segs.size(), nchunks,
                        (unsigned long long)seed, dorder.as<int>(), cnt.as<int>(), (const int*)nullptr,
                        (int*)nullptr, (int*)nullptr, (int*)nullptr, directed ? 1 : 0);
-    CHK(scan_exclusive(ctx, cnt.as<int>(), off.as<int>(), (int)nchunks + 1));
     int mi = 0;
-    HIPCHK(hipMemcpyAsync(&mi, off.as<int>() + nchunks, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    CHK(scan_exclusive(ctx, cnt.as<int>(), off.as<int>(), (int)nchunks + 1, &mi));
     if (mi < 0 || (long long)mi * 2 >= ((long long)1 << 31))
       return set_err(GSPX_ERR_INVALID, "gspx_sbm_build: more than 2^30 edges");
     m = mi;
@@ -205,13 +202,8 @@ extern "C" int gspx_sbm_build_ex(gspx_ctx* ctx, int64_t N, int k, const int32_t*
                        (unsigned long long)seed, dorder.as<int>(), (int*)nullptr, off.as<int>(), er.as<int>(),
                        ec.as<int>(), deg.as<int>(), directed ? 1 : 0);
   }
-  CHK(scan_exclusive(ctx, deg.as<int>(), h->rowptr.as<int>(), n + 1));
-  int stored = 0;  // 2 m for an undirected graph without self-loops; fewer with them, m when directed
-  HIPCHK(hipMemcpyAsync(&stored, h->rowptr.as<int>() + n, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  h->nnz = stored;
-  CHK(h->col.alloc((size_t)std::max<long long>(stored, 1) * sizeof(int)));
-  CHK(h->val.alloc((size_t)std::max<long long>(stored, 1) * sizeof(double)));
+  // (nnz: 2 m for an undirected graph without self-loops; fewer with them, m when directed)
+  CHK(adjacency_offsets(h.get(), deg.as<int>(), "gspx_sbm_build"));
   if (m > 0) {
     CHK(cursor.alloc(((size_t)N + 1) * sizeof(int)));
     HIPCHK(hipMemsetAsync(cursor.p, 0, ((size_t)N + 1) * sizeof(int), st));
@@ -222,7 +214,6 @@ extern "C" int gspx_sbm_build_ex(gspx_ctx* ctx, int64_t N, int k, const int32_t*
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
-  h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  *out = h.release();
+  adjacency_close(h, t0, out);
   return GSPX_OK;
 }

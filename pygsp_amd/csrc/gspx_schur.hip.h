@@ -1,7 +1,7 @@
 // gspx_schur.hip.h - Schur complements of A = L + shift I on the device: the harmonic extension at a shift with the kept
 // rows of A x (gspx_schur_cg_dev), and the Kron reduction built from it (gspx_kron_build; pygsp/reduction.py:309-381
 // solves A_uu directly with spsolve).  gfx950 only.  Included by gspx.hip after gspx_linegraph.hip.h (uses the
-// harmonic frame of gspx_ops.hip.h, scan_exclusive, gspx_knn, DevMem, HIPCHK, CHK).
+// harmonic frame of gspx_ops.hip.h, the adjacency frame of gspx_adjacency.hip.h, DevMem, HIPCHK, CHK).
 //
 // With kept set k and eliminated set u the Schur complement A_kk - A_ku A_uu^-1 A_uk is rows k of A X, where X holds the
 // indicator columns of the kept vertices extended by A_uu X_u = -A_uk: the solve gspx_dirichlet_cg_dev runs for
@@ -249,22 +249,12 @@ extern "C" int gspx_kron_build(gspx_graph* g, double shift, const int32_t* ind_h
   HIPCHK(hipGetLastError());
   std::unique_ptr<gspx_knn> h;
   if (w_out) {
-    h.reset(new gspx_knn());
-    h->ctx = ctx;
-    h->N = nk;
-    CHK(h->rowptr.alloc(((size_t)nk + 1) * sizeof(int)));
-    HIPCHK(hipMemsetAsync(h->rowptr.p, 0, ((size_t)nk + 1) * sizeof(int), st));
+    CHK(adjacency_open(ctx, nk, h));
     const unsigned nbw = (unsigned)((nk + 3) / 4);
     hipLaunchKernelGGL(gspx::k_kron_w, dim3(nbw), dim3(256), 0, st, L, (int)nk, h->rowptr.as<int>(),
                        (const int*)nullptr, (int*)nullptr, (double*)nullptr);
-    CHK(scan_exclusive(ctx, h->rowptr.as<int>(), h->rowptr.as<int>(), (int)nk + 1));  // lengths -> offsets, in place
-    int total = 0;
-    HIPCHK(hipMemcpyAsync(&total, h->rowptr.as<int>() + nk, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    h->nnz = total;
-    if (total > 0) {
-      CHK(h->col.alloc((size_t)total * sizeof(int)));
-      CHK(h->val.alloc((size_t)total * sizeof(double)));
+    CHK(adjacency_offsets(h.get(), h->rowptr.as<int>(), "kron_build"));  // lengths -> offsets, in place
+    if (h->nnz > 0) {
       hipLaunchKernelGGL(gspx::k_kron_w, dim3(nbw), dim3(256), 0, st, L, (int)nk, (int*)nullptr,
                          (const int*)h->rowptr.as<int>(), h->col.as<int>(), h->val.as<double>());
       HIPCHK(hipGetLastError());
@@ -274,9 +264,6 @@ extern "C" int gspx_kron_build(gspx_graph* g, double shift, const int32_t* ind_h
   CHK(finish_timed(ctx, kernel_ms));
   lap(mk.e[0], ctx->ev[1], &phase[2]);
   for (int i = 0; i < 5; ++i) ctx->timing[i] = i < 3 ? phase[i] : 0.0;
-  if (h) {
-    h->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *w_out = h.release();
-  }
+  if (h) adjacency_close(h, t0, w_out);
   return GSPX_OK;
 }

@@ -1,4 +1,4 @@
-// gspx_setup.hip.h - graph set-up in ONE call, on the device.  After gspx_knn.hip.h.
+// gspx_setup.hip.h - graph set-up in ONE call, on the device.  After gspx_graph.hip.h and gspx_adjacency.hip.h.
 //
 // What pygsp/graphs/graph.py:98-176 + 510-630 do to a weight matrix before the first filter call - the checks
 // of Graph.__init__ (NaN / inf, self-loops, negative weights, graph.py:108-134), the directedness test
@@ -397,9 +397,8 @@ static int symmetrize_dev(gspx_ctx* ctx, int N, int64_t nnz, const int* wptr, co
   hipLaunchKernelGGL((gspx::k_sym_merge<TIn, false>), dim3(nb), dim3(256), 0, st, wptr, wcol, wval, tptr.as<int>(),
                      order.as<int>(), rows.as<int>(), N, sptr.as<int>(), (const int*)nullptr, (int*)nullptr, (TS*)nullptr);
   HIPCHK(hipGetLastError());
-  CHK(scan_exclusive(ctx, sptr.as<int>(), sptr.as<int>(), N + 1));
   int total = 0;
-  HIPCHK(hipMemcpy(&total, sptr.as<int>() + N, sizeof(int), hipMemcpyDeviceToHost));
+  CHK(scan_exclusive(ctx, sptr.as<int>(), sptr.as<int>(), N + 1, &total));
   *snnz = total;
   CHK(scol.alloc((size_t)std::max(total, 1) * 4));
   CHK(sval.alloc((size_t)std::max(total, 1) * sizeof(TS)));

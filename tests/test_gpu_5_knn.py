@@ -10,6 +10,7 @@ import functools
 
 import numpy as np
 import pytest
+from scipy import sparse
 
 from conftest import csr_from
 from oracle import knn_oracle as knn
@@ -297,6 +298,27 @@ def test_radius_graphs(ctx, golden_knn):
         engine.radius_graph(rng.uniform(0, 1, (50, 2)) * 100, 0.01, ctx=ctx)   # "No neighbors found"
     with pytest.raises(ValueError):
         graphs.NNGraph(g["Xr"], NNtype="hexagon")
+
+
+def test_radius_graph_empty(ctx):
+    """No pair within epsilon and sigma given: an empty 50 x 50 matrix (with sigma omitted the same cloud is the
+    "No neighbors found" error of test_radius_graphs), on the host and through a device handle."""
+    X = np.random.default_rng(17).uniform(0, 1, (50, 2)) * 100
+    W, sigma, _ = engine.radius_graph(X, 0.01, sigma=1.0, ctx=ctx)
+    Wd, sigma_d, _ = engine.radius_graph(X, 0.01, sigma=1.0, ctx=ctx, keep_on_device=True)
+    assert Wd.shape == (50, 50) and Wd.nnz == 0
+    for M, sg in ((W, sigma), (Wd.download(), sigma_d)):
+        assert sparse.isspmatrix_csr(M) and M.shape == (50, 50) and M.nnz == 0 and sg == 1.0
+        np.testing.assert_array_equal(M.indptr, np.zeros(51, dtype=np.int32))
+        assert M.indices.size == 0 and M.data.size == 0
+
+
+def test_sbm_graph_empty(ctx):
+    """A block model whose only probability is zero: an empty 5 x 5 matrix, undirected and directed."""
+    for directed in (False, True):
+        W, _ = engine.sbm_graph(np.zeros(5, int), [[0.0]], seed=1, ctx=ctx, directed=directed)
+        assert sparse.isspmatrix_csr(W) and W.shape == (5, 5) and W.nnz == 0
+        np.testing.assert_array_equal(W.indptr, np.zeros(6, dtype=np.int32))
 
 
 def test_other_metrics(ctx, golden_knn):

@@ -649,6 +649,35 @@ int gspx_bench_gather(gspx_ctx* ctx, int64_t panel_rows, int row_bytes, int64_t 
  * out[2] this handle's rank (ncclCommUserRank; -1 for NULL). */
 int gspx_comm_info(gspx_comm* comm, int64_t out[3]);
 
+/* k-means on a row-major fp64 device panel X (N x d, pitch ldx >= d doubles): pygsp_amd/clustering.py.  Limits:
+ * 1 <= d <= 128, 1 <= C <= min(N, 1024), C * d <= 8192 (64 KiB of centroids; the assignment kernel keeps them in LDS
+ * at a padded pitch, up to 91 456 bytes with its staging and reduction space, the update kernel up to 79 872 bytes);
+ * anything else is GSPX_ERR_INVALID.  Squared distances are acc = acc + (x_j - c_j) * (x_j - c_j), j = 0 .. d - 1, without FMA; every sum
+ * has one fixed order, no atomics, the same bits on every call.
+ *
+ * gspx_kmeans_block_rows: update_rows = the rows per block of the update's and the seeding's partial sums (a constant),
+ * assign_rows = the rows per workgroup of the assignment kernel, whose partial inertia is summed per workgroup (a
+ * function of d alone).  Needs no device.
+ *
+ * gspx_kmeans_dev: Lloyd's iteration from the C x d centroids in `cent` (device, dense rows; overwritten with the
+ * result).  Assign; stop converged when no label changed (the first assignment counts every row); stop unconverged
+ * when max_iter updates have been made; else update and repeat.  labels (device, N int32), mind (device, N doubles or
+ * NULL: each row's squared distance to its centroid) and *inertia belong to the returned centroids; *n_iter = updates
+ * made.  A cluster without members keeps its centroid.
+ *
+ * gspx_kmeans_seed_dev: k-means++ from C host draws u[c] in [0, 1): the chosen rows are copied to `cent` (device,
+ * C x d) and their indices to `chosen` (host).  The rule is stated above the function in csrc/gspx_cluster.hip.h.
+ *
+ * gspx_rows_normalize_dev: in place, each row divided by the square root of acc = acc + x_j * x_j; a zero row stays
+ * (any d >= 1). */
+int gspx_kmeans_block_rows(int d, int* update_rows, int* assign_rows);
+int gspx_kmeans_dev(gspx_ctx* ctx, int64_t N, int d, int C, const double* X, int64_t ldx, double* cent,
+                    int64_t max_iter, int32_t* labels, double* mind, double* inertia, int64_t* n_iter,
+                    int32_t* converged, double* kernel_ms);
+int gspx_kmeans_seed_dev(gspx_ctx* ctx, int64_t N, int d, int C, const double* X, int64_t ldx, const double* u,
+                         double* cent, int64_t* chosen, double* kernel_ms);
+int gspx_rows_normalize_dev(gspx_ctx* ctx, int64_t N, int d, double* X, int64_t ldx, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

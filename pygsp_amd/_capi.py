@@ -154,6 +154,14 @@ SIGNATURES = {
                                          _c.POINTER(_c.c_double)]),
     "gspx_segment_pool_vjp_dev": (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P, _P, _P,
                                              _P, _c.POINTER(_c.c_double)]),
+    # k-means (pygsp_amd/clustering.py)
+    "gspx_kmeans_block_rows": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "gspx_kmeans_dev": (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _P, _c.c_int64, _P, _c.c_int64, _P, _P,
+                                   _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32),
+                                   _c.POINTER(_c.c_double)]),
+    "gspx_kmeans_seed_dev": (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _P, _c.c_int64, _P, _P, _P,
+                                        _c.POINTER(_c.c_double)]),
+    "gspx_rows_normalize_dev": (_c.c_int, [_P, _c.c_int64, _c.c_int, _P, _c.c_int64, _c.POINTER(_c.c_double)]),
     # graph learning (pygsp_amd/graph_learning.py)
     "gspx_edge_sqdist_dev": (_c.c_int, [_P, _c.c_int64, _P, _P, _c.POINTER(_c.c_double)]),
     "gspx_learn_log_degrees_dev": (_c.c_int, [_P, _P, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_int64,

@@ -98,3 +98,4 @@ extern "C" const char* gspx_version(void) { return "gspx 0.1 (gfx950)"; }
 #include "gspx_optim.hip.h"       // prox_tv: the graph total-variation proximal operator             (on ops, fista)
 #include "gspx_layout.hip.h"      // spring layout: all-pairs repulsion, attraction and update        (on ops)
 #include "gspx_coarsen.hip.h"     // heavy-edge matching, coarse graphs, segment pooling and its vjp     (on graph, adjacency)
+#include "gspx_cluster.hip.h"     // k-means: assignment, update, k-means++ seeding, row normalisation (on ops)
